@@ -38,9 +38,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="timed windows of --steps steps each; `value` is the FIRST window (exactly --steps steps between fences), "
-                         "the others give value_windows (median / min / max)")
+                         "the others give value_windows (median / min / max).  Default 1: --steps is the number of timed steps")
     ap.add_argument("--n-raw", type=int, default=100001)
     ap.add_argument("--keyframes", type=int, default=250)
     ap.add_argument("--kf-n-raw", type=int, default=30001)
@@ -78,7 +78,13 @@ def parse():
     ap.add_argument("--sequential-scans", type=int, default=48,
                     help="secondary figure (rank 0): a sequential replay — raw stream -> pose -> keyframe -> next scan — through the C++ node "
                          "code (host/lvi_host.hpp) with the incremental local map and with the full per-scan assembly; 0 = skip")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its LAST timed step (the pose records "
+                         "lvi_scan_batch_run hands its caller, every rank's) as DIR/<name>.npy, float32 / float64")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def main():
@@ -296,6 +302,25 @@ def main():
         if len(rows):
             ok = ok and bool((rows.view(np.uint32) == rows[0].view(np.uint32)).all())
 
+    # ---------------------------------------------------------------- --dump-outputs: the records of the last timed step, all ranks
+    dumped = None
+    if args.dump_outputs:
+        last = step0 + args.warmup + n_windows * args.steps - 1
+        rows = d_rec[last * per_step:(last + 1) * per_step]
+        if use_dist:
+            rows = R.gather_records(rows, world, dist, force=True).reshape(world * per_step, 8)      # every rank issues this collective
+        if rank == 0:
+            last_rec = rows.cpu().numpy()
+            sid = np.array([r * args.pool + (j % args.pool) for r in range(world) for j in range(last * per_step, (last + 1) * per_step)])
+            arrays = dict(pose=last_rec[:, 0:6].copy(),                                        # float32 [roll, pitch, yaw, x, y, z] per scan
+                          status=last_rec[:, 6].copy().view(np.int32).astype(np.float64),
+                          iters=last_rec[:, 7].copy().view(np.int32).astype(np.float64),
+                          scan_id=sid.astype(np.float64))                                      # global scan id: the seed of its input
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in arrays.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            dumped = dict(dir=args.dump_outputs, step=last, files={k: list(a.shape) for k, a in arrays.items()})
+
     # ---------------------------------------------------------------- tracker leg (secondary metric: LK frames/sec), frame pairs sharded over the ranks
     # (runs before the profiled pass: measured on this runtime, once a pass with HIP timing events has run in the process,
     # every later 0.9 MB frame upload of the tracker takes ~1 ms instead of ~40 us)
@@ -444,6 +469,8 @@ def main():
                      for s in stats[:14]],
         setup_s=round(setup_s, 1),
     )
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if tracker_out is not None:
         out["tracker"] = tracker_out
     if seq_out is not None:

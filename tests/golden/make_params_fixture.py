@@ -1,6 +1,6 @@
-"""TEST INFRASTRUCTURE — run in the build container (the reference tree does not travel to the GPU box):
-parses /root/reference/config_pkg/config/params_{lidar,camera}.yaml with the harness' own loader and commits the values
-the hot path reads as tests/golden/reference_params.json (data, not source).    python tests/golden/make_params_fixture.py"""
+"""TEST INFRASTRUCTURE — parses the reference's config_pkg/config/params_{lidar,camera}.yaml (copies stored in this
+directory) with the harness' own loader and commits the values the hot path reads as tests/golden/reference_params.json
+(data, not source).    python tests/golden/make_params_fixture.py"""
 import json
 import os
 import sys
@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import __graft_entry__ as graft  # noqa: E402
 
-REF = "/root/reference/config_pkg/config"
+REF = os.path.dirname(os.path.abspath(__file__))
 
 
 def parse():

@@ -225,7 +225,7 @@ os.environ["LVI_BENCH_DEVICE"] = "cpu"
 import bench
 sys.argv = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2", "--prime-steps", "2", "--profile-steps", "1",
             "--n-raw", "5001", "--keyframes", "5", "--kf-n-raw", "5001", "--map-points", "20000", "--pool", "3", "--inflight", "2", "--batch", "2",
-            "--icp-iters", "6", "--no-cpu", "--tracker-seconds", "0.05", "--sequential-scans", "0", "--cached-plan-steps", "2"]
+            "--icp-iters", "6", "--no-cpu", "--tracker-seconds", "0.05", "--sequential-scans", "0", "--cached-plan-steps", "2"] + %(extra)r
 bench.main()
 """
 
@@ -237,7 +237,7 @@ def test_bench_main_two_ranks_gloo(tmp_path):
     import json
     port = _free_port()
     script = tmp_path / "bench_worker.py"
-    script.write_text(BENCH_WORKER % dict(root=ROOT))
+    script.write_text(BENCH_WORKER % dict(root=ROOT, extra=["--dump-outputs", "dump"]))
     procs = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="2")
@@ -253,3 +253,34 @@ def test_bench_main_two_ranks_gloo(tmp_path):
     assert d["results_ok"] is True, d["pose_err_vs_truth"]
     assert len(d["tracker"]["per_rank"]) == 2 and d["tracker"]["value"] > 0
     assert d["value_cached_plan"]["scans_per_sec"] > 0
+    import numpy as np                                          # --dump-outputs: both ranks' records of the last timed step, on rank 0
+    assert d["dump_outputs"]["step"] == 2 + 1 + 2 * 3 - 1
+    sid = np.load(tmp_path / "dump" / "scan_id.npy")
+    assert sid.tolist() == [r * 3 + (8 * 4 + j) % 3 for r in range(2) for j in range(4)]
+    assert np.load(tmp_path / "dump" / "pose.npy").shape == (8, 6) and (np.load(tmp_path / "dump" / "iters.npy") == 6).all()
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs DIR (one rank, oracle-backed handles): the pose records of the last timed step as .npy files,
+    float32 / float64, identical from run to run; --steps sets the number of timed steps"""
+    import json
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        script = tmp_path / ("bench_dump_%d.py" % run)
+        script.write_text(BENCH_WORKER.replace('"--gpus", "2"', '"--gpus", "1"') % dict(root=ROOT, extra=["--dump-outputs", "dump%d" % run, "--no-tracker"]))
+        env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", OMP_NUM_THREADS="2")
+        p = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, cwd=str(tmp_path), timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and len(d["value_windows"]["window_s"]) == 2 and d["results_ok"] is True
+        # prime 2 + warm-up 1 + 2 windows x 3 timed steps: the last timed step is step 8
+        assert d["dump_outputs"]["step"] == 2 + 1 + 2 * 3 - 1
+        dumps.append({n: np.load(tmp_path / ("dump%d" % run) / (n + ".npy")) for n in ("pose", "status", "iters", "scan_id")})
+    a, b = dumps
+    assert a["pose"].dtype == np.float32 and a["pose"].shape == (2 * 2, 6)
+    assert all(x.dtype == np.float64 and x.shape == (4,) for k, x in a.items() if k != "pose")
+    assert (a["status"] == 0).all() and (a["iters"] == 6).all()
+    assert a["scan_id"].tolist() == [(8 * 4 + j) % 3 for j in range(4)]
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
