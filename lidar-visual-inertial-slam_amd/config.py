@@ -46,3 +46,10 @@ def load_camera_yaml(path):
     node = dict(freq=int(d["freq"]) or 100, F_threshold=float(d["F_threshold"]), equalize=int(d["equalize"]), fisheye=int(d["fisheye"]),
                 image_width=int(d["image_width"]), image_height=int(d["image_height"]), image_topic=d["image_topic"], point_cloud_topic=d["point_cloud_topic"])
     return tracker, cam, node
+
+
+def load_camera_lidar_yaml(path):
+    """→ the lidar depth settings of the camera yaml (parameters.cpp: USE_LIDAR, LIDAR_SKIP, POINT_CLOUD_TOPIC):
+    dict(use_lidar, lidar_skip, point_cloud_topic), the keyword arguments of the depth register and the node"""
+    d = _opencv_yaml(path)
+    return dict(use_lidar=int(d["use_lidar"]), lidar_skip=int(d["lidar_skip"]), point_cloud_topic=str(d["point_cloud_topic"]))

@@ -201,6 +201,9 @@ int32_t lvh_trk_image(lvh_trk* t, const uint8_t* img, double stamp, int32_t* out
         return LVI_OK;
     });
 }
+// the node object, for translation units that install hooks on it (host/lvi_depth_capi.cpp: the depth register)
+void* lvh_trk_node(lvh_trk* t) { return t ? t->node.get() : nullptr; }
+
 // cur_pts / ids / track_cnt of the tracker after the last callback: [n][4] = x, y, id, track_cnt
 int32_t lvh_trk_points(lvh_trk* t, float* rows, int32_t capacity, int32_t* n)
 {

@@ -3,8 +3,9 @@
 // discontinuity restart, frequency control, readImage (CLAHE + pyramidal LK + Shi-Tomasi on the MI355X), updateID, message
 // assembly, first-publish suppression — is lvi_host::FeatureTrackerNode; this file converts messages.  rejectWithF's RANSAC
 // stays OpenCV on the host (cv::findFundamentalMat), installed as the tracker's hook.  The lidar depth association
-// (DepthRegister) is outside the hot path: the depth channel carries the reference's "no depth" value -1 unless the
-// node installs get_depth.  Builds only where rclcpp, image_transport, cv_bridge and OpenCV exist.
+// (lidar_callback :273-377 and DepthRegister::get_depth, feature_tracker.h:116-331) is lvi_host::DepthRegister on the
+// MI355X, installed as the node's get_depth; the TF lookups (vins_world <- vins_body_ros at Time(0)) stay here.
+// Builds only where rclcpp, image_transport, cv_bridge, OpenCV, PCL (fromROSMsg) and tf2 exist.
 #include <cv_bridge/cv_bridge.h>
 #include <image_transport/image_transport.hpp>
 #include <opencv2/calib3d.hpp>
@@ -12,18 +13,60 @@
 #include <sensor_msgs/msg/channel_float32.hpp>
 #include <sensor_msgs/msg/image.hpp>
 #include <sensor_msgs/msg/point_cloud.hpp>
+#include <sensor_msgs/msg/point_cloud2.hpp>
 #include <std_msgs/msg/bool.hpp>
+#include <pcl_conversions/pcl_conversions.h>
+#include <tf2/LinearMath/Matrix3x3.h>
+#include <tf2_geometry_msgs/tf2_geometry_msgs.hpp>
+#include <tf2_ros/buffer.h>
+#include <tf2_ros/transform_listener.h>
 
+#include <mutex>
+
+#include "../lvi_depth_host.hpp"
 #include "../lvi_host.hpp"
 #include "camodocal/camera_models/CameraFactory.h"
 #include "camodocal/camera_models/CataCamera.h"
-#include "parameters.h"   // the reference's readParameters(): ROW, COL, MAX_CNT, MIN_DIST, FREQ, F_THRESHOLD, EQUALIZE, CAM_NAMES (feature_tracker/src/parameters.h)
+#include "parameters.h"   // the reference's readParameters(): ROW, COL, MAX_CNT, MIN_DIST, FREQ, F_THRESHOLD, EQUALIZE, CAM_NAMES,
+                          // POINT_CLOUD_TOPIC, LIDAR_SKIP (feature_tracker/src/parameters.h)
 
 static std::unique_ptr<lvi_host::TrackerHandle> handle;
 static std::unique_ptr<lvi_host::FeatureTracker> tracker;
 static std::unique_ptr<lvi_host::FeatureTrackerNode> node_logic;
 static rclcpp::Publisher<sensor_msgs::msg::PointCloud>::SharedPtr pub_feature;
 static rclcpp::Publisher<std_msgs::msg::Bool>::SharedPtr pub_restart;
+static std::unique_ptr<lvi_host::DepthRegister> depth_register;
+static std::shared_ptr<tf2_ros::Buffer> tfBuffer;
+static std::shared_ptr<tf2_ros::TransformListener> listener;
+static std::mutex mtx_depth;                      // the two callbacks run on a 2-thread executor; the handle is used by one at a time
+
+// the reference's TF lookup (vins_world <- vins_body_ros, Time(0)) as (x, y, z, roll, pitch, yaw); false when it throws
+static bool lookup_body_pose(const rclcpp::Duration& timeout, lvi_host::BodyPose& pose)
+{
+    tf2::Stamped<tf2::Transform> t;
+    try {
+        tf2::fromMsg(tfBuffer->lookupTransform("vins_world", "vins_body_ros", rclcpp::Time(0), timeout), t);
+    } catch (tf2::TransformException&) {
+        return false;
+    }
+    double r, p, y;
+    tf2::Matrix3x3(t.getRotation()).getRPY(r, p, y);
+    pose = lvi_host::BodyPose{{(float)t.getOrigin().x(), (float)t.getOrigin().y(), (float)t.getOrigin().z(), (float)r, (float)p, (float)y}};
+    return true;
+}
+
+void lidar_callback(const sensor_msgs::msg::PointCloud2::SharedPtr laser_msg)      // :273-377
+{
+    pcl::PointCloud<pcl::PointXYZI> cloud;
+    pcl::fromROSMsg(*laser_msg, cloud);
+    std::vector<lvi_pt> pts(cloud.size());
+    for (size_t i = 0; i < cloud.size(); i++) pts[i] = lvi_pt{cloud[i].x, cloud[i].y, cloud[i].z, cloud[i].intensity};
+    lvi_host::BodyPose pose;
+    const bool have = lookup_body_pose(rclcpp::Duration::from_seconds(0.01), pose);
+    const double stamp = laser_msg->header.stamp.sec + laser_msg->header.stamp.nanosec * 1e-9;
+    std::lock_guard<std::mutex> lock(mtx_depth);
+    depth_register->lidar_callback(pts, have ? &pose : nullptr, stamp);    // skip counting first, as the reference
+}
 
 void img_callback(const sensor_msgs::msg::Image::ConstSharedPtr img_msg)
 {
@@ -38,7 +81,11 @@ void img_callback(const sensor_msgs::msg::Image::ConstSharedPtr img_msg)
     cv::Mat img = ptr->image.rowRange(0, ROW);
     if (!img.isContinuous()) img = img.clone();
     lvi_host::FeatureMsg m;
+    std::unique_lock<std::mutex> lock(mtx_depth);
+    lvi_host::BodyPose pose;                                                            // get_depth's TF lookup (feature_tracker.h:134-146)
+    depth_register->set_image_pose(lookup_body_pose(rclcpp::Duration::from_seconds(0.0), pose) ? &pose : nullptr);
     const auto outcome = node_logic->img_callback(img.data, cur_img_time, &m);
+    lock.unlock();
     if (outcome == lvi_host::FeatureTrackerNode::RESTART) {                             // :50-59
         std_msgs::msg::Bool restart_flag; restart_flag.data = true;
         pub_restart->publish(restart_flag);
@@ -82,8 +129,14 @@ int main(int argc, char** argv)
         status.assign(st.begin(), st.end());
     };
     node_logic = std::make_unique<lvi_host::FeatureTrackerNode>(*tracker, FREQ);
+    // DepthRegister (:404) + the lidar window: 5 s of clouds at up to 20 Hz, 2^18 points per cloud
+    depth_register = std::make_unique<lvi_host::DepthRegister>(0, 101, 1 << 18, p.max_features, LIDAR_SKIP, 5.0);
+    depth_register->install(*node_logic);
+    tfBuffer = std::make_shared<tf2_ros::Buffer>(n->get_clock());
+    listener = std::make_shared<tf2_ros::TransformListener>(*tfBuffer);
     image_transport::ImageTransport it(n);                                              // :410-416
     image_transport::Subscriber sub = it.subscribe("/camera/image_raw", 10, img_callback);
+    auto sub_lidar = n->create_subscription<sensor_msgs::msg::PointCloud2>(POINT_CLOUD_TOPIC, rclcpp::QoS(rclcpp::KeepLast(100)), lidar_callback);
     pub_feature = n->create_publisher<sensor_msgs::msg::PointCloud>("/vins/feature/feature", 1000);
     pub_restart = n->create_publisher<std_msgs::msg::Bool>("/vins/feature/restart", 1000);
     RCLCPP_INFO(rclcpp::get_logger("rclcpp"), "\033[1;32m----> VINS Feature Extraction Started (MI355X).\033[0m");

@@ -31,14 +31,20 @@ class SeqResult(C.Structure):
 FUNDAMENTAL_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_double, C.POINTER(C.c_uint8), C.c_void_p)
 
 
-def build_host_library(out_path, link_dir, link_name, extra=()):
-    """g++ -shared of host/lvi_seq_capi.cpp against lib<link_name>.so in link_dir (rpath set)"""
-    src = os.path.join(HOST_DIR, "lvi_seq_capi.cpp")
-    deps = [src, os.path.join(HOST_DIR, "lvi_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_hotpath.h")]
+# the depth register's flattening (include/lvi_depth.h is exported by liblvi_hip.so only): linked into the HIP host library alone
+DEPTH_SOURCES = ("lvi_depth_capi.cpp",)
+
+
+def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
+    """g++ -shared of host/lvi_seq_capi.cpp (+ the named host/ sources) against lib<link_name>.so in link_dir (rpath set)"""
+    srcs = [os.path.join(HOST_DIR, "lvi_seq_capi.cpp")] + [os.path.join(HOST_DIR, f) for f in sources]
+    deps = srcs + [os.path.join(HOST_DIR, "lvi_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_hotpath.h")]
+    if sources:
+        deps += [os.path.join(HOST_DIR, "lvi_depth_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_depth.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
-    cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", out_path, src, "-L" + link_dir, "-l" + link_name,
+    cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", out_path, *srcs, "-L" + link_dir, "-l" + link_name,
            "-Wl,-rpath," + link_dir, *extra]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -72,6 +78,17 @@ class HostLibrary:
         d.lvh_trk_image.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int32,
                                     C.POINTER(C.c_int32)]
         d.lvh_trk_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        self.has_depth = hasattr(d, "lvh_depth_create")      # the HIP host library only
+        if self.has_depth:
+            d.lvh_depth_last_error.restype = C.c_char_p
+            d.lvh_depth_create.restype = C.c_void_p
+            d.lvh_depth_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double]
+            d.lvh_depth_destroy.argtypes = [C.c_void_p]
+            d.lvh_depth_handle.restype = C.c_void_p
+            d.lvh_depth_handle.argtypes = [C.c_void_p]
+            d.lvh_depth_install.argtypes = [C.c_void_p, C.c_void_p]
+            d.lvh_depth_lidar.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_int32)]
+            d.lvh_depth_set_image_pose.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
 
     def check(self, code, where):
         if code < 0:
@@ -213,3 +230,50 @@ class TrackerNode:
         rows = np.zeros((self.cap, 4), np.float32)
         self.hl.check(self.hl.dll.lvh_trk_points(self._t, A._ptr(rows), self.cap, C.byref(n)), "lvh_trk_points")
         return rows[:n.value].copy()
+
+
+class NodeDepthRegister:
+    """lvi_host::DepthRegister (host/lvi_depth_host.hpp) installed as the get_depth of a TrackerNode: the node's
+    lidar_callback (feature_tracker_node.cpp:273-377) and the depth channel of its messages.  pose6 = (x, y, z, roll,
+    pitch, yaw) of the body in the world frame, or None for a failed TF lookup.  HIP host library only."""
+
+    def __init__(self, hostlib, node, abi_lib, device=0, max_clouds=64, max_cloud_points=131072, max_features=150, lidar_skip=3, window_s=5.0):
+        from .depth import DepthRegister, bind as depth_bind
+        if not hostlib.has_depth:
+            raise RuntimeError("this host library has no depth register (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        self._d = hostlib.dll.lvh_depth_create(int(device), int(max_clouds), int(max_cloud_points), int(max_features), int(lidar_skip), float(window_s))
+        if not self._d:
+            raise A.LviError(-3, "lvh_depth_create", hostlib.dll.lvh_depth_last_error().decode(errors="replace"))
+        self._check(hostlib.dll.lvh_depth_install(self._d, node._t), "lvh_depth_install")
+        self.node = node
+        # a DepthRegister view of the handle the C++ side owns (debug views; never destroyed from here)
+        self.register = DepthRegister.__new__(DepthRegister)
+        self.register.lib = depth_bind(abi_lib)
+        self.register.max_features, self.register.max_cloud_points, self.register.max_clouds = int(max_features), int(max_cloud_points), int(max_clouds)
+        self.register._h = C.c_void_p(hostlib.dll.lvh_depth_handle(self._d))
+        self.register.close = lambda: None
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_depth_last_error().decode(errors="replace"))
+        return code
+
+    @staticmethod
+    def _pose(pose6):
+        return None if pose6 is None else (C.c_float * 6)(*[float(v) for v in np.asarray(pose6, np.float32).reshape(6)])
+
+    def close(self):
+        if self._d:
+            self.hl.dll.lvh_depth_destroy(self._d)
+            self._d = None
+
+    def lidar_callback(self, cloud, pose6, stamp):
+        pts = A.as_pts(cloud)
+        used = C.c_int32(0)
+        self._check(self.hl.dll.lvh_depth_lidar(self._d, A._ptr(pts), len(pts), self._pose(pose6), float(stamp), C.byref(used)), "lvh_depth_lidar")
+        return bool(used.value)
+
+    def set_image_pose(self, pose6):
+        """the transform the next image's get_depth reads (the reference's TF lookup at Time(0))"""
+        self._check(self.hl.dll.lvh_depth_set_image_pose(self._d, self._pose(pose6)), "lvh_depth_set_image_pose")
