@@ -411,7 +411,9 @@ int32_t lvi_undistort_points(lvi_tracker *t, const lvi_mei_params *cam, const fl
 
 int32_t lvi_tracker_push_image(lvi_tracker *t, const uint8_t *img, int32_t w, int32_t h, int32_t stride);
 int32_t lvi_tracker_set_points(lvi_tracker *t, const float *cur_xy, int32_t n);                   /* H2D cur_pts */
-int32_t lvi_tracker_run_lk(lvi_tracker *t);                                                        /* cur → forw, device-resident */
+/* run_lk tracks the points of the last lvi_tracker_set_points (cur → forw, device-resident), however many
+ * lvi_tracker_finish_frame calls came between: finish_frame stages its kept points apart and leaves them alone. */
+int32_t lvi_tracker_run_lk(lvi_tracker *t);
 int32_t lvi_tracker_get_lk(lvi_tracker *t, float *forw_xy, uint8_t *status, float *err, int32_t capacity, int32_t *n);
 int32_t lvi_tracker_set_mask(lvi_tracker *t, const uint8_t *mask, int32_t w, int32_t h, int32_t stride); /* NULL → all 255 */
 int32_t lvi_tracker_run_gftt(lvi_tracker *t, int32_t max_corners);                                 /* on forw */

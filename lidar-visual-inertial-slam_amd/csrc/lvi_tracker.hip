@@ -866,7 +866,9 @@ struct lvi_tracker {
     // device from pinned memory — measured: the runtime's own handling of a pageable 0.9 MB source costs up to 1 ms per
     // frame in a process with many GPU mappings, and the call had to wait for it before returning
     uint8_t* h_frame[2] = {nullptr, nullptr}; hipEvent_t ev_frame[2] = {nullptr, nullptr}; int frame_slot = 0;
-    float* h_pts[2] = {nullptr, nullptr}; hipEvent_t ev_pts[2] = {nullptr, nullptr}; int pts_slot = 0;      // the same for cur_pts
+    float* h_pts[2] = {nullptr, nullptr}; hipEvent_t ev_pts[2] = {nullptr, nullptr}; int pts_slot = 0;      // the same for cur_pts (set_points only)
+    float* h_kept[2] = {nullptr, nullptr}; hipEvent_t ev_kept[2] = {nullptr, nullptr}; int kept_slot = 0;   // the kept points of finish_frame: a pair of
+                                                                                                           // its own, so it never overwrites run_lk's points
     // Small inputs and results do not travel through copy commands (a 1 KB hipMemcpyAsync is a 4 us blit kernel on the stream, and the node
     // path had eleven of them per frame): kernels read the caller's points / circle centres in place from the pinned slots above and
     // write the LK results and the frame's result block into pinned host memory; the host waits once and reads.
@@ -995,6 +997,9 @@ int32_t lvi_tracker_create(const lvi_tracker_params* p, int32_t device, lvi_trac
             LVI_HIP(hipHostMalloc((void**)&t->h_pts[s], sizeof(float) * 2 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
             LVI_HIP(hipEventCreateWithFlags(&t->ev_pts[s], hipEventDisableTiming));
             LVI_HIP(hipEventRecord(t->ev_pts[s], t->ctx.stream));
+            LVI_HIP(hipHostMalloc((void**)&t->h_kept[s], sizeof(float) * 2 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
+            LVI_HIP(hipEventCreateWithFlags(&t->ev_kept[s], hipEventDisableTiming));
+            LVI_HIP(hipEventRecord(t->ev_kept[s], t->ctx.stream));
         }
         LVI_HIP(hipHostMalloc((void**)&t->h_frame_out, sizeof(float) * (4 + 4 * (size_t)std::max(t->P.max_features, 64)), hipHostMallocDefault));
         LVI_HIP(hipHostMalloc((void**)&t->h_lk, sizeof(float) * 4 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
@@ -1020,6 +1025,8 @@ void lvi_tracker_destroy(lvi_tracker* t)
         if (t->h_centers[s]) (void)hipHostFree(t->h_centers[s]);
         if (t->ev_centers[s]) (void)hipEventDestroy(t->ev_centers[s]);
         if (t->ev_pts[s]) (void)hipEventDestroy(t->ev_pts[s]);
+        if (t->h_kept[s]) (void)hipHostFree(t->h_kept[s]);
+        if (t->ev_kept[s]) (void)hipEventDestroy(t->ev_kept[s]);
     }
     if (t->h_frame_out) (void)hipHostFree(t->h_frame_out);
     if (t->h_lk) (void)hipHostFree(t->h_lk);
@@ -1259,16 +1266,16 @@ int32_t lvi_tracker_finish_frame(lvi_tracker* t, const lvi_mei_params* cam, cons
             const float* kept_src = t->d_un_in;
             int slot = -1;
             if (n_kept) {
-                slot = (t->pts_slot ^= 1);
-                LVI_HIP(hipEventSynchronize(t->ev_pts[slot]));
-                std::memcpy(t->h_pts[slot], kept_xy, sizeof(float) * 2 * (size_t)n_kept);
-                kept_src = t->h_pts[slot];                                  // read in place
+                slot = (t->kept_slot ^= 1);
+                LVI_HIP(hipEventSynchronize(t->ev_kept[slot]));
+                std::memcpy(t->h_kept[slot], kept_xy, sizeof(float) * 2 * (size_t)n_kept);
+                kept_src = t->h_kept[slot];                                 // read in place
             }
             int* d_hdr = reinterpret_cast<int*>(t->d_frame_out);
             int* h_hdr = reinterpret_cast<int*>(t->h_frame_out);
             LVI_LAUNCH(t->ctx, "frame_concat", 0, hipLaunchKernelGGL(frame_concat_kernel, dim3(1), dim3(64), 0, t->ctx.stream, kept_src, n_kept, t->d_gftt_xy, t->d_out_n, t->d_ncand,
                                                                      with_gftt ? 1 : 0, F, t->d_all_xy, d_hdr, h_hdr, t->h_frame_out + 4));
-            if (slot >= 0) LVI_HIP(hipEventRecord(t->ev_pts[slot], t->ctx.stream));
+            if (slot >= 0) LVI_HIP(hipEventRecord(t->ev_kept[slot], t->ctx.stream));
             if (cam) LVI_LAUNCH(t->ctx, "mei_undistort", 16.0 * F, hipLaunchKernelGGL(mei_undistort_kernel, dim3(div_up(F, 64)), dim3(64), 0, t->ctx.stream, *cam, t->d_all_xy, F,
                                                                                        t->h_frame_out + 4 + 2 * (size_t)F, (const int*)(d_hdr + 2)));
             LVI_HIP(hipStreamSynchronize(t->ctx.stream));                   // the ONE wait of the frame end: both kernels wrote into pinned host memory

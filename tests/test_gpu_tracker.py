@@ -274,9 +274,10 @@ def test_lk_float_accumulator_variant_report(pkg, oracle, hip):
                p99_dpos_px=float(np.quantile(d_all, 0.99)), median_dpos_px=float(np.median(d_all)), frac_identical=float((d_all == 0).mean()))
     print("LK float-accumulator variant vs exact integer sums (HIP):", rep)
     # what the measurement must keep showing: the choice is a rounding-level matter — flips are rare (points sitting on the minEig
-    # threshold or the border) and common points agree far below a hundredth of a pixel
-    assert rep["flip_rate"] < 5e-3, rep
-    assert rep["p99_dpos_px"] < 1e-2, rep
+    # threshold or the border) and common points agree far below a thousandth of a pixel (measured: 1 flip in 51 270 points,
+    # p99 2.5e-4 px)
+    assert rep["flip_rate"] <= 2e-4, rep
+    assert rep["p99_dpos_px"] <= 1e-3, rep
     o.close(); g.close()
 
 
