@@ -430,11 +430,68 @@ __device__ __forceinline__ unsigned vox_fx_point(const VoxFx& f, const lvi_pt& p
     v[3] = fx_rn_scaled((double)p.intensity, f.sci);
     return (unsigned)ijk0 + (unsigned)ijk1 * f.mul1 + (unsigned)ijk2 * f.mul2;
 }
-__device__ __forceinline__ float fx_mean_xyz(unsigned long long sum, unsigned cnt, int cell, double leaf, int k)
+// RNE_f32((C + S / N) * 2^-k) in integers: S = a N + r (0 <= r < N), the magnitude M + rr / N, then a quotient of at least 26
+// bits and one round-to-nearest-even with the remainder as sticky bit.  C = cell * mantissa(leaf) * 2^12, so |C| < 2^62 needs
+// |cell| < 2^26 (the contract's range, lvi_voxel.hpp); N <= 2^25; the result is never subnormal.
+__device__ __forceinline__ float fx_round_exact(long long C, long long S, unsigned N, int k)
 {
-    return (float)((double)cell * leaf + ldexp(__ll2double_rn((long long)sum) / (double)cnt, -k));
+    long long a = S / (long long)N, r = S - a * (long long)N;
+    if (r < 0) { a -= 1; r += N; }
+    const long long I = C + a;
+    const bool neg = I < 0;
+    const unsigned long long M = neg ? (unsigned long long)(r ? -(I + 1) : -I) : (unsigned long long)I;
+    const unsigned long long rr = neg && r ? (unsigned long long)(N - r) : (unsigned long long)r;
+    unsigned long long Q;
+    bool sticky;
+    int t = 0;
+    if (M >= (1ull << 25)) { Q = M; sticky = rr != 0; }
+    else {
+        const unsigned long long X = M * N + rr;                        // < 2^50
+        if (X == 0) return 0.f;
+        t = max(0, 26 + (32 - __clz((int)N)) - (64 - __clzll((long long)X)));
+        const unsigned long long Y = X << t;                             // < 2^52
+        Q = Y / N; sticky = Y - Q * N != 0;
+    }
+    const int sh = (64 - __clzll((long long)Q)) - 24;                    // >= 2: Q >= 2^25
+    unsigned long long m = Q >> sh;
+    const unsigned long long rem = Q & ((1ull << sh) - 1), half = 1ull << (sh - 1);
+    if (rem > half || (rem == half && (sticky || (m & 1)))) m++;
+    const float f = ldexpf((float)m, sh - t - k);                        // m <= 2^24: exact
+    return neg ? -f : f;
 }
-__device__ __forceinline__ float fx_mean_int(unsigned long long sum, unsigned cnt, int k) { return (float)ldexp(__ll2double_rn((long long)sum) / (double)cnt, -k); }
+// The voxel's centroid is RNE_f32(cell * leaf + sum / (cnt 2^k)) per coordinate and RNE_f32(sum / (cnt 2^ki)) for the intensity,
+// each rounded once (lvi_voxel.hpp); for |cell| < 2^26, cell * leaf is exact in binary64 and an integer multiple of 2^-k.
+// fx_estimate gives the binary64 estimate y = c + sum / cnt * 2^-k and clears `ok` unless y provably rounds to that value.
+// Far from a midpoint: the 29 low bits of y are the bits below an f32 mantissa, the rounding midpoint is 2^28 of them; y is off
+// by at most ~2^(eo - ey + 1.1) + 0.5 of its own ulps (the int -> double conversion and the division: 2^-52 of o each; the
+// addition: half an ulp); the margin 8 + 2^(eo - ey + 3) covers that, and eo - ey <= 20 keeps it far below the 2^27 ulps to the
+// midpoint of the next binade.  Near a midpoint (a quarter of the voxels of a map: the mean of two points is often exactly one):
+// y is still right when it was computed exactly (sum below 2^53, the division exact by fma, the addition exact by TwoSum).
+__device__ __forceinline__ double fx_estimate(double c, unsigned long long sum, unsigned cnt, int k, bool& ok)
+{
+    const double sd = __ll2double_rn((long long)sum), nd = (double)cnt;
+    const double qd = sd / nd;
+    const double o = ldexp(qd, -k);
+    const double y = c + o;
+    const int low = __double2loint(y) & 0x1FFFFFFF;
+    const int de = ((__double2hiint(o) >> 20) & 0x7FF) - ((__double2hiint(y) >> 20) & 0x7FF);
+    if (de > 20 || abs(low - (1 << 28)) <= 8 + (1 << max(de + 3, 0))) {
+        const double b = y - c;
+        ok = ok && (unsigned long long)((long long)sum + (1ll << 53)) < (1ull << 54) && fma(-qd, nd, sd) == 0.0 && (c - (y - b)) + (o - b) == 0.0;
+    }
+    return y;
+}
+// the whole voxel in integers, for the rare voxel with a coordinate next to a rounding midpoint (one call site per kernel)
+__device__ __noinline__ lvi_pt fx_centroid_exact(int c0, int c1, int c2, double leaf, int k, int ki, unsigned long long sx,
+                                                 unsigned long long sy, unsigned long long sz, unsigned long long si, unsigned cnt)
+{
+    lvi_pt o;
+    o.x = fx_round_exact((long long)ldexp((double)c0 * leaf, k), (long long)sx, cnt, k);
+    o.y = fx_round_exact((long long)ldexp((double)c1 * leaf, k), (long long)sy, cnt, k);
+    o.z = fx_round_exact((long long)ldexp((double)c2 * leaf, k), (long long)sz, cnt, k);
+    o.intensity = fx_round_exact(0ll, (long long)si, cnt, ki);
+    return o;
+}
 // absolute integer coordinates of a point's voxel: floor(p * inv) — the float floor PCL takes before it subtracts min_b
 __device__ __forceinline__ void vox_cell_abs(const VoxGrid& g, const lvi_pt& p, int c[3])
 {
@@ -452,9 +509,12 @@ __device__ __forceinline__ lvi_pt fx_centroid(const VoxGrid& g, unsigned key, un
 {
     int c[3];
     vox_cell_of_key(g, key, c);
+    bool ok = true;
+    const double x = fx_estimate((double)c[0] * g.leaf_d, sx, cnt, g.fx_k, ok), y = fx_estimate((double)c[1] * g.leaf_d, sy, cnt, g.fx_k, ok);
+    const double z = fx_estimate((double)c[2] * g.leaf_d, sz, cnt, g.fx_k, ok), in = fx_estimate(0.0, si, cnt, g.fx_ki, ok);
+    if (!ok) return fx_centroid_exact(c[0], c[1], c[2], g.leaf_d, g.fx_k, g.fx_ki, sx, sy, sz, si, cnt);
     lvi_pt o;
-    o.x = fx_mean_xyz(sx, cnt, c[0], g.leaf_d, g.fx_k); o.y = fx_mean_xyz(sy, cnt, c[1], g.leaf_d, g.fx_k);
-    o.z = fx_mean_xyz(sz, cnt, c[2], g.leaf_d, g.fx_k); o.intensity = fx_mean_int(si, cnt, g.fx_ki);
+    o.x = (float)x; o.y = (float)y; o.z = (float)z; o.intensity = (float)in;
     return o;
 }
 

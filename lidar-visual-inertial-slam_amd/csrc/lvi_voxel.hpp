@@ -26,10 +26,16 @@ struct VoxGrid {                 // device, per segment
     int overflow;                // PCL's "leaf size too small" rule hit: output = input
     int nvox;
     int out_off;
-    // ---- centroid arithmetic (every realisation, the incremental map included): exact integer sums of
-    //      (value - cell * leaf) * 2^fx_k per voxel, cell = the voxel's ABSOLUTE integer coordinate floor(value * inv): the origin
-    //      of a voxel's sums is a property of the voxel, not of the bounding box, so the sums do not depend on which other points
-    //      are in the cloud, nor on the order the points of a voxel are visited in.  Intensity: value * 2^fx_ki (origin 0).
+    // ---- centroid arithmetic (every realisation, the incremental map included).  Per voxel and coordinate, with
+    //      cell = the voxel's ABSOLUTE integer coordinate floor(value * inv):
+    //          q_i = RNE(2^fx_k * (v_i - cell * leaf))   (binary64 offset: exact unless |v_i| < 2^-28 leaf in cell -1)
+    //          centroid = RNE_f32(cell * leaf + sum q_i / (cnt * 2^fx_k)), rounded once (fx_centroid)
+    //      The origin of a voxel's sums is a property of the voxel, not of the bounding box, so the sums do not depend on which
+    //      other points are in the cloud, nor on the order the points of a voxel are visited in.  Intensity: q_i = RNE(I_i * 2^fx_ki)
+    //      (origin 0), RNE_f32(sum q_i / (cnt * 2^fx_ki)); fx_ki from the segment's largest |intensity| (29 on the incremental map,
+    //      which takes intensities < 256 only).  Within 2^-(fx_k+1) of the true mean before the final half ulp; NOT the true
+    //      mean rounded once for coordinates below ~2^(24 - fx_k), whose bits are finer than the grid.  Range: |cell| < 2^26
+    //      (cell * leaf * 2^fx_k < 2^62 in the exact finalisation; 2000 m at a 0.02 m leaf is a cell of ~2^17).
     double leaf_d;               // (double)leaf
     int fx_k, fx_ki;             // scale exponents: |value - cell*leaf| < 2 leaf < 2^(37 - fx_k); |intensity| < 2^(37 - fx_ki), at least 2^8
     // ---- binned path: bin = idx >> bin_shift, nbins <= VB_NB

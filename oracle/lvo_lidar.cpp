@@ -35,6 +35,10 @@ thread_local std::string g_err;
 int32_t fail(int32_t code, const char* msg) { g_err = msg; return code; }
 }  // namespace
 void lvo_set_error(const char* msg) { g_err = msg; }
+// VoxelGrid centroid arithmetic (lvo_voxel.h): 0 = PCL's f32 running sums (default), 1 = the HIP contract.  Process-wide, test
+// infrastructure only.
+extern "C" void lvo_set_centroid_mode(int mode) { lvo::centroid_mode() = mode == 1 ? 1 : 0; }
+extern "C" int lvo_get_centroid_mode(void) { return lvo::centroid_mode(); }
 namespace {
 
 struct smoothness_t { float value; size_t ind; };                       // featureExtraction.cpp:4-7

@@ -23,6 +23,40 @@ struct VoxelDebug {
     bool overflow = false;
 };
 
+// Centroid arithmetic, process-wide (test infrastructure only; lvo_set_centroid_mode in lvo_lidar.cpp):
+//   0 (default)  pcl::CentroidPoint literally: f32 running sums in sorted order, divided by the f32 count;
+//   1            the HIP realisations' contract (csrc/lvi_voxel.hpp): per voxel and coordinate
+//                q_i = RNE(2^k (v_i - cell leaf)), value = RNE_f32(cell leaf + sum q_i / (cnt 2^k)), rounded once.
+inline int& centroid_mode() { static int m = 0; return m; }
+
+// RNE_f32((C + S / N) 2^-k) in integers (the same steps as fx_round_exact in csrc/lvi_voxel.hip)
+inline float fx_round_exact(long long C, long long S, unsigned N, int k)
+{
+    long long a = S / (long long)N, r = S - a * (long long)N;
+    if (r < 0) { a -= 1; r += N; }
+    const long long I = C + a;
+    const bool neg = I < 0;
+    const unsigned long long M = neg ? (unsigned long long)(r ? -(I + 1) : -I) : (unsigned long long)I;
+    const unsigned long long rr = neg && r ? (unsigned long long)(N - r) : (unsigned long long)r;
+    unsigned long long Q;
+    bool sticky;
+    int t = 0;
+    if (M >= (1ull << 25)) { Q = M; sticky = rr != 0; }
+    else {
+        const unsigned long long X = M * N + rr;
+        if (X == 0) return 0.f;
+        t = std::max(0, 26 + (32 - __builtin_clz(N)) - (64 - __builtin_clzll(X)));
+        const unsigned long long Y = X << t;
+        Q = Y / N; sticky = Y - Q * N != 0;
+    }
+    const int sh = (64 - __builtin_clzll(Q)) - 24;
+    unsigned long long m = Q >> sh;
+    const unsigned long long rem = Q & ((1ull << sh) - 1), half = 1ull << (sh - 1);
+    if (rem > half || (rem == half && (sticky || (m & 1)))) m++;
+    const float f = std::ldexp((float)m, sh - t - k);
+    return neg ? -f : f;
+}
+
 struct cloud_point_index_idx {
     unsigned int idx;
     unsigned int cloud_point_index;
@@ -74,10 +108,42 @@ inline int voxel_grid_filter(const lvi_pt* in, int n, float leaf, std::vector<lv
     // unstable std::sort by idx only — same libstdc++ introsort as the reference platform
     std::sort(index_vector.begin(), index_vector.end(), std::less<cloud_point_index_idx>());
 
+    // mode 1: fixed-point scales of the sums from the leaf and the segment's largest |intensity| (vox_fx_setup)
+    int fx_k = 0, fx_ki = 0;
+    {
+        float imax = 0.f;
+        for (int j = 0; j < n; j++) imax = std::max(imax, std::fabs(in[j].intensity));
+        int ex = 0, exi = 0;
+        (void)std::frexp(2.0f * leaf, &ex);
+        (void)std::frexp(imax, &exi);
+        fx_k = 37 - ex;
+        fx_ki = 37 - std::max(exi, 8);
+    }
     size_t index = 0;
     while (index < index_vector.size()) {
         size_t i = index + 1;
         while (i < index_vector.size() && index_vector[i].idx == index_vector[index].idx) ++i;
+        if (centroid_mode() == 1) {
+            const int cell[3] = {(int)(index_vector[index].idx % (unsigned)div_b[0]) + min_b[0],
+                                 (int)(index_vector[index].idx / (unsigned)div_b[0] % (unsigned)div_b[1]) + min_b[1],
+                                 (int)(index_vector[index].idx / (unsigned)divb_mul[2]) + min_b[2]};
+            long long sum[4] = {0, 0, 0, 0};
+            for (size_t li = index; li < i; ++li) {
+                const lvi_pt& p = in[index_vector[li].cloud_point_index];
+                const float v[4] = {p.x, p.y, p.z, p.intensity};
+                for (int d = 0; d < 3; d++) sum[d] += std::llrint(std::ldexp((double)v[d] - (double)cell[d] * (double)leaf, fx_k));
+                sum[3] += std::llrint(std::ldexp((double)v[3], fx_ki));
+            }
+            const unsigned cnt = (unsigned)(i - index);
+            lvi_pt o;
+            float* of = &o.x;
+            for (int d = 0; d < 3; d++) of[d] = fx_round_exact((long long)std::ldexp((double)cell[d] * (double)leaf, fx_k), sum[d], cnt, fx_k);
+            o.intensity = fx_round_exact(0, sum[3], cnt, fx_ki);
+            out.push_back(o);
+            if (dbg) { dbg->cells.push_back((int32_t)index_vector[index].idx); dbg->counts.push_back((int32_t)cnt); }
+            index = i;
+            continue;
+        }
         // CentroidPoint<PointXYZI>: f32 running sums of xyz and intensity, divided by the count
         float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
         for (size_t li = index; li < i; ++li) {

@@ -1,4 +1,4 @@
-"""Parity soak (test infrastructure, run by hand on the GPU box: `python tests/soak_parity.py [N] [seed] [cases,to,print,in,detail]`).
+"""Parity soak (test infrastructure, run by hand on the GPU box: `python tests/soak_parity.py [N] [seed] [cases,to,print,in,detail | all] [centroid mode]`).
 
 The randomised sweep of tests/test_gpu_lidar.py::test_parity_sweep_over_scans_and_settings, longer and wider: N cases
 over ring counts (4 = pipelined sector kernel, 6 / 16 = its sequential form), scan sizes, noise, thresholds, leaf sizes,
@@ -21,6 +21,7 @@ counted, printed and put in one of the classes the reference itself leaves open:
               f32 inside cv::gemm in an order it does not specify, the HIP path in f64
 Anything else is "unexplained"; the exit code is the number of unexplained cases.  PARITY UNPINNED (see oracle/
 headers): the checker is the CPU restatement."""
+import ctypes
 import json
 import os
 import sys
@@ -68,14 +69,29 @@ def tied_sectors(info, curv, n_scan):
 def main():
     n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 2024
-    detail = set(int(c) for c in sys.argv[3].split(",")) if len(sys.argv) > 3 else None
-    summary = run(n_cases, seed, only=detail, verbose=detail is not None)
+    detail = set(int(c) for c in sys.argv[3].split(",")) if len(sys.argv) > 3 and sys.argv[3] != "all" else None
+    mode = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+    summary = run(n_cases, seed, only=detail, verbose=detail is not None, centroid_mode=mode)
     print(json.dumps(summary))
     return summary["classes"]["unexplained"]
 
 
-def run(n_cases, seed, only=None, verbose=False):
-    """execute the cases in `only` (all when None) of the seeded stream of n_cases cases; returns the summary dict"""
+def run(n_cases, seed, only=None, verbose=False, centroid_mode=0):
+    """execute the cases in `only` (all when None) of the seeded stream of n_cases cases; returns the summary dict.
+    centroid_mode 1 runs the oracle's VoxelGrids with the HIP centroid contract instead of PCL's f32 sums (lvo_set_centroid_mode)"""
+    from oracle import loader
+    dll = loader.load(graft.import_package()).dll
+    dll.lvo_set_centroid_mode.argtypes = [ctypes.c_int]
+    dll.lvo_set_centroid_mode(centroid_mode)
+    try:
+        s = _run(n_cases, seed, only, verbose)
+    finally:
+        dll.lvo_set_centroid_mode(0)
+    s["centroid_mode"] = centroid_mode
+    return s
+
+
+def _run(n_cases, seed, only=None, verbose=False):
     pkg = graft.import_package()
     from oracle import loader
     oracle, hip = loader.load(pkg), pkg.load_hip()

@@ -110,6 +110,7 @@ def main(n_cases=None, seed=None):
         m = np.unique(m, axis=0)
         _, first = np.unique(np.floor(m[:, :3] / np.float32(0.4)).astype(np.int64), axis=0, return_index=True)
         m = m[np.sort(first)]
+        assert np.abs(m[:, :3]).min() >= 2.0 ** (23 - 37)        # outside the near-zero band of either leaf
         for h in (o, g):
             h.map_set(m, m)
         diffs = []

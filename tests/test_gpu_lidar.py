@@ -5,9 +5,12 @@ f32 values that follow a fixed operation order bit-exact; voxel centroids within
 count * 2^-23 * max|coord| (PCL's sum order inside a voxel is unspecified); pose within
 1e-4 m / 1e-4 rad.  PARITY UNPINNED: the oracle restates the reference, which ships no
 golden vectors (see oracle/ headers)."""
+import ctypes
+
 import numpy as np
 import pytest
 
+import centroid_ref
 from helpers import bits, centroid_tol, make_small_scene, small_params, xyzi
 
 pytestmark = pytest.mark.gpu
@@ -366,6 +369,9 @@ def test_map_build_and_knn_exact(pkg, pair, scene):
     (aco, aso), (acg, asg) = o.get_map_ds(), g.get_map_ds()
     np.testing.assert_array_equal(xyzi(aco).view(np.uint32), xyzi(acg).view(np.uint32))
     np.testing.assert_array_equal(xyzi(aso).view(np.uint32), xyzi(asg).view(np.uint32))
+    # that holds because no coordinate lies in the near-zero band, where a one-point voxel is the model, not the point
+    for raw, ds, leaf in ((mcg, acg, 0.2), (msg, asg, 0.4)):
+        np.testing.assert_array_equal(xyzi(ds).view(np.uint32), centroid_ref.model_centroids(raw, leaf)["pts"].view(np.uint32))
     for which, m in ((0, acg), (1, asg)):
         q = xyzi(m)[rng.integers(0, len(m), 4000)].copy()
         q[:, :3] += rng.normal(0, 0.15, (4000, 3)).astype(np.float32)
@@ -391,6 +397,8 @@ def test_knn_index_bit_exact_on_identical_map(pkg, oracle, hip):
     _, first = np.unique(np.floor(m[:, :3] / np.float32(0.4)).astype(np.int64), axis=0, return_index=True)
     m = m[np.sort(first)]                                                               # at most one point per 0.4-voxel (and per 0.2-voxel)
     assert len(m) > 20000
+    # a one-point voxel is the point itself only outside the near-zero band (bits finer than the 2^-k grid)
+    assert np.abs(m[:, :3]).min() >= 2.0 ** (23 - min(centroid_ref.fx_k(0.2), centroid_ref.fx_k(0.4)))
     for h in (o, g):
         h.map_set(m, m)
     (mco, mso), (mcg, msg) = o.get_map_ds(), g.get_map_ds()
@@ -772,8 +780,26 @@ def test_full_size_scan_to_map(pkg, oracle, hip, bench_map, fixed):
         h.map_upload(mc, ms); h.map_build()
     co, cg = o.counts(), g.counts()
     assert co["map_corner_ds"] == cg["map_corner_ds"] and co["map_surf_ds"] == cg["map_surf_ds"] > 50_000
+    worst = _full_size_scans(S, o, g, fixed, exact_surf_ds=False)
+    print(f"full-size scan-to-map ({'10 fixed' if fixed else 'reference'} iterations): worst |pose_hip - pose_oracle| = {worst:.2e}")
+    # the same scans with the oracle's VoxelGrids on the HIP centroid contract: the second-stage grid then sees
+    # identical ring-DS centroids on both sides, so its count is exact
+    d = oracle.dll
+    d.lvo_set_centroid_mode.argtypes = [ctypes.c_int]
+    d.lvo_set_centroid_mode(1)
+    try:
+        worst1 = _full_size_scans(S, o, g, fixed, exact_surf_ds=True)
+    finally:
+        d.lvo_set_centroid_mode(0)
+    print(f"  oracle centroids on the HIP contract: surf_ds exact, worst |pose_hip - pose_oracle| = {worst1:.2e}")
+    o.close(); g.close()
+
+
+def _full_size_scans(S, o, g, fixed, exact_surf_ds):
+    """bench.py's scan pool of rank 0 (same poses, seeds, guesses) through both handles: DS counts, status, iterations,
+    selected counts and pose; returns the worst pose difference"""
     worst = 0.0
-    for sid in range(3):                                         # bench.py's scan pool of rank 0: same poses, seeds, guesses
+    for sid in range(3):
         pose = S.loop_pose(0.37 + 0.71 * sid, 0.01 * np.sin(sid), -0.02 * np.cos(sid))
         scan = S.make_scan(100001, pose, 12345 + sid)
         guess = S.perturbed_guess(pose, sid)
@@ -781,7 +807,10 @@ def test_full_size_scan_to_map(pkg, oracle, hip, bench_map, fixed):
             h.map_build()                                        # the reference re-voxelises and re-indexes per scan
             h.scan_upload(scan); h.scan_organize(); h.scan_extract(); h.scan_downsample()
         co, cg = o.counts(), g.counts()
-        assert abs(co.pop("surf_ds") - cg.pop("surf_ds")) <= 3, (co, cg)     # second-stage grid: see test_parity_sweep_…
+        if exact_surf_ds:
+            assert co["surf_ds"] == cg["surf_ds"], (co, cg)
+        else:
+            assert abs(co.pop("surf_ds") - cg.pop("surf_ds")) <= 3, (co, cg)     # second-stage grid: see test_parity_sweep_…
         assert co == cg, (co, cg)
         ro, rg = o.scan_match(guess), g.scan_match(guess)
         assert ro["status"] == rg["status"] == 0
@@ -795,8 +824,7 @@ def test_full_size_scan_to_map(pkg, oracle, hip, bench_map, fixed):
         assert dp[:3].max() < 1e-4 and dp[3:].max() < 1e-4, (sid, dp)
         worst = max(worst, float(dp.max()))
         assert np.abs(rg["pose"][3:] - pose[3:]).max() < 0.05 and np.abs(rg["pose"][:3] - pose[:3]).max() < 0.01
-    print(f"full-size scan-to-map ({'10 fixed' if fixed else 'reference'} iterations): worst |pose_hip - pose_oracle| = {worst:.2e}")
-    o.close(); g.close()
+    return worst
 
 
 # ----------------------------------------------------------------------------- sector pipeline robustness

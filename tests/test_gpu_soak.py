@@ -50,6 +50,21 @@ def test_lidar_soak_classified():
     print("lidar soak:", s["executed"], "cases,", s["differing"], "differing:", s["classes"], "worst staged pose diff %.2e" % s["worst_pose_diff_staged"])
 
 
+def test_lidar_soak_with_the_hip_centroid_contract_in_the_oracle():
+    """the same cases with the oracle's VoxelGrids switched to the HIP centroid contract (lvo_set_centroid_mode(1)): the
+    centroid arithmetic was the stated cause of the second_ds and staged-pose differences, so they must vanish"""
+    only = sorted(set(KNOWN) | set(range(0, 50, 2)))
+    s = soak_parity.run(200, 2024, only=only, centroid_mode=1)
+    assert s["executed"] == len(only) and s["centroid_mode"] == 1
+    assert s["classes"]["unexplained"] == 0, s["report"]
+    assert s["classes"]["second_ds"] == 0, s["report"]
+    for r in s["report"]:
+        assert r["kind"] in ("ties", "knife"), r
+    assert s["worst_pose_diff_staged"] < 1e-4, s["report"]
+    print("lidar soak, centroid mode 1:", s["executed"], "cases,", s["differing"], "differing:", s["classes"],
+          "worst staged pose diff %.2e" % s["worst_pose_diff_staged"])
+
+
 def test_tracker_soak_bit_exact(capsys):
     assert soak_tracker.main(60, 2025) == 0
 
