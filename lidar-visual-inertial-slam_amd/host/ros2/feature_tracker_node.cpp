@@ -2,7 +2,10 @@
 // /vins/feature/feature message (feature_tracker_node.cpp:37-231, 410-416).  The callback logic — first image,
 // discontinuity restart, frequency control, readImage (CLAHE + pyramidal LK + Shi-Tomasi on the MI355X), updateID, message
 // assembly, first-publish suppression — is lvi_host::FeatureTrackerNode; this file converts messages.  rejectWithF's RANSAC
-// stays OpenCV on the host (cv::findFundamentalMat), installed as the tracker's hook.  The lidar depth association
+// stays OpenCV on the host (cv::findFundamentalMat), installed as the tracker's hook, unless the parameter
+// use_device_fundamental is true: then lvi_host::DeviceFundamental (a restatement of OpenCV 4.5.x's
+// FM_RANSAC) runs it on the MI355X.  The default stays OpenCV.  This source is not compiled by build.py (no ROS 2 there).
+// The lidar depth association
 // (lidar_callback :273-377 and DepthRegister::get_depth, feature_tracker.h:116-331) is lvi_host::DepthRegister on the
 // MI355X, installed as the node's get_depth; the TF lookups (vins_world <- vins_body_ros at Time(0)) stay here.
 // Builds only where rclcpp, image_transport, cv_bridge, OpenCV, PCL (fromROSMsg) and tf2 exist.
@@ -24,6 +27,7 @@
 #include <mutex>
 
 #include "../lvi_depth_host.hpp"
+#include "../lvi_fmat_host.hpp"
 #include "../lvi_host.hpp"
 #include "camodocal/camera_models/CameraFactory.h"
 #include "camodocal/camera_models/CataCamera.h"
@@ -36,6 +40,7 @@ static std::unique_ptr<lvi_host::FeatureTrackerNode> node_logic;
 static rclcpp::Publisher<sensor_msgs::msg::PointCloud>::SharedPtr pub_feature;
 static rclcpp::Publisher<std_msgs::msg::Bool>::SharedPtr pub_restart;
 static std::unique_ptr<lvi_host::DepthRegister> depth_register;
+static std::unique_ptr<lvi_host::DeviceFundamental> device_fundamental;   // only with use_device_fundamental
 static std::shared_ptr<tf2_ros::Buffer> tfBuffer;
 static std::shared_ptr<tf2_ros::TransformListener> listener;
 static std::mutex mtx_depth;                      // the two callbacks run on a 2-thread executor; the handle is used by one at a time
@@ -128,6 +133,10 @@ int main(int argc, char** argv)
         cv::findFundamentalMat(ca, cb, cv::FM_RANSAC, thr, 0.99, st);                   // feature_tracker.cpp:229
         status.assign(st.begin(), st.end());
     };
+    if (n->declare_parameter<bool>("use_device_fundamental", false)) {                  // opt-in: rejectWithF without OpenCV
+        device_fundamental = std::make_unique<lvi_host::DeviceFundamental>(0, std::max(MAX_CNT, 8), 1000);
+        device_fundamental->install(*tracker);
+    }
     node_logic = std::make_unique<lvi_host::FeatureTrackerNode>(*tracker, FREQ);
     // DepthRegister (:404) + the lidar window: 5 s of clouds at up to 20 Hz, 2^18 points per cloud
     depth_register = std::make_unique<lvi_host::DepthRegister>(0, 101, 1 << 18, p.max_features, LIDAR_SKIP, 5.0);

@@ -33,6 +33,8 @@ FUNDAMENTAL_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C
 
 # the depth register's flattening (include/lvi_depth.h is exported by liblvi_hip.so only): linked into the HIP host library alone
 DEPTH_SOURCES = ("lvi_depth_capi.cpp",)
+# the device RANSAC's (include/lvi_fmat.h, the same restriction)
+FMAT_SOURCES = ("lvi_fmat_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -40,7 +42,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
     srcs = [os.path.join(HOST_DIR, "lvi_seq_capi.cpp")] + [os.path.join(HOST_DIR, f) for f in sources]
     deps = srcs + [os.path.join(HOST_DIR, "lvi_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_hotpath.h")]
     if sources:
-        deps += [os.path.join(HOST_DIR, "lvi_depth_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_depth.h")]
+        deps += [os.path.join(HOST_DIR, "lvi_depth_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_depth.h"),
+                 os.path.join(HOST_DIR, "lvi_fmat_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmat.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -89,6 +92,10 @@ class HostLibrary:
             d.lvh_depth_install.argtypes = [C.c_void_p, C.c_void_p]
             d.lvh_depth_lidar.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_int32)]
             d.lvh_depth_set_image_pose.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self.has_fmat = hasattr(d, "lvh_trk_use_device_fundamental")      # the HIP host library only
+        if self.has_fmat:
+            d.lvh_fmat_last_error.restype = C.c_char_p
+            d.lvh_trk_use_device_fundamental.argtypes = [C.c_void_p, C.c_int32]
 
     def check(self, code, where):
         if code < 0:
@@ -212,6 +219,16 @@ class TrackerNode:
                 status[i] = int(st[i])
         self._hook = FUNDAMENTAL_FN(tramp)
         self.hl.dll.lvh_trk_set_fundamental_hook(self._t, self._hook, None)
+
+    def use_device_fundamental(self, device=0):
+        """rejectWithF's findFundamentalMat := the device RANSAC (lvi_host::DeviceFundamental, include/lvi_fmat.h).  HIP
+        host library only; set_fundamental_hook replaces it again."""
+        if not self.hl.has_fmat:
+            raise RuntimeError("this host library has no device RANSAC (only the one linked against liblvi_hip.so has)")
+        code = self.hl.dll.lvh_trk_use_device_fundamental(self._t, int(device))
+        if code < 0:
+            raise A.LviError(code, "lvh_trk_use_device_fundamental", self.hl.dll.lvh_fmat_last_error().decode(errors="replace"))
+        self._hook = None
 
     def image(self, img, stamp):
         img = np.ascontiguousarray(img, np.uint8)
