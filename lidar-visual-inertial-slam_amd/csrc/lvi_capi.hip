@@ -54,6 +54,11 @@ void voxel_debug_fetch(const Ctx& ctx, const VoxelPlan& p, int n_in, std::vector
 
 using namespace lvi;
 
+struct lvi_lidar;
+namespace lvi {
+LidarDev& lidar_slot0(lvi_lidar* h);                // the keyframe store's slot (lvi_gmap.hip)
+}
+
 struct lvi_lidar {
     LidarDev d;                                     // slot 0: owns the streams, the profiler, the keyframe store and the raw map
     std::vector<std::unique_ptr<LidarDev>> more;    // batch slots 1 .. batch_scans-1 (lvi_scan_batch_*)
@@ -70,6 +75,8 @@ struct lvi_lidar {
     std::atomic<int> shared_by{0};                  // handles that read this one's raw map (they may live on other host threads): it must not change while > 0
     std::vector<lvi_lidar*> sharers;                // … who they are (g_share_mu): an owner that is destroyed first sends them back to their own memory
 };
+
+LidarDev& lvi::lidar_slot0(lvi_lidar* h) { return h->d; }
 
 namespace {
 
@@ -273,6 +280,7 @@ void lvi_lidar_destroy(lvi_lidar* h)
     (void)hipSetDevice(d.device);
     if (d.ctx.stream) { (void)hipStreamSynchronize(d.ctx.stream); }
     if (d.ctx2.stream) { (void)hipStreamSynchronize(d.ctx2.stream); }
+    try { gmap_free(d); } catch (...) {}
     d.prof.collect();
     for (auto& q : h->more) release_slot(*q);
     release_slot(d);
@@ -772,6 +780,7 @@ int32_t lvi_keyframes_clear(lvi_lidar* h)
     return guarded(h, [&]() -> int32_t {
         LidarDev& d = h->d;
         join_map(d); sync(d);                                        // an assembly in flight still reads the pool
+        gmap_join(d);                                                // … and so may a global-map build
         d.kf_off_c.clear(); d.kf_n_c.clear(); d.kf_off_s.clear(); d.kf_n_s.clear(); d.kf_pose.clear(); d.kf_pool_used = 0;
         d.inc_ready = false; d.inc_mult.clear(); d.inc_pose.clear();
         return LVI_OK;

@@ -1690,7 +1690,7 @@ void stage_map_index(const Slots& sl, const Ctx& cx)
     LVI_LAUNCH(cx, "grid_scatter", 32.0 * nds, hipLaunchKernelGGL(grid_scatter_kernel, dim3(GRID_PT_BLOCKS, 2, S), dim3(256), 0, cx.stream, G));
 }
 
-static void kf_matrix(const float* T, float M[12])
+void kf_matrix(const float* T, float M[12])
 {
     // pcl::getTransformation(x, y, z, roll, pitch, yaw), transformIn = [roll, pitch, yaw, x, y, z] (:404-407), host libm as the reference
     const float A = std::cos(T[2]), B = std::sin(T[2]), C = std::cos(T[1]), D = std::sin(T[1]), E = std::cos(T[0]), F = std::sin(T[0]), DE = D * E, DF = D * F;
@@ -1790,6 +1790,14 @@ __global__ __launch_bounds__(256) void kf_assemble_kernel(const LidarDev::KfSeg*
     for (int i = blockIdx.x * 256 + threadIdx.x; i < sg.n; i += gridDim.x * 256) out[i] = to_map(sg.A, in[i]);
 }
 
+void kf_assemble_launch(const Ctx& cx, const LidarDev::KfSeg* d_segs, int nseg, int maxn, const lvi_pt* pool, lvi_pt* outC, lvi_pt* outS, double n_pts)
+{
+    for (int s0 = 0; s0 < nseg; s0 += 65535) {                 // blockIdx.y = piece: at most 65535 per launch
+        const dim3 grid(std::min(div_up(maxn, 256), 64), std::min(nseg - s0, 65535));
+        LVI_LAUNCH(cx, "kf_assemble", 32.0 * n_pts, hipLaunchKernelGGL(kf_assemble_kernel, grid, dim3(256), 0, cx.stream, d_segs + s0, pool, outC, outS));
+    }
+}
+
 void stage_map_assemble(LidarDev& d, const int32_t* keys, int n_keys)
 {
     join_map(d);                                    // the previous build may still read the raw buffers
@@ -1813,9 +1821,7 @@ void stage_map_assemble(LidarDev& d, const int32_t* keys, int n_keys)
     }
     if (nseg) {
         LVI_HIP(hipMemcpyAsync(d.d_kfSeg, d.h_kfSeg, sizeof(LidarDev::KfSeg) * (size_t)nseg, hipMemcpyHostToDevice, d.ctx.stream));
-        const dim3 grid(std::min(div_up(maxn, 256), 64), nseg);
-        LVI_LAUNCH(d.ctx, "kf_assemble", 32.0 * ((double)oc + os), hipLaunchKernelGGL(kf_assemble_kernel, grid, dim3(256), 0, d.ctx.stream,
-                                                                                     d.d_kfSeg, d.kfPool, d.mapCornerRaw, d.mapSurfRaw));
+        kf_assemble_launch(d.ctx, d.d_kfSeg, nseg, maxn, d.kfPool, d.mapCornerRaw, d.mapSurfRaw, (double)oc + os);
     }
     d.n_map_corner = oc; d.n_map_surf = os; d.have_map_raw = true;
     d.voxMap.bbox_cached = false;

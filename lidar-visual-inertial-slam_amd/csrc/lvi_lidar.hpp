@@ -55,6 +55,8 @@ struct GridIndex {                       // uniform 0.5 m grid over one DS map (
     struct Meta { double origin[3]; double edge, inv_edge; int dim[3]; int ncells; int n; int ok; int R; }* meta = nullptr;   // device
 };
 
+struct GmapDev;                                         // lvi_gmap.hip: the global-map arena (include/lvi_gmap.h)
+
 struct LidarDev {
     lvi_lidar_params P;
     int device = 0;
@@ -155,6 +157,7 @@ struct LidarDev {
     // local map (the replay configuration: one frozen raw map, re-voxelised and re-indexed for every scan)
     LidarDev* map_owner = nullptr;                         // slot 0 for z > 0
     const lvi_livox_pt* raw_bound = nullptr;               // lvi_scan_batch_bind_device: the scan is read in place (no copy)
+    GmapDev* gmap = nullptr;                               // lvi_gmap_reserve (slot 0): null until then, nothing allocated
 };
 
 // the scans of one batched launch sequence: slot 0 owns the streams, the profiler and the raw local map
@@ -189,5 +192,11 @@ void stage_scan_match_enqueue(LidarDev& d, const lvi_imu_hint* imu, void* d_reco
 void debug_knn(LidarDev& d, int which, const lvi_pt* d_queries, int nq, int* d_idx, float* d_sqd);
 void debug_residuals(LidarDev& d, int which, const float pose[6]);
 void transform_cloud(LidarDev& d, const lvi_pt* d_in, int n, const float pose6[6], lvi_pt* d_out);
+void kf_matrix(const float* T, float M[12]);               // pcl::getTransformation of a keyframe pose (host libm)
+// kf_assemble_kernel over nseg pieces of the keyframe pool (launched in chunks of at most 65535 pieces)
+void kf_assemble_launch(const Ctx& cx, const LidarDev::KfSeg* d_segs, int nseg, int maxn, const lvi_pt* pool, lvi_pt* outC, lvi_pt* outS, double n_pts);
+// lvi_gmap.hip
+void gmap_join(LidarDev& d);                               // wait for a global-map build in flight (lvi_keyframes_clear)
+void gmap_free(LidarDev& d);                               // … and free the arena (lvi_lidar_destroy)
 
 }  // namespace lvi

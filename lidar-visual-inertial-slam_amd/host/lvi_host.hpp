@@ -221,6 +221,44 @@ inline void getTranslationAndEulerAngles(const Affine3f& t, float& x, float& y, 
 
 struct PointTypePose { float x, y, z, intensity, roll, pitch, yaw; double time; };     // utility.h:71-78
 
+// ---- key-pose searches shared by extractNearby (:894-929) and publishGlobalMap (:460-510) ----------------------------
+inline float keyPoseSqDist(const lvi_pt& a, const lvi_pt& b)
+{
+    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// kdtree radiusSearch(center, radius) over the key poses: sorted by distance (brute force, ties by index)
+inline std::vector<lvi_pt> keyPosesWithin(const std::vector<lvi_pt>& keyPoses3D, const lvi_pt& center, double radius)
+{
+    std::vector<std::pair<float, int>> hits;
+    for (int i = 0; i < (int)keyPoses3D.size(); i++) {
+        const float d = keyPoseSqDist(keyPoses3D[i], center);
+        if ((double)d <= radius * radius) hits.push_back({d, i});
+    }
+    std::stable_sort(hits.begin(), hits.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    std::vector<lvi_pt> out;
+    for (auto& hpair : hits) out.push_back(keyPoses3D[hpair.second]);
+    return out;
+}
+// the VoxelGrid of key poses (downSizeFilterSurroundingKeyPoses, downSizeFilterGlobalMapKeyPoses): the library's
+inline std::vector<lvi_pt> downsampleKeyPoses(lvi_lidar* h, const std::vector<lvi_pt>& poses, float leaf)
+{
+    std::vector<lvi_pt> ds(std::max<size_t>(poses.size(), 1));
+    int32_t nds = 0;
+    check(lvi_voxel_downsample(h, poses.data(), (int32_t)poses.size(), leaf, ds.data(), (int32_t)ds.size(), &nds), "lvi_voxel_downsample(key poses)");
+    ds.resize(nds);
+    return ds;
+}
+// nearestKSearch(pt, 1) over all key poses for every DS pose: its intensity becomes the nearest key's index (first on ties)
+inline void assignNearestKeys(const std::vector<lvi_pt>& keyPoses3D, std::vector<lvi_pt>& ds)
+{
+    for (auto& pt : ds) {
+        int best = 0; float bd = keyPoseSqDist(keyPoses3D[0], pt);
+        for (int i = 1; i < (int)keyPoses3D.size(); i++) { const float d = keyPoseSqDist(keyPoses3D[i], pt); if (d < bd) { bd = d; best = i; } }
+        pt.intensity = keyPoses3D[best].intensity;
+    }
+}
+
 struct MapCallerParams {                       // params_lidar.yaml:17,60-66 (utility.h:176,278-288)
     bool   useImuHeadingInitialization = false;
     double mappingProcessInterval = 0.15;
@@ -316,28 +354,10 @@ public:
 
     void extractNearby()                                                                  // :894-929
     {
-        const lvi_pt back = cloudKeyPoses3D.back();
-        const double radius = (double)P.surroundingKeyframeSearchRadius;
-        // kdtree radiusSearch (sorted by distance; brute force over the key poses, ties by index)
-        std::vector<std::pair<float, int>> hits;
-        for (int i = 0; i < (int)cloudKeyPoses3D.size(); i++) {
-            const float d = sqDist(cloudKeyPoses3D[i], back);
-            if ((double)d <= radius * radius) hits.push_back({d, i});
-        }
-        std::stable_sort(hits.begin(), hits.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-        std::vector<lvi_pt> surroundingKeyPoses;
-        for (auto& hpair : hits) surroundingKeyPoses.push_back(cloudKeyPoses3D[hpair.second]);
-        // downSizeFilterSurroundingKeyPoses: the library's VoxelGrid, leaf surroundingKeyframeDensity
-        std::vector<lvi_pt> surroundingKeyPosesDS(std::max<size_t>(surroundingKeyPoses.size(), 1));
-        int32_t nds = 0;
-        check(lvi_voxel_downsample(h_.get(), surroundingKeyPoses.data(), (int32_t)surroundingKeyPoses.size(), P.surroundingKeyframeDensity,
-                                   surroundingKeyPosesDS.data(), (int32_t)surroundingKeyPosesDS.size(), &nds), "lvi_voxel_downsample(key poses)");
-        surroundingKeyPosesDS.resize(nds);
-        for (auto& pt : surroundingKeyPosesDS) {                                          // nearestKSearch(pt, 1) → the key's index
-            int best = 0; float bd = sqDist(cloudKeyPoses3D[0], pt);
-            for (int i = 1; i < (int)cloudKeyPoses3D.size(); i++) { const float d = sqDist(cloudKeyPoses3D[i], pt); if (d < bd) { bd = d; best = i; } }
-            pt.intensity = cloudKeyPoses3D[best].intensity;
-        }
+        // kdtree radiusSearch, downSizeFilterSurroundingKeyPoses (the library's VoxelGrid, leaf surroundingKeyframeDensity), nearestKSearch
+        std::vector<lvi_pt> surroundingKeyPosesDS = downsampleKeyPoses(
+            h_.get(), keyPosesWithin(cloudKeyPoses3D, cloudKeyPoses3D.back(), (double)P.surroundingKeyframeSearchRadius), P.surroundingKeyframeDensity);
+        assignNearestKeys(cloudKeyPoses3D, surroundingKeyPosesDS);
         for (int i = (int)cloudKeyPoses3D.size() - 1; i >= 0; --i) {                      // the latest key frames (robot rotating in place)
             if (timeLaserInfoCur - cloudKeyPoses6D[i].time < 10.0) surroundingKeyPosesDS.push_back(cloudKeyPoses3D[i]);
             else break;
@@ -349,7 +369,7 @@ public:
     {
         lastKeys.clear();
         for (const lvi_pt& pt : cloudToExtract) {
-            if (std::sqrt(sqDist(pt, cloudKeyPoses3D.back())) > P.surroundingKeyframeSearchRadius) continue;     // pointDistance (utility.h:408-411)
+            if (std::sqrt(keyPoseSqDist(pt, cloudKeyPoses3D.back())) > P.surroundingKeyframeSearchRadius) continue;     // pointDistance (utility.h:408-411)
             lastKeys.push_back((int32_t)pt.intensity);
         }
         if (P.incrementalMap) check(lvi_map_update(h_.get(), lastKeys.data(), (int32_t)lastKeys.size()), "lvi_map_update");
@@ -399,11 +419,6 @@ public:
         lastSavedKeyFrame = true;
     }
 private:
-    static float sqDist(const lvi_pt& a, const lvi_pt& b)
-    {
-        const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-        return (dx * dx + dy * dy) + dz * dz;
-    }
     void applyIncrement(const Affine3f& transIncre)
     {
         const Affine3f transTobe = getTransformation(transformTobeMapped[3], transformTobeMapped[4], transformTobeMapped[5],

@@ -78,6 +78,7 @@ lvh_seq* lvh_seq_create(const lvi_lidar_params* lp, int32_t device, const lvh_se
 }
 void lvh_seq_destroy(lvh_seq* s) { delete s; }
 lvi_lidar* lvh_seq_handle(lvh_seq* s) { return s ? s->h->get() : nullptr; }
+void* lvh_seq_node(lvh_seq* s) { return s ? s->mo.get() : nullptr; }      // the MapOptimizationNode (lvi_gmap_capi.cpp)
 
 static void fill_result(lvh_seq* s, bool processed, lvh_seq_result* out)
 {

@@ -2,10 +2,18 @@
 // odometry messages (mapOptimization.cpp:161-177, 238-245, 298-333, 1666-1746).  updateInitialGuess, extractNearby, the
 // keyframe decision and the key poses run in lvi_host::MapOptimizationNode (host C++ over the C-ABI); the keyframe clouds,
 // the local map (incremental lvi_map_update), downsampleCurrentScan and scan2MapOptimization run on the MI355X.
-// Outside the hot path and therefore NOT reproduced here: the GTSAM / iSAM2 factor graph, GPS and loop factors,
-// the save_map service and the visualisation thread — the key pose pushed is the scan-matching result ("odometry chain").
-// Builds only where rclcpp, tf2_ros, pcl_conversions and the lidar_odometry messages exist.
+// The global map (publishGlobalMap on its 0.2 Hz thread, :421-427 / :460-510), the save_map service (:179-238) and the
+// shutdown save (:428-457) fuse the device keyframe store on the MI355X through lvi_host::GlobalMapper (include/lvi_gmap.h);
+// the files are written with pcl::io as the reference writes them.  Deviation: the directory is created and the files are
+// overwritten; the reference's `rm -r` of the directory is not reproduced.
+// Outside the hot path and therefore NOT reproduced here: the GTSAM / iSAM2 factor graph, GPS and loop factors
+// — the key pose pushed is the scan-matching result ("odometry chain").
+// Builds only where rclcpp, tf2_ros, pcl_conversions and the lidar_odometry messages / services exist.
+#include <cstdlib>
+#include <iostream>
+#include <filesystem>
 #include <mutex>
+#include <thread>
 
 #include <pcl/point_cloud.h>
 #include <pcl/point_types.h>
@@ -18,19 +26,38 @@
 #include <tf2_geometry_msgs/tf2_geometry_msgs.hpp>
 #include <tf2_ros/transform_broadcaster.h>
 
+#include "../lvi_gmap_host.hpp"
 #include "../lvi_host.hpp"
 #include "lidar_odometry/msg/cloud_info.hpp"
-#include "utility.h"   // the reference's ParamServer, publishCloud, qos, stamp2Sec
+#include "lidar_odometry/srv/save_map.hpp"
+#include "utility.h"   // the reference's ParamServer, publishCloud, qos, stamp2Sec (and pcl/io/pcd_io.h)
+
+// cloudKeyPoses6D's point type (mapOptimization.cpp:29-44): x y z intensity roll pitch yaw (float), time (double)
+struct PointXYZIRPYT {
+    PCL_ADD_POINT4D;
+    PCL_ADD_INTENSITY;
+    float roll;
+    float pitch;
+    float yaw;
+    double time;
+    EIGEN_MAKE_ALIGNED_OPERATOR_NEW
+} EIGEN_ALIGN16;
+POINT_CLOUD_REGISTER_POINT_STRUCT(PointXYZIRPYT, (float, x, x)(float, y, y)(float, z, z)(float, intensity, intensity)(float, roll, roll)
+                                                 (float, pitch, pitch)(float, yaw, yaw)(double, time, time))
 
 class mapOptimization : public ParamServer {
     rclcpp::Publisher<nav_msgs::msg::Odometry>::SharedPtr pubLaserOdometryGlobal, pubLaserOdometryIncremental;
-    rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr pubKeyPoses, pubRecentKeyFrames;
+    rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr pubKeyPoses, pubRecentKeyFrames, pubLaserCloudSurround;
     rclcpp::Publisher<nav_msgs::msg::Path>::SharedPtr pubPath;
     rclcpp::Subscription<lidar_odometry::msg::CloudInfo>::SharedPtr subCloud;
+    rclcpp::Service<lidar_odometry::srv::SaveMap>::SharedPtr srvSaveMap;
     std::unique_ptr<tf2_ros::TransformBroadcaster> br;
-    std::mutex mtx;
+    std::mutex mtx;               // the node's state and every call on the handle but lvi_gmap_result / lvi_gmap_fetch
+    std::mutex gmapMtx;           // one global-map build at a time, with its result / fetch (taken before mtx)
     std::unique_ptr<lvi_host::LidarHandle> handle;
     std::unique_ptr<lvi_host::MapOptimizationNode> mo;
+    std::unique_ptr<lvi_host::GlobalMapper> gmap;
+    rclcpp::Time timeLaserInfoStamp;
     nav_msgs::msg::Path globalPath;
     // incremental odometry (publishOdometry :1693-1741)
     bool lastIncreOdomPubFlag = false;
@@ -54,6 +81,13 @@ public:
         c.surroundingKeyframeDensity = surroundingKeyframeDensity; c.surroundingKeyframeSearchRadius = surroundingKeyframeSearchRadius;
         c.sensorIsLivox = sensor == SensorType::LIVOX;
         mo = std::make_unique<lvi_host::MapOptimizationNode>(*handle, c);
+        lvi_host::GlobalMapParams g;
+        g.globalMapVisualizationSearchRadius = globalMapVisualizationSearchRadius;
+        g.globalMapVisualizationPoseDensity = globalMapVisualizationPoseDensity;
+        g.globalMapVisualizationLeafSize = globalMapVisualizationLeafSize;
+        gmap = std::make_unique<lvi_host::GlobalMapper>(*mo, handle->get(), g);
+        gmap->reserve(p.max_keyframe_points);                                                                          // the arena, once
+        pubLaserCloudSurround = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/map_global", 1);       // :162
         pubKeyPoses = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/trajectory", 1);                 // :161-167
         pubLaserOdometryGlobal = create_publisher<nav_msgs::msg::Odometry>("lio_sam/mapping/odometry", qos);
         pubLaserOdometryIncremental = create_publisher<nav_msgs::msg::Odometry>("lio_sam/mapping/odometry_incremental", qos);
@@ -62,6 +96,89 @@ public:
         br = std::make_unique<tf2_ros::TransformBroadcaster>(this);
         subCloud = create_subscription<lidar_odometry::msg::CloudInfo>(                                                  // :169-171
             "lio_sam/feature/cloud_info", qos, std::bind(&mapOptimization::laserCloudInfoHandler, this, std::placeholders::_1));
+        srvSaveMap = create_service<lidar_odometry::srv::SaveMap>(                                                      // :179-238
+            "lio_sam/save_map", [this](const std::shared_ptr<rmw_request_id_t>, const std::shared_ptr<lidar_odometry::srv::SaveMap::Request> req,
+                                       std::shared_ptr<lidar_odometry::srv::SaveMap::Response> res) {
+                const std::string dir = std::string(std::getenv("HOME")) + (req->destination.empty() ? savePCDDirectory : req->destination);
+                RCLCPP_INFO(get_logger(), "Saving map to pcd files in %s", dir.c_str());
+                res->success = saveMap(dir, req->resolution, req->resolution, req->resolution != 0, false);
+            });
+    }
+
+    static pcl::PointCloud<pcl::PointXYZI>::Ptr toPcl(const std::vector<lvi_pt>& v)
+    {
+        pcl::PointCloud<pcl::PointXYZI>::Ptr c(new pcl::PointCloud<pcl::PointXYZI>());
+        c->resize(v.size());
+        for (size_t i = 0; i < v.size(); i++) { auto& q = (*c)[i]; q.x = v[i].x; q.y = v[i].y; q.z = v[i].z; q.intensity = v[i].intensity; }
+        return c;
+    }
+
+    // save_map (binary: trajectory, transformations, CornerMap, SurfMap, GlobalMap; :179-236) or the shutdown save (ASCII:
+    // trajectory, transformations, cloudCorner, cloudSurf, cloudGlobal; :428-457).  The fuse runs on the GPU under the node's
+    // mutex; the files are written outside it.  Returns what save_map's `success` reports: the GlobalMap write.
+    bool saveMap(const std::string& dir, float leafCorner, float leafSurf, bool filtered, bool ascii)
+    {
+        std::vector<lvi_pt> raw[2], ds[2];
+        pcl::PointCloud<pcl::PointXYZI>::Ptr kp3 = nullptr;
+        pcl::PointCloud<PointXYZIRPYT>::Ptr kp6(new pcl::PointCloud<PointXYZIRPYT>());
+        {
+            std::lock_guard<std::mutex> g(gmapMtx);
+            std::lock_guard<std::mutex> lock(mtx);
+            gmap->fuseAll(filtered ? leafCorner : 0.f, filtered ? leafSurf : 0.f, raw, ds);
+            kp3 = toPcl(mo->cloudKeyPoses3D);
+            for (const lvi_host::PointTypePose& p : mo->cloudKeyPoses6D) {
+                PointXYZIRPYT q; q.x = p.x; q.y = p.y; q.z = p.z; q.intensity = p.intensity; q.roll = p.roll; q.pitch = p.pitch; q.yaw = p.yaw; q.time = p.time;
+                kp6->push_back(q);
+            }
+        }
+        std::error_code ec;
+        std::filesystem::create_directories(dir, ec);
+        const std::string d = dir.empty() || dir.back() == '/' ? dir : dir + "/";
+        pcl::PointCloud<pcl::PointXYZI>::Ptr global = toPcl(raw[0]);
+        *global += *toPcl(raw[1]);                                      // the RAW corner cloud, then the RAW surf cloud
+        if (ascii) {
+            pcl::io::savePCDFileASCII(d + "trajectory.pcd", *kp3);
+            pcl::io::savePCDFileASCII(d + "transformations.pcd", *kp6);
+            pcl::io::savePCDFileASCII(d + "cloudCorner.pcd", *toPcl(ds[0]));
+            pcl::io::savePCDFileASCII(d + "cloudSurf.pcd", *toPcl(ds[1]));
+            return pcl::io::savePCDFileASCII(d + "cloudGlobal.pcd", *global) == 0;
+        }
+        pcl::io::savePCDFileBinary(d + "trajectory.pcd", *kp3);
+        pcl::io::savePCDFileBinary(d + "transformations.pcd", *kp6);
+        pcl::io::savePCDFileBinary(d + "CornerMap.pcd", *toPcl(ds[0]));
+        pcl::io::savePCDFileBinary(d + "SurfMap.pcd", *toPcl(ds[1]));
+        return pcl::io::savePCDFileBinary(d + "GlobalMap.pcd", *global) == 0;
+    }
+
+    // publishGlobalMap (:460-510): the node's mutex is held for the key selection and the enqueue of the build only; the
+    // wait for the GPU and the copy of the cloud run beside the scan path (include/lvi_gmap.h's concurrency rule)
+    void publishGlobalMap()
+    {
+        if (pubLaserCloudSurround->get_subscription_count() == 0) return;
+        std::lock_guard<std::mutex> g(gmapMtx);
+        rclcpp::Time stamp;
+        {
+            std::lock_guard<std::mutex> lock(mtx);
+            if (!gmap->startGlobalMap()) return;                                                  // no key poses
+            stamp = timeLaserInfoStamp;
+        }
+        std::vector<lvi_pt> cloud;
+        gmap->finishGlobalMap(cloud);
+        publishCloud(pubLaserCloudSurround, toPcl(cloud), stamp, odometryFrame);
+    }
+
+    void visualizeGlobalMapThread()                                                                // :421-457
+    {
+        rclcpp::Rate rate(0.2);
+        while (rclcpp::ok()) {
+            rate.sleep();
+            try { publishGlobalMap(); }
+            catch (const std::exception& e) { RCLCPP_ERROR(get_logger(), "publishGlobalMap: %s", e.what()); }
+        }
+        if (!savePCD) return;
+        const std::string dir = std::string(std::getenv("HOME")) + savePCDDirectory;
+        std::cout << "Saving map to pcd files in " << dir << std::endl;
+        saveMap(dir, mappingCornerLeafSize, mappingSurfLeafSize, true, true);
     }
 
     static void toHost(const sensor_msgs::msg::PointCloud2& msg, std::vector<lvi_pt>& out)
@@ -81,6 +198,7 @@ public:
         ci.initial_guess_roll = msgIn->initial_guess_roll; ci.initial_guess_pitch = msgIn->initial_guess_pitch; ci.initial_guess_yaw = msgIn->initial_guess_yaw;
         toHost(msgIn->cloud_corner, ci.cloud_corner); toHost(msgIn->cloud_surface, ci.cloud_surface);
         std::lock_guard<std::mutex> lock(mtx);
+        timeLaserInfoStamp = msgIn->header.stamp;
         const float* T = mo->transformTobeMapped;
         incrementalOdometryAffineFront = lvi_host::getTransformation(T[3], T[4], T[5], T[0], T[1], T[2]);          // updateInitialGuess :809
         if (!mo->laserCloudInfoHandler(ci)) return;                                      // mappingProcessInterval gate; else: guess, map, match, keyframe
@@ -162,8 +280,10 @@ int main(int argc, char** argv)
     rclcpp::executors::SingleThreadedExecutor exec;
     auto MO = std::make_shared<mapOptimization>(options);
     exec.add_node(MO);
+    std::thread visualizeMapThread(&mapOptimization::visualizeGlobalMapThread, MO);             // :1799
     RCLCPP_INFO(rclcpp::get_logger("rclcpp"), "\033[1;32m----> Map Optimization Started (MI355X scan matching).\033[0m");
     exec.spin();
     rclcpp::shutdown();
+    visualizeMapThread.join();                                                                  // the shutdown save runs there
     return 0;
 }

@@ -35,6 +35,8 @@ FUNDAMENTAL_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C
 DEPTH_SOURCES = ("lvi_depth_capi.cpp",)
 # the device RANSAC's (include/lvi_fmat.h, the same restriction)
 FMAT_SOURCES = ("lvi_fmat_capi.cpp",)
+# the global mapper's (include/lvi_gmap.h, the same restriction)
+GMAP_SOURCES = ("lvi_gmap_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -43,7 +45,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
     deps = srcs + [os.path.join(HOST_DIR, "lvi_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_hotpath.h")]
     if sources:
         deps += [os.path.join(HOST_DIR, "lvi_depth_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_depth.h"),
-                 os.path.join(HOST_DIR, "lvi_fmat_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmat.h")]
+                 os.path.join(HOST_DIR, "lvi_fmat_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmat.h"),
+                 os.path.join(HOST_DIR, "lvi_gmap_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_gmap.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -92,6 +95,17 @@ class HostLibrary:
             d.lvh_depth_install.argtypes = [C.c_void_p, C.c_void_p]
             d.lvh_depth_lidar.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_int32)]
             d.lvh_depth_set_image_pose.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self.has_gmap = hasattr(d, "lvh_gmap_create")      # the HIP host library only
+        if self.has_gmap:
+            d.lvh_gmap_last_error.restype = C.c_char_p
+            d.lvh_gmap_create.restype = C.c_void_p
+            d.lvh_gmap_create.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
+            d.lvh_gmap_destroy.argtypes = [C.c_void_p]
+            d.lvh_gmap_reserve.argtypes = [C.c_void_p, C.c_int32]
+            d.lvh_gmap_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+            d.lvh_gmap_publish.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+            d.lvh_gmap_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+            d.lvh_gmap_save.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
         self.has_fmat = hasattr(d, "lvh_trk_use_device_fundamental")      # the HIP host library only
         if self.has_fmat:
             d.lvh_fmat_last_error.restype = C.c_char_p
@@ -294,3 +308,58 @@ class NodeDepthRegister:
     def set_image_pose(self, pose6):
         """the transform the next image's get_depth reads (the reference's TF lookup at Time(0))"""
         self._check(self.hl.dll.lvh_depth_set_image_pose(self._d, self._pose(pose6)), "lvh_depth_set_image_pose")
+
+
+class GlobalMapper:
+    """lvi_host::GlobalMapper (host/lvi_gmap_host.hpp) over a SequentialMapper's node: publishGlobalMap
+    (mapOptimization.cpp:460-510) and the save_map service (:179-236).  HIP host library only."""
+
+    def __init__(self, hostlib, mapper, search_radius=1000.0, pose_density=1.0, leaf_size=0.05):
+        if not hostlib.has_gmap:
+            raise RuntimeError("this host library has no global mapper (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        self._g = hostlib.dll.lvh_gmap_create(mapper._s, float(search_radius), float(pose_density), float(leaf_size))
+        if not self._g:
+            raise A.LviError(-1, "lvh_gmap_create", hostlib.dll.lvh_gmap_last_error().decode(errors="replace"))
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_gmap_last_error().decode(errors="replace"))
+        return code
+
+    def close(self):
+        if self._g:
+            self.hl.dll.lvh_gmap_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reserve(self, max_points):
+        self._check(self.hl.dll.lvh_gmap_reserve(self._g, int(max_points)), "lvh_gmap_reserve")
+
+    def keys(self):
+        """publishGlobalMap steps 2-6: the key clouds of globalMapKeyFrames in fuse order"""
+        n = C.c_int32(0)
+        self._check(self.hl.dll.lvh_gmap_keys(self._g, None, 0, C.byref(n)), "lvh_gmap_keys")
+        out = np.zeros(max(n.value, 1), np.int32)
+        self._check(self.hl.dll.lvh_gmap_keys(self._g, A._ptr(out), len(out), C.byref(n)), "lvh_gmap_keys")
+        return out[:n.value].copy()
+
+    def publishGlobalMap(self):
+        """the published cloud and dict(n_fused, n_out, overflow, filtered); None when there are no key poses"""
+        info = (C.c_int32 * 4)()
+        if self._check(self.hl.dll.lvh_gmap_publish(self._g, info), "lvh_gmap_publish") == 0:
+            return None
+        n = C.c_int32(0)
+        self._check(self.hl.dll.lvh_gmap_cloud(self._g, None, 0, C.byref(n)), "lvh_gmap_cloud")
+        out = np.zeros(max(n.value, 1), A.PT_DTYPE)
+        self._check(self.hl.dll.lvh_gmap_cloud(self._g, A._ptr(out), len(out), C.byref(n)), "lvh_gmap_cloud")
+        return out[:n.value].copy(), dict(n_fused=info[0], n_out=info[1], overflow=bool(info[2]), filtered=bool(info[3]))
+
+    def saveMap(self, directory, resolution):
+        """the save_map service: five binary PCD files in `directory`; returns its `success`"""
+        return bool(self._check(self.hl.dll.lvh_gmap_save(self._g, os.fsencode(str(directory)), float(resolution)), "lvh_gmap_save"))
