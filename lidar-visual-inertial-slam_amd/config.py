@@ -28,6 +28,26 @@ def load_lidar_yaml(path):
     return lidar, caller, rest
 
 
+LOOP_KEYS = dict(loopClosureEnableFlag="enable", loopClosureFrequency="frequency", historyKeyframeSearchRadius="search_radius",
+                 historyKeyframeSearchTimeDiff="search_time_diff", historyKeyframeSearchNum="search_num", historyKeyframeFitnessScore="fitness_score")
+
+
+def load_loop_yaml(path):
+    """→ the loop-closure settings of params_lidar.yaml (utility.h:281-286): dict(enable, frequency, search_radius,
+    search_time_diff, search_num, fitness_score, surf_leaf), the settings of host_api.LoopCloser and of the loop thread;
+    surf_leaf = mappingSurfLeafSize, the submaps' VoxelGrid"""
+    node = yaml.safe_load(open(path))
+    for k in ("/**", "ros__parameters"):
+        node = node[k]
+    out = {v: node[k] for k, v in LOOP_KEYS.items()}
+    out["enable"] = bool(out["enable"])
+    out["search_num"] = int(out["search_num"])
+    for k in ("frequency", "search_radius", "search_time_diff", "fitness_score"):
+        out[k] = float(out[k])
+    out["surf_leaf"] = float(node["mappingSurfLeafSize"])
+    return out
+
+
 def _opencv_yaml(path):
     txt = open(path).read()
     txt = re.sub(r"^%YAML[:\s]*1\.0\s*$", "", txt, flags=re.M)          # FileStorage header is not YAML 1.1 directive syntax

@@ -281,6 +281,7 @@ void lvi_lidar_destroy(lvi_lidar* h)
     if (d.ctx.stream) { (void)hipStreamSynchronize(d.ctx.stream); }
     if (d.ctx2.stream) { (void)hipStreamSynchronize(d.ctx2.stream); }
     try { gmap_free(d); } catch (...) {}
+    try { loop_free(d); } catch (...) {}
     d.prof.collect();
     for (auto& q : h->more) release_slot(*q);
     release_slot(d);
@@ -781,6 +782,7 @@ int32_t lvi_keyframes_clear(lvi_lidar* h)
         LidarDev& d = h->d;
         join_map(d); sync(d);                                        // an assembly in flight still reads the pool
         gmap_join(d);                                                // … and so may a global-map build
+        loop_join(d);                                                // … or a loop-closure job
         d.kf_off_c.clear(); d.kf_n_c.clear(); d.kf_off_s.clear(); d.kf_n_s.clear(); d.kf_pose.clear(); d.kf_pool_used = 0;
         d.inc_ready = false; d.inc_mult.clear(); d.inc_pose.clear();
         return LVI_OK;

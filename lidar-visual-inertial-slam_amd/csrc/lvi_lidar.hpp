@@ -56,6 +56,7 @@ struct GridIndex {                       // uniform 0.5 m grid over one DS map (
 };
 
 struct GmapDev;                                         // lvi_gmap.hip: the global-map arena (include/lvi_gmap.h)
+struct LoopDev;                                         // lvi_loop.hip: the loop-closure arena (include/lvi_loop.h)
 
 struct LidarDev {
     lvi_lidar_params P;
@@ -158,6 +159,7 @@ struct LidarDev {
     LidarDev* map_owner = nullptr;                         // slot 0 for z > 0
     const lvi_livox_pt* raw_bound = nullptr;               // lvi_scan_batch_bind_device: the scan is read in place (no copy)
     GmapDev* gmap = nullptr;                               // lvi_gmap_reserve (slot 0): null until then, nothing allocated
+    LoopDev* loop = nullptr;                               // lvi_loop_reserve (slot 0): likewise
 };
 
 // the scans of one batched launch sequence: slot 0 owns the streams, the profiler and the raw local map
@@ -198,5 +200,8 @@ void kf_assemble_launch(const Ctx& cx, const LidarDev::KfSeg* d_segs, int nseg, 
 // lvi_gmap.hip
 void gmap_join(LidarDev& d);                               // wait for a global-map build in flight (lvi_keyframes_clear)
 void gmap_free(LidarDev& d);                               // … and free the arena (lvi_lidar_destroy)
+// lvi_loop.hip
+void loop_join(LidarDev& d);                               // wait for a loop-closure job in flight (lvi_keyframes_clear)
+void loop_free(LidarDev& d);                               // … and free the arena (lvi_lidar_destroy)
 
 }  // namespace lvi

@@ -418,6 +418,7 @@ public:
         cloudKeyPoses3D.push_back(thisPose3D); cloudKeyPoses6D.push_back(thisPose6D);
         lastSavedKeyFrame = true;
     }
+    double laserTime() const { return timeLaserInfoCur; }                                  // stamp of the last scan taken (the loop thread's time rule)
 private:
     void applyIncrement(const Affine3f& transIncre)
     {

@@ -6,10 +6,15 @@
 // shutdown save (:428-457) fuse the device keyframe store on the MI355X through lvi_host::GlobalMapper (include/lvi_gmap.h);
 // the files are written with pcl::io as the reference writes them.  Deviation: the directory is created and the files are
 // overwritten; the reference's `rm -r` of the directory is not reproduced.
-// Outside the hot path and therefore NOT reproduced here: the GTSAM / iSAM2 factor graph, GPS and loop factors
-// — the key pose pushed is the scan-matching result ("odometry chain").
+// The loop-closure thread (:523-535) runs performLoopClosure through lvi_host::LoopCloser (include/lvi_loop.h): the key
+// search on the host, the two submaps and the ICP on the MI355X; it publishes the two clouds and visualizeLoopClosure's
+// markers and leaves the constraints in takeLoopConstraints() for a GTSAM back end.
+// Outside the hot path and therefore NOT reproduced here: the GTSAM / iSAM2 factor graph, GPS and the
+// APPLICATION of loop factors (addLoopFactor, correctPoses) — the key pose pushed is the scan-matching result ("odometry
+// chain"), which does not consume the constraint queue.
 // Builds only where rclcpp, tf2_ros, pcl_conversions and the lidar_odometry messages / services exist.
 #include <cstdlib>
+#include <deque>
 #include <iostream>
 #include <filesystem>
 #include <mutex>
@@ -22,12 +27,15 @@
 #include <nav_msgs/msg/odometry.hpp>
 #include <nav_msgs/msg/path.hpp>
 #include <sensor_msgs/msg/point_cloud2.hpp>
+#include <std_msgs/msg/float64_multi_array.hpp>
+#include <visualization_msgs/msg/marker_array.hpp>
 #include <tf2/LinearMath/Quaternion.h>
 #include <tf2_geometry_msgs/tf2_geometry_msgs.hpp>
 #include <tf2_ros/transform_broadcaster.h>
 
 #include "../lvi_gmap_host.hpp"
 #include "../lvi_host.hpp"
+#include "../lvi_loop_host.hpp"
 #include "lidar_odometry/msg/cloud_info.hpp"
 #include "lidar_odometry/srv/save_map.hpp"
 #include "utility.h"   // the reference's ParamServer, publishCloud, qos, stamp2Sec (and pcl/io/pcd_io.h)
@@ -49,14 +57,22 @@ class mapOptimization : public ParamServer {
     rclcpp::Publisher<nav_msgs::msg::Odometry>::SharedPtr pubLaserOdometryGlobal, pubLaserOdometryIncremental;
     rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr pubKeyPoses, pubRecentKeyFrames, pubLaserCloudSurround;
     rclcpp::Publisher<nav_msgs::msg::Path>::SharedPtr pubPath;
+    rclcpp::Publisher<sensor_msgs::msg::PointCloud2>::SharedPtr pubHistoryKeyFrames, pubIcpKeyFrames;
+    rclcpp::Publisher<visualization_msgs::msg::MarkerArray>::SharedPtr pubLoopConstraintEdge;
+    rclcpp::Subscription<std_msgs::msg::Float64MultiArray>::SharedPtr subLoop;
     rclcpp::Subscription<lidar_odometry::msg::CloudInfo>::SharedPtr subCloud;
     rclcpp::Service<lidar_odometry::srv::SaveMap>::SharedPtr srvSaveMap;
     std::unique_ptr<tf2_ros::TransformBroadcaster> br;
-    std::mutex mtx;               // the node's state and every call on the handle but lvi_gmap_result / lvi_gmap_fetch
+    std::mutex mtx;               // the node's state and every call on the handle but lvi_gmap_result / lvi_gmap_fetch / lvi_loop_result / lvi_loop_fetch
     std::mutex gmapMtx;           // one global-map build at a time, with its result / fetch (taken before mtx)
     std::unique_ptr<lvi_host::LidarHandle> handle;
     std::unique_ptr<lvi_host::MapOptimizationNode> mo;
     std::unique_ptr<lvi_host::GlobalMapper> gmap;
+    std::mutex loopMtx;           // one loop job at a time, with its result / fetch (taken before mtx)
+    std::mutex mtxLoopInfo;       // loopInfoVec (:539)
+    std::mutex loopQueueMtx;      // the constraint queue
+    std::unique_ptr<lvi_host::LoopCloser> loop;
+    std::deque<lvi_host::LoopConstraint> loopConstraints;      // loopIndexQueue / loopPoseQueue / loopNoiseQueue for a GTSAM back end
     rclcpp::Time timeLaserInfoStamp;
     nav_msgs::msg::Path globalPath;
     // incremental odometry (publishOdometry :1693-1741)
@@ -87,6 +103,21 @@ public:
         g.globalMapVisualizationLeafSize = globalMapVisualizationLeafSize;
         gmap = std::make_unique<lvi_host::GlobalMapper>(*mo, handle->get(), g);
         gmap->reserve(p.max_keyframe_points);                                                                          // the arena, once
+        lvi_host::LoopParams lpp;
+        lpp.loopClosureEnableFlag = loopClosureEnableFlag; lpp.loopClosureFrequency = loopClosureFrequency;
+        lpp.historyKeyframeSearchRadius = historyKeyframeSearchRadius; lpp.historyKeyframeSearchTimeDiff = historyKeyframeSearchTimeDiff;
+        lpp.historyKeyframeSearchNum = historyKeyframeSearchNum; lpp.historyKeyframeFitnessScore = historyKeyframeFitnessScore;
+        lpp.mappingSurfLeafSize = mappingSurfLeafSize;
+        loop = std::make_unique<lvi_host::LoopCloser>(*mo, handle->get(), lpp);
+        if (loopClosureEnableFlag) loop->reserve(1 << 20, 1 << 24);                                                    // the arena, once: one key / 2 n + 1 keys
+        pubHistoryKeyFrames = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/icp_loop_closure_history_cloud", 1);   // :239
+        pubIcpKeyFrames = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/icp_loop_closure_history_cloud", 1);       // :240 (the same topic, as written)
+        pubLoopConstraintEdge = create_publisher<visualization_msgs::msg::MarkerArray>("/lio_sam/mapping/loop_closure_constraints", 1);
+        subLoop = create_subscription<std_msgs::msg::Float64MultiArray>(                                                 // :175-177
+            "/vins/loop/match_frame", qos, [this](const std_msgs::msg::Float64MultiArray::SharedPtr m) {
+                std::lock_guard<std::mutex> lock(mtxLoopInfo);
+                loop->loopInfoHandler(m->data.data(), m->data.size());
+            });
         pubLaserCloudSurround = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/map_global", 1);       // :162
         pubKeyPoses = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/trajectory", 1);                 // :161-167
         pubLaserOdometryGlobal = create_publisher<nav_msgs::msg::Odometry>("lio_sam/mapping/odometry", qos);
@@ -179,6 +210,82 @@ public:
         const std::string dir = std::string(std::getenv("HOME")) + savePCDDirectory;
         std::cout << "Saving map to pcd files in " << dir << std::endl;
         saveMap(dir, mappingCornerLeafSize, mappingSurfLeafSize, true, true);
+    }
+
+    // performLoopClosure (:549-628): the node's mutex is held for the pose copies, the key search and the enqueue of the job
+    // only; the wait for the GPU, the gates and the constraint run beside the scan path (include/lvi_loop.h's concurrency rule)
+    void performLoopClosure()
+    {
+        std::lock_guard<std::mutex> g(loopMtx);
+        rclcpp::Time stamp;
+        {
+            std::lock_guard<std::mutex> lock(mtx);
+            std::lock_guard<std::mutex> li(mtxLoopInfo);
+            if (!loop->startLoop()) return;                                                       // no key poses, no loop found
+            stamp = timeLaserInfoStamp;
+        }
+        const bool pushed = loop->finishLoop();
+        if (loop->lastInfo.status == LVI_LOOP_TOO_FEW_POINTS) return;                            // :572-573
+        std::vector<lvi_pt> cloud;
+        if (pubHistoryKeyFrames->get_subscription_count() != 0) {                                 // :574-575
+            loop->fetch(LVI_LOOP_TARGET, cloud);
+            publishCloud(pubHistoryKeyFrames, toPcl(cloud), stamp, odometryFrame);
+        }
+        if (!pushed) return;                                                                      // :592-593
+        if (pubIcpKeyFrames->get_subscription_count() != 0) {                                     // :596-601
+            loop->fetch(LVI_LOOP_ALIGNED, cloud);
+            publishCloud(pubIcpKeyFrames, toPcl(cloud), stamp, odometryFrame);
+        }
+        std::lock_guard<std::mutex> q(loopQueueMtx);                                              // :620-624
+        while (!loop->loopQueue.empty()) { loopConstraints.push_back(loop->loopQueue.front()); loop->loopQueue.pop_front(); }
+    }
+
+    // the constraints found since the last call, oldest first: what addLoopFactor (:1491-1508) of a GTSAM back end consumes
+    std::deque<lvi_host::LoopConstraint> takeLoopConstraints()
+    {
+        std::lock_guard<std::mutex> q(loopQueueMtx);
+        std::deque<lvi_host::LoopConstraint> out;
+        out.swap(loopConstraints);
+        return out;
+    }
+
+    void visualizeLoopClosure()                                                                   // :743-794
+    {
+        std::lock_guard<std::mutex> g(loopMtx);
+        if (loop->loopIndexContainer.empty()) return;
+        visualization_msgs::msg::MarkerArray markerArray;
+        visualization_msgs::msg::Marker markerNode, markerEdge;
+        rclcpp::Time stamp;
+        { std::lock_guard<std::mutex> lock(mtx); stamp = timeLaserInfoStamp; }
+        markerNode.header.frame_id = odometryFrame; markerNode.header.stamp = stamp;
+        markerNode.action = visualization_msgs::msg::Marker::ADD; markerNode.type = visualization_msgs::msg::Marker::SPHERE_LIST;
+        markerNode.ns = "loop_nodes"; markerNode.id = 0; markerNode.pose.orientation.w = 1;
+        markerNode.scale.x = 0.3; markerNode.scale.y = 0.3; markerNode.scale.z = 0.3;
+        markerNode.color.r = 0; markerNode.color.g = 0.8; markerNode.color.b = 1; markerNode.color.a = 1;
+        markerEdge.header.frame_id = odometryFrame; markerEdge.header.stamp = stamp;
+        markerEdge.action = visualization_msgs::msg::Marker::ADD; markerEdge.type = visualization_msgs::msg::Marker::LINE_LIST;
+        markerEdge.ns = "loop_edges"; markerEdge.id = 1; markerEdge.pose.orientation.w = 1; markerEdge.scale.x = 0.1;
+        markerEdge.color.r = 0.9; markerEdge.color.g = 0.9; markerEdge.color.b = 0; markerEdge.color.a = 1;
+        for (const auto& kv : loop->loopIndexContainer) {
+            for (int key : {kv.first, kv.second}) {
+                geometry_msgs::msg::Point p;
+                p.x = loop->copy_cloudKeyPoses6D[key].x; p.y = loop->copy_cloudKeyPoses6D[key].y; p.z = loop->copy_cloudKeyPoses6D[key].z;
+                markerNode.points.push_back(p); markerEdge.points.push_back(p);
+            }
+        }
+        markerArray.markers.push_back(markerNode); markerArray.markers.push_back(markerEdge);
+        pubLoopConstraintEdge->publish(markerArray);
+    }
+
+    void loopClosureThread()                                                                      // :523-535
+    {
+        if (loopClosureEnableFlag == false) return;
+        rclcpp::Rate rate(loopClosureFrequency);
+        while (rclcpp::ok()) {
+            rate.sleep();
+            try { performLoopClosure(); visualizeLoopClosure(); }
+            catch (const std::exception& e) { RCLCPP_ERROR(get_logger(), "performLoopClosure: %s", e.what()); }
+        }
     }
 
     static void toHost(const sensor_msgs::msg::PointCloud2& msg, std::vector<lvi_pt>& out)
@@ -280,10 +387,12 @@ int main(int argc, char** argv)
     rclcpp::executors::SingleThreadedExecutor exec;
     auto MO = std::make_shared<mapOptimization>(options);
     exec.add_node(MO);
+    std::thread loopthread(&mapOptimization::loopClosureThread, MO);                            // :1798
     std::thread visualizeMapThread(&mapOptimization::visualizeGlobalMapThread, MO);             // :1799
     RCLCPP_INFO(rclcpp::get_logger("rclcpp"), "\033[1;32m----> Map Optimization Started (MI355X scan matching).\033[0m");
     exec.spin();
     rclcpp::shutdown();
+    loopthread.join();
     visualizeMapThread.join();                                                                  // the shutdown save runs there
     return 0;
 }

@@ -37,6 +37,8 @@ DEPTH_SOURCES = ("lvi_depth_capi.cpp",)
 FMAT_SOURCES = ("lvi_fmat_capi.cpp",)
 # the global mapper's (include/lvi_gmap.h, the same restriction)
 GMAP_SOURCES = ("lvi_gmap_capi.cpp",)
+# the loop closer's (include/lvi_loop.h, the same restriction)
+LOOP_SOURCES = ("lvi_loop_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -46,7 +48,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
     if sources:
         deps += [os.path.join(HOST_DIR, "lvi_depth_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_depth.h"),
                  os.path.join(HOST_DIR, "lvi_fmat_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmat.h"),
-                 os.path.join(HOST_DIR, "lvi_gmap_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_gmap.h")]
+                 os.path.join(HOST_DIR, "lvi_gmap_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_gmap.h"),
+                 os.path.join(HOST_DIR, "lvi_loop_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_loop.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -106,6 +109,22 @@ class HostLibrary:
             d.lvh_gmap_publish.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
             d.lvh_gmap_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
             d.lvh_gmap_save.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
+        self.has_loop = hasattr(d, "lvh_loop_create")      # the HIP host library only
+        if self.has_loop:
+            from .loop import LoopInfo
+            d.lvh_loop_last_error.restype = C.c_char_p
+            d.lvh_loop_create.restype = C.c_void_p
+            d.lvh_loop_create.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_int32]
+            d.lvh_loop_destroy.argtypes = [C.c_void_p]
+            d.lvh_loop_reserve.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+            d.lvh_loop_info_msg.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
+            d.lvh_loop_detect.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_int32)]
+            d.lvh_loop_start.argtypes = [C.c_void_p, C.c_double]
+            d.lvh_loop_finish.argtypes = [C.c_void_p, C.POINTER(LoopInfo)]
+            d.lvh_loop_queue_size.argtypes = [C.c_void_p]
+            d.lvh_loop_pop.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float)]
+            d.lvh_loop_closed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+            d.lvh_loop_cloud.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         self.has_fmat = hasattr(d, "lvh_trk_use_device_fundamental")      # the HIP host library only
         if self.has_fmat:
             d.lvh_fmat_last_error.restype = C.c_char_p
@@ -363,3 +382,100 @@ class GlobalMapper:
     def saveMap(self, directory, resolution):
         """the save_map service: five binary PCD files in `directory`; returns its `success`"""
         return bool(self._check(self.hl.dll.lvh_gmap_save(self._g, os.fsencode(str(directory)), float(resolution)), "lvh_gmap_save"))
+
+
+class LoopCloser:
+    """lvi_host::LoopCloser (host/lvi_loop_host.hpp) over a SequentialMapper's node: the loop-closure thread of
+    mapOptimization.cpp (:523-741) up to the constraint queue.  HIP host library only."""
+
+    def __init__(self, hostlib, mapper, search_radius=15.0, search_time_diff=30.0, search_num=25, fitness_score=0.3, surf_leaf=0.4,
+                 incremental_cloud=1, **_ignored):
+        if not hostlib.has_loop:
+            raise RuntimeError("this host library has no loop closer (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        self._g = hostlib.dll.lvh_loop_create(mapper._s, float(search_radius), float(search_time_diff), int(search_num), float(fitness_score),
+                                              float(surf_leaf), int(incremental_cloud))
+        if not self._g:
+            raise A.LviError(-1, "lvh_loop_create", hostlib.dll.lvh_loop_last_error().decode(errors="replace"))
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_loop_last_error().decode(errors="replace"))
+        return code
+
+    def close(self):
+        if self._g:
+            self.hl.dll.lvh_loop_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reserve(self, max_source_points, max_target_points):
+        self._check(self.hl.dll.lvh_loop_reserve(self._g, int(max_source_points), int(max_target_points)), "lvh_loop_reserve")
+
+    def loopInfoHandler(self, data):
+        """a loop-info message (kept only when it holds two values); returns the queue's length"""
+        d = np.ascontiguousarray(data, np.float64).reshape(-1)
+        return self._check(self.hl.dll.lvh_loop_info_msg(self._g, d.ctypes.data_as(C.POINTER(C.c_double)), len(d)), "lvh_loop_info_msg")
+
+    def _detect(self, which, t):
+        keys = (C.c_int32 * 2)(-1, -1)
+        ok = self._check(self.hl.dll.lvh_loop_detect(self._g, which, float(t), keys), "lvh_loop_detect")
+        return (keys[0], keys[1]) if ok else None
+
+    def detectLoopClosureDistance(self, time_laser_info_cur):
+        """(cur, pre) or None, on fresh copies of the node's key poses"""
+        return self._detect(0, time_laser_info_cur)
+
+    def detectLoopClosureExternal(self):
+        return self._detect(1, 0.0)
+
+    def startLoop(self, time_laser_info_cur):
+        """the key search and the enqueue of the device job; False when no loop was found"""
+        return bool(self._check(self.hl.dll.lvh_loop_start(self._g, float(time_laser_info_cur)), "lvh_loop_start"))
+
+    def finishLoop(self):
+        """(pushed, info): waits for the job, applies the gates and pushes the constraint"""
+        from .loop import LoopInfo
+        r = LoopInfo()
+        ok = bool(self._check(self.hl.dll.lvh_loop_finish(self._g, C.byref(r)), "lvh_loop_finish"))
+        info = {k: getattr(r, k) for k, _ in LoopInfo._fields_ if k != "transformation"}
+        info["transformation"] = np.array(r.transformation, np.float32).reshape(4, 4)
+        return ok, info
+
+    def performLoopClosure(self, time_laser_info_cur):
+        if not self.startLoop(time_laser_info_cur):
+            return False, None
+        return self.finishLoop()
+
+    def queue_size(self):
+        return int(self.hl.dll.lvh_loop_queue_size(self._g))
+
+    def pop(self):
+        """the oldest constraint: dict(key_cur, key_pre, between [4, 4] float64, noise) or None"""
+        keys = (C.c_int32 * 2)()
+        b = np.zeros(16, np.float64)
+        noise = C.c_float(0)
+        if not self._check(self.hl.dll.lvh_loop_pop(self._g, keys, b.ctypes.data_as(C.POINTER(C.c_double)), C.byref(noise)), "lvh_loop_pop"):
+            return None
+        return dict(key_cur=keys[0], key_pre=keys[1], between=b.reshape(4, 4), noise=float(noise.value))
+
+    def closed(self):
+        """loopIndexContainer as {cur: pre}"""
+        n = C.c_int32(0)
+        self._check(self.hl.dll.lvh_loop_closed(self._g, None, 0, C.byref(n)), "lvh_loop_closed")
+        out = np.zeros((max(n.value, 1), 2), np.int32)
+        self._check(self.hl.dll.lvh_loop_closed(self._g, A._ptr(out), len(out), C.byref(n)), "lvh_loop_closed")
+        return {int(a): int(b) for a, b in out[:n.value]}
+
+    def cloud(self, what):
+        """the target submap (loop.TARGET, pubHistoryKeyFrames) or the aligned source (loop.ALIGNED, pubIcpKeyFrames) of the last job"""
+        n = C.c_int32(0)
+        self._check(self.hl.dll.lvh_loop_cloud(self._g, int(what), None, 0, C.byref(n)), "lvh_loop_cloud")
+        out = np.zeros(max(n.value, 1), A.PT_DTYPE)
+        self._check(self.hl.dll.lvh_loop_cloud(self._g, int(what), A._ptr(out), len(out), C.byref(n)), "lvh_loop_cloud")
+        return out[:n.value].copy()

@@ -1,0 +1,317 @@
+"""CPU tier of the loop-closure registration (include/lvi_loop.h, host/lvi_loop_host.hpp): known-answer tests of the
+restatement (loop_ref.py) in both precisions, of the host mirror's key search and constraint compiled from its header,
+the exports of the two HIP-side libraries, the yaml loader, and the GPU tier's scenes against the 300 / 1000 gates and the
+fitness gate."""
+import ctypes as C
+import os
+import subprocess
+import textwrap
+
+import numpy as np
+import pytest
+
+import loop_ref as LR
+import loop_scenes as SC
+from helpers import small_params
+
+F32, F64 = np.float32, np.float64
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "lidar-visual-inertial-slam_amd")
+
+
+def _exports(path):
+    r = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True)
+    return {line.split()[-1] for line in r.stdout.splitlines() if line.strip()}
+
+
+def test_hip_library_exports_loop(pkg):
+    syms = _exports(pkg.HIP_LIB_PATH)
+    for name in pkg.loop.LOOP_SIGNATURES:
+        assert name in syms, name
+    with open(os.path.join(REPO, "include", "lvi_hotpath.h")) as f:
+        assert "lvi_loop" not in f.read()                     # a separate ABI: lvi_hotpath.h (and the oracle) untouched
+    with open(os.path.join(REPO, "include", "lvi_loop.h")) as f:
+        hdr = f.read()
+    assert "#define LVI_LOOP_ABI_VERSION 1" in hdr
+    for name in pkg.loop.LOOP_SIGNATURES:
+        assert name + "(" in hdr, name
+    assert pkg.LoopIcp is pkg.loop.LoopIcp
+
+
+def test_host_library_links_loop(pkg):
+    syms = _exports(pkg.host_api.HOST_HIP_LIB)
+    for name in ("lvh_loop_create", "lvh_loop_reserve", "lvh_loop_info_msg", "lvh_loop_detect", "lvh_loop_start", "lvh_loop_finish", "lvh_loop_pop",
+                 "lvh_loop_closed", "lvh_loop_cloud"):
+        assert name in syms, name
+    assert "lvh_loop_create" not in _exports(pkg.HIP_LIB_PATH)
+    assert "lvi_loop_capi.cpp" in pkg.host_api.LOOP_SOURCES
+
+
+def test_oracle_does_not_export_loop(pkg, oracle):
+    assert not hasattr(oracle.dll, "lvi_loop_start")
+
+
+def test_load_loop_yaml(pkg):
+    d = pkg.config.load_loop_yaml(os.path.join(REPO, "tests", "golden", "params_lidar.yaml"))
+    assert d == dict(enable=True, frequency=1.0, search_radius=15.0, search_time_diff=30.0, search_num=25, fitness_score=0.3, surf_leaf=0.4)
+    assert isinstance(d["search_num"], int) and isinstance(d["enable"], bool)
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------------------
+def _cloud(n, seed, scale=10.0):
+    return np.random.default_rng(seed).uniform(-scale, scale, (n, 3))
+
+
+@pytest.mark.parametrize("precision,tol", [("f32", 2e-4), ("f64", 1e-9)])
+def test_icp_recovers_rigid_motion(precision, tol):
+    """a cloud against its own rigidly moved copy: the motion is recovered and the fitness vanishes"""
+    tgt = _cloud(400, 1)
+    M = LR.rpy_matrix(0.12, -0.08, 0.05, 0.01, -0.015, 0.02)
+    src = LR.transform(np.linalg.inv(M), tgt)                            # M maps the source back onto the target
+    for inc in (True, False):
+        r = LR.icp(src, tgt, LR.nn_exhaustive, precision=precision, incremental_cloud=inc)
+        assert r["status"] == LR.OK and r["converged"] and r["n_corr"] == 400
+        assert np.abs(r["T"].astype(F64) - M).max() < tol, (precision, inc)
+        assert r["fitness"] < tol ** 2 * 10 + 1e-12
+        assert np.abs(r["aligned"].astype(F64) - tgt).max() < 10 * tol + 1e-9
+
+
+def test_umeyama_reflection_branch():
+    """a mirrored configuration: det U det V < 0, the last singular direction flips and R stays a rotation"""
+    P = np.array([[3.0, 0, 0], [-3.0, 0, 0], [0, 2.0, 0], [0, -2.0, 0], [0, 0, 1.0], [0, 0, -1.0]])   # z: the smallest singular direction
+    Q = P * np.array([1.0, 1.0, -1.0])                                   # mirrored in z
+    for dt in (F32, F64):
+        T, reflected = LR.umeyama(P.astype(dt), Q.astype(dt))
+        assert reflected
+        R = T[:3, :3].astype(F64)
+        assert abs(np.linalg.det(R) - 1.0) < 1e-5 and np.abs(R @ R.T - np.eye(3)).max() < 1e-5
+        # the best ROTATION for a z mirror keeps x and y and cannot undo the mirror
+        assert np.abs(R - np.eye(3)).max() < 1e-5
+    T, reflected = LR.umeyama(P, LR.transform(LR.rpy_matrix(1, 2, 3, 0.3, 0.2, 0.1), P))
+    assert not reflected and np.abs(T - LR.rpy_matrix(1, 2, 3, 0.3, 0.2, 0.1)).max() < 1e-12
+
+
+def _step(angle=0.0, t=0.0, dt=F64):
+    return LR.rpy_matrix(t, 0.0, 0.0, 0.0, 0.0, angle).astype(dt)
+
+
+def test_convergence_states_in_order():
+    """DefaultConvergenceCriteria: each state by a constructed sequence, and their order of precedence"""
+    big = _step(0.1, 0.5)
+    # iteration limit (counts as converged) before everything else, even with an identity step and a zero MSE
+    c = LR.Criteria(max_iters=2)
+    assert not c.has_converged(big, [1.0]) and c.state == LR.NOT_CONVERGED
+    assert c.has_converged(_step(), [0.0]) and c.state == LR.ITERATIONS and c.iterations == 2
+    # the transform test: cos >= 1 - eps AND |t|^2 <= eps; either alone is not enough
+    c = LR.Criteria()
+    assert not c.has_converged(_step(0.0, 2e-3), [1.0])                  # |t|^2 = 4e-6 > 1e-6
+    assert not c.has_converged(_step(2e-3, 0.0), [2.0])                  # 1 - cos = 2e-6 > 1e-6
+    assert c.has_converged(_step(1e-3, 0.9e-3), [3.0]) and c.state == LR.TRANSFORM     # 1 - cos = 5e-7, |t|^2 = 8.1e-7
+    # absolute MSE before relative MSE
+    c = LR.Criteria()
+    assert not c.has_converged(big, [1e-13 * 1e3])
+    assert c.has_converged(big, [1e-13, 1e-13]) and c.state == LR.ABS_MSE
+    # relative MSE: the previous value starts at +max (never relative-converged on the first iteration)
+    c = LR.Criteria()
+    assert not c.has_converged(big, [4.0, 2.0]) and c.mse == 3.0 and c.prev_mse == 3.0
+    assert not c.has_converged(big, [3.0 * (1 + 2e-6)])
+    assert c.has_converged(big, [3.0 * (1 + 2e-6) * (1 - 5e-7)]) and c.state == LR.REL_MSE
+    # f32 steps are read in f32
+    c = LR.Criteria()
+    assert c.has_converged(_step(1e-4, 1e-4, F32), [1.0]) and c.state == LR.TRANSFORM
+
+
+def test_fewer_than_three_correspondences():
+    tgt = _cloud(50, 2)
+    src = _cloud(20, 3) + 100.0                                          # nothing within 30 m
+    src[:2] = tgt[:2] + 0.01                                             # two pairs only
+    for precision in ("f32", "f64"):
+        r = LR.icp(src, tgt, LR.nn_exhaustive, precision=precision)
+        assert r["status"] == LR.NO_CORR and not r["converged"] and r["state"] == LR.NO_CORRESPONDENCES and r["n_corr"] == 2
+        assert r["iterations"] == 0 and np.array_equal(r["T"], np.eye(4))
+    r = LR.icp(src, tgt, LR.nn_exhaustive, min_source=21)
+    assert r["status"] == LR.TOO_FEW_POINTS
+    r = LR.icp(src, tgt, LR.nn_exhaustive, min_target=51)
+    assert r["status"] == LR.TOO_FEW_POINTS
+
+
+def test_fitness_hand_case():
+    """the mean squared NN distance of EVERY source point under the final transformation, no distance cut"""
+    tgt = np.array([[0.0, 0, 0], [10.0, 0, 0], [0, 10.0, 0], [0, 0, 10.0]])
+    src = np.vstack([tgt, [[1000.0, 0, 0]]])                             # four exact pairs and one point 990 m from its neighbour
+    r = LR.icp(src, tgt, LR.nn_exhaustive, precision="f64", max_corr_dist=5.0)
+    assert r["converged"] and r["n_corr"] == 4 and np.abs(r["T"] - np.eye(4)).max() < 1e-12
+    assert abs(r["fitness"] - 990.0 ** 2 / 5) < 1e-6
+    idx, d = LR.nn_exhaustive(np.array([[1.0, 1.0, 0.0]]), np.array([[2.0, 1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]))
+    assert idx[0] == 0 and d[0] == 1.0                                   # three equidistant points: the lowest index
+
+
+def test_nn_variants_agree(oracle):
+    q, t = _cloud(300, 5).astype(F32), _cloud(2000, 6).astype(F32)
+    ia, da = LR.nn_exhaustive(q, t)
+    ib, db = LR.nn_kdtree(oracle)(q, t)
+    np.testing.assert_array_equal(da, db)
+    assert np.all((ia == ib) | (LR.sqd(q, t[ib]) == da))
+    ic, dc = LR.nn_reranked(oracle)(q.astype(F64), t.astype(F64))
+    id_, dd = LR.nn_exhaustive(q.astype(F64), t.astype(F64))
+    np.testing.assert_array_equal(ic, id_)
+    np.testing.assert_array_equal(dc, dd)
+
+
+# ---- the host mirror, compiled from its header ------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def mirror(tmp_path_factory):
+    d = tmp_path_factory.mktemp("loop_host")
+    src = d / "m.cpp"
+    src.write_text(textwrap.dedent("""
+        #include "lvi_loop_host.hpp"
+        using namespace lvi_host;
+        static void poses(const double* p, int n, std::vector<lvi_pt>& p3, std::vector<PointTypePose>& p6)
+        {
+            for (int i = 0; i < n; i++) {
+                p3.push_back(lvi_pt{(float)p[4 * i], (float)p[4 * i + 1], (float)p[4 * i + 2], (float)i});
+                p6.push_back(PointTypePose{(float)p[4 * i], (float)p[4 * i + 1], (float)p[4 * i + 2], (float)i, 0.f, 0.f, 0.f, p[4 * i + 3]});
+            }
+        }
+        static std::map<int, int> closed_map(const int* closed, int n) { std::map<int, int> m; for (int i = 0; i < n; i++) m[closed[2 * i]] = closed[2 * i + 1]; return m; }
+        // p: [n][4] = x, y, z, time; closed: [nc][2]
+        extern "C" int detect_distance(const double* p, int n, const int* closed, int nc, double now, float radius, float tdiff, int* out)
+        {
+            std::vector<lvi_pt> p3; std::vector<PointTypePose> p6; poses(p, n, p3, p6);
+            LoopParams P; P.historyKeyframeSearchRadius = radius; P.historyKeyframeSearchTimeDiff = tdiff;
+            return loopDetectDistance(p3, p6, closed_map(closed, nc), P, now, out, out + 1) ? 1 : 0;
+        }
+        // msgs: [nm][2] = loopTimeCur, loopTimePre (oldest first); *left = messages still queued afterwards
+        extern "C" int detect_external(const double* p, int n, const int* closed, int nc, const double* msgs, int nm, float tdiff, int* out, int* left)
+        {
+            std::vector<lvi_pt> p3; std::vector<PointTypePose> p6; poses(p, n, p3, p6);
+            LoopParams P; P.historyKeyframeSearchTimeDiff = tdiff;
+            std::deque<std::pair<double, double>> q;
+            for (int i = 0; i < nm; i++) q.push_back({msgs[2 * i], msgs[2 * i + 1]});
+            const bool ok = loopDetectExternal(q, p6, closed_map(closed, nc), P, out, out + 1);
+            *left = (int)q.size();
+            return ok ? 1 : 0;
+        }
+        // poses as (roll, pitch, yaw, x, y, z)
+        extern "C" void constraint_of(const float* corr, const float* cur, const float* pre, double fitness, double* between, float* noise)
+        {
+            const PointTypePose a{cur[3], cur[4], cur[5], 0.f, cur[0], cur[1], cur[2], 0.0}, b{pre[3], pre[4], pre[5], 1.f, pre[0], pre[1], pre[2], 0.0};
+            const LoopConstraint c = LoopCloser::constraintOf(corr, a, b, 7, 3, fitness);
+            for (int i = 0; i < 16; i++) between[i] = c.between[i];
+            *noise = c.noise;
+        }
+        """))
+    so = d / "libm.so"
+    # declarations only from the product headers: nothing of the HIP library is called, so nothing is linked
+    subprocess.run(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-I", os.path.join(PKG, "host"), str(src), "-o", str(so),
+                    "-Wl,--unresolved-symbols=ignore-all"], check=True)
+    return C.CDLL(str(so))
+
+
+def _pp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _dist(mirror, poses, now, closed=(), radius=15.0, tdiff=30.0):
+    p = np.ascontiguousarray(poses, F64)
+    cl = np.ascontiguousarray(np.asarray(closed, np.int32).reshape(-1, 2))
+    out = np.full(2, -7, np.int32)
+    mirror.detect_distance.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p]
+    ok = mirror.detect_distance(_pp(p), len(p), _pp(cl), len(cl), now, radius, tdiff, _pp(out))
+    return (int(out[0]), int(out[1])) if ok else None
+
+
+def test_detect_distance_hand_cases(mirror):
+    """nearest first (not lowest index first), the time rule, a key already closed, cur == pre"""
+    # x, y, z, time.  The last key (cur = 4, t = 100) sees keys 0 (3 m), 1 (1 m) and 2 (2 m) of an old pass and key 3 (0.5 m, recent)
+    poses = [(3.0, 0, 0, 0.0), (1.0, 0, 0, 1.0), (0.0, 2.0, 0, 2.0), (0.5, 0, 0, 99.0), (0.0, 0, 0, 100.0)]
+    assert _dist(mirror, poses, 100.0) == (4, 1)                          # the nearest OLD key: 1, not 0 and not the nearer recent 3
+    assert _dist(mirror, poses, 100.0, radius=0.9) is None                # only the recent key and cur itself within reach
+    assert _dist(mirror, poses, 100.0, closed=[(4, 1)]) is None           # cur already closed
+    assert _dist(mirror, poses, 100.0, closed=[(3, 1)]) == (4, 1)         # another key's loop does not matter
+    assert _dist(mirror, poses, 100.0, tdiff=99.5) == (4, 0)              # only key 0 is more than 99.5 s old
+    assert _dist(mirror, poses, 100.0, tdiff=200.0) is None
+    # the rule is |time - timeLaserInfoCur|, the node's clock, not the newest key's stamp
+    # and cur == pre: at t = 20 the first hit, cur itself (distance 0, |100 - 20| > 30), passes the rule: no loop, although
+    # key 3 would pass it as well
+    assert _dist(mirror, poses, 20.0, tdiff=30.0) is None
+    assert _dist(mirror, poses, 110.0, tdiff=10.5) == (4, 3)              # the node's clock: |100 - 110| <= 10.5 < |99 - 110|
+    # cur == pre: the newest key is the first hit (distance 0); when it alone passes the time rule there is no loop
+    assert _dist(mirror, [(0.0, 0, 0, 100.0)], 0.0) is None
+    assert _dist(mirror, [(1.0, 0, 0, 50.0), (0.0, 0, 0, 100.0)], 45.0, tdiff=30.0) is None   # first hit is cur itself (|100 - 45| > 30): cur == pre
+    # equal distances: the lower index
+    poses = [(1.0, 0, 0, 0.0), (-1.0, 0, 0, 0.0), (0, 1.0, 0, 0.0), (0.0, 0, 0, 100.0)]
+    assert _dist(mirror, poses, 100.0) == (3, 0)
+
+
+def _ext(mirror, poses, msgs, closed=(), tdiff=30.0):
+    p = np.ascontiguousarray(poses, F64)
+    cl = np.ascontiguousarray(np.asarray(closed, np.int32).reshape(-1, 2))
+    ms = np.ascontiguousarray(np.asarray(msgs, F64).reshape(-1, 2))
+    out = np.full(2, -7, np.int32)
+    left = C.c_int(-1)
+    mirror.detect_external.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int)]
+    ok = mirror.detect_external(_pp(p), len(p), _pp(cl), len(cl), _pp(ms), len(ms), tdiff, _pp(out), C.byref(left))
+    return ((int(out[0]), int(out[1])) if ok else None), left.value
+
+
+def test_detect_external_hand_cases(mirror):
+    poses = [(float(i), 0, 0, 10.0 * i) for i in range(8)]               # stamps 0, 10, …, 70
+    assert _ext(mirror, poses, []) == (None, 0)
+    # cur: the earliest key with stamp >= 55 (key 6); pre: the latest key with stamp <= 12 (key 1); the message is consumed
+    assert _ext(mirror, poses, [(55.0, 12.0), (1.0, 2.0)]) == ((6, 1), 1)
+    assert _ext(mirror, poses, [(55.0, 40.0)]) == (None, 0)               # the two times less than 30 s apart
+    assert _ext(mirror, poses, [(55.0, 12.0)], closed=[(6, 0)]) == (None, 0)
+    assert _ext(mirror, poses, [(500.0, 12.0)]) == ((7, 1), 0)            # no key that late: the newest
+    assert _ext(mirror, poses, [(55.0, -5.0)]) == ((6, 0), 0)             # no key that early: key 0
+    assert _ext(mirror, poses[:1], [(55.0, 12.0)]) == (None, 0)           # fewer than two keys
+    assert _ext(mirror, poses, [(-40.0, -80.0)]) == (None, 0)             # cur == pre == 0
+
+
+def test_constraint_between_matches_float64(mirror):
+    """tCorrect = correction * tWrong and its Euler angles in f32, the gtsam poses and between() in double: against the
+    float64 numpy computation to f32 resolution of the poses"""
+    rng = np.random.default_rng(11)
+    mirror.constraint_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_float)]
+    for _ in range(20):
+        cur = np.concatenate([rng.uniform(-0.3, 0.3, 2), rng.uniform(-3, 3, 1), rng.uniform(-30, 30, 3)]).astype(F32)
+        pre = np.concatenate([rng.uniform(-0.3, 0.3, 2), rng.uniform(-3, 3, 1), rng.uniform(-30, 30, 3)]).astype(F32)
+        corr = LR.rpy_matrix(*rng.uniform(-0.5, 0.5, 3), *rng.uniform(-0.03, 0.03, 3)).astype(F32)
+        between = np.zeros(16, F64)
+        noise = C.c_float(0)
+        mirror.constraint_of(_pp(np.ascontiguousarray(corr)), _pp(cur), _pp(pre), 0.123456789, _pp(between), C.byref(noise))
+        ref = LR.constraint(corr.astype(F64), cur, pre)
+        B = between.reshape(4, 4)
+        assert np.abs(B[:3, :3] - ref[:3, :3]).max() < 2e-6 and np.abs(B[:3, 3] - ref[:3, 3]).max() < 5e-5
+        np.testing.assert_array_equal(B[3], [0, 0, 0, 1])
+        assert noise.value == float(F32(0.123456789))
+    # identity correction, cur == pre: between is the identity to f32 rounding of the Euler round trip
+    mirror.constraint_of(_pp(np.eye(4, dtype=F32)), _pp(cur), _pp(cur), 0.0, _pp(between), C.byref(noise))
+    assert np.abs(between.reshape(4, 4) - np.eye(4)).max() < 5e-5
+
+
+# ---- the GPU tier's scenes, confirmed on the CPU -------------------------------------------------------------------------
+def test_scenes_pass_gates_and_sit_clear_of_the_fitness_gate(pkg, oracle):
+    """every scene of test_gpu_loop.py: the filtered submaps pass the 300 / 1000 gates, the float64 reference accepts the
+    drifted revisits and rejects the other two with its fitness well away from 0.3, and on the revisits it brings the drifted
+    pose closer to the truth"""
+    passes = SC.base_passes(pkg, oracle)
+    ora = pkg.LidarHotpath(oracle, **small_params(max_map_points=1 << 21))
+    for name in SC.DRIFTS:
+        sc = SC.scene(name, passes)
+        assert sc["stamps"][SC.CUR] - sc["stamps"][SC.PRE] > 30.0
+        refs = SC.submaps_ref(pkg, ora, sc["kfs"], SC.CUR, SC.PRE)
+        src, tgt = refs[0]["pts"], refs[1]["pts"]
+        assert not refs[0]["overflow"] and not refs[1]["overflow"]
+        assert len(src) >= 300 and len(tgt) >= 1000, (name, len(src), len(tgt))
+        r32, r64 = SC.reference_pair(oracle, src, tgt)
+        print(f"[scene] {name}: source {len(src)} target {len(tgt)}; f64 converged {r64['converged']} state {r64['state']} iterations {r64['iterations']} "
+              f"fitness {r64['fitness']:.6g}; f32 iterations {r32['iterations']} fitness {r32['fitness']:.6g}; gaps {SC.gaps(r32['T'], r32['fitness'], r64['T'], r64['fitness'])}")
+        for r in (r32, r64):
+            assert (r["converged"] and r["fitness"] <= SC.FITNESS_GATE) == SC.ACCEPT[name], name
+            assert abs(r["fitness"] - SC.FITNESS_GATE) > 0.1, name
+        if SC.ACCEPT[name]:
+            res = r64["T"] @ sc["D"]
+            assert LR.rot_angle(np.eye(4), res) < 0.25 * LR.rot_angle(np.eye(4), sc["D"])
+            assert np.linalg.norm(res[:3, 3]) < 0.25 * np.linalg.norm(sc["D"][:3, 3])
+    ora.close()
