@@ -73,3 +73,19 @@ def load_camera_lidar_yaml(path):
     dict(use_lidar, lidar_skip, point_cloud_topic), the keyword arguments of the depth register and the node"""
     d = _opencv_yaml(path)
     return dict(use_lidar=int(d["use_lidar"]), lidar_skip=int(d["lidar_skip"]), point_cloud_topic=str(d["point_cloud_topic"]))
+
+
+def load_brief_pattern(path):
+    """→ (x1, y1, x2, y2): the BRIEF pair offsets of support_files/brief_pattern.yml (OpenCV FileStorage yaml; what
+    BriefExtractor's constructor reads, keyframe.cpp:273-291), 256 ints each within ±24: the pattern argument of
+    kf.KeyframeDescriber"""
+    d = _opencv_yaml(path)
+    out = []
+    for k in ("x1", "y1", "x2", "y2"):
+        v = d.get(k)
+        if not isinstance(v, list) or len(v) != 256:
+            raise ValueError(f"{path}: {k} must hold 256 entries")
+        if any(isinstance(e, bool) or not isinstance(e, int) or abs(e) > 24 for e in v):
+            raise ValueError(f"{path}: {k} must hold integers within ±24")
+        out.append([int(e) for e in v])
+    return tuple(out)

@@ -17,6 +17,7 @@
 // minimum-distance pick done by one wavefront with ballot-resolved conflicts.
 #include <algorithm>
 
+#include "lvi_mei.hpp"
 #include "lvi_sort.hpp"
 
 namespace lvi {
@@ -169,34 +170,13 @@ __global__ __launch_bounds__(256) void clahe_interp_kernel(ClaheArgs a)
 // f-3  CataCamera::liftProjective with the 8-step recursive distortion model + (b.x/b.z, b.y/b.z) → Point2f
 // (CataCamera.cc:556-626, 766-783; feature_tracker.cpp:306-309).  All in double, one thread per point.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void mei_distortion(const lvi_mei_params& c, double pux, double puy, double& dux, double& duy)
-{
-    const double mx2_u = pux * pux, my2_u = puy * puy, mxy_u = pux * puy;
-    const double rho2_u = mx2_u + my2_u;
-    const double rad_dist_u = c.k1 * rho2_u + c.k2 * rho2_u * rho2_u;
-    dux = pux * rad_dist_u + 2.0 * c.p1 * mxy_u + c.p2 * (rho2_u + 2.0 * mx2_u);
-    duy = puy * rad_dist_u + 2.0 * c.p2 * mxy_u + c.p1 * (rho2_u + 2.0 * my2_u);
-}
-
+// (the device function lives in lvi_mei.hpp: the keyframe describer of lvi_kf.hip compiles the same code)
 __global__ __launch_bounds__(64) void mei_undistort_kernel(lvi_mei_params c, const float* __restrict__ xy, int n, float* __restrict__ out, const int* __restrict__ n_dev = nullptr)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (n_dev) n = min(n, *n_dev);                  // (the count of a device-side concatenation)
     if (i >= n) return;
-    const double inv_K11 = 1.0 / c.gamma1, inv_K13 = -c.u0 / c.gamma1, inv_K22 = 1.0 / c.gamma2, inv_K23 = -c.v0 / c.gamma2;
-    const bool noDistortion = c.k1 == 0.0 && c.k2 == 0.0 && c.p1 == 0.0 && c.p2 == 0.0;
-    const double mx_d = inv_K11 * (double)xy[2 * i] + inv_K13, my_d = inv_K22 * (double)xy[2 * i + 1] + inv_K23;
-    double mx_u = mx_d, my_u = my_d;
-    if (!noDistortion) {
-        double dux, duy;
-        mei_distortion(c, mx_d, my_d, dux, duy);
-        mx_u = mx_d - dux; my_u = my_d - duy;
-        for (int it = 1; it < 8; ++it) { mei_distortion(c, mx_u, my_u, dux, duy); mx_u = mx_d - dux; my_u = my_d - duy; }
-    }
-    double bz;
-    if (c.xi == 1.0) bz = (1.0 - mx_u * mx_u - my_u * my_u) / 2.0;
-    else { const double rho2_d = mx_u * mx_u + my_u * my_u; bz = 1.0 - c.xi * (rho2_d + 1.0) / (c.xi + sqrt(1.0 + (1.0 - c.xi * c.xi) * rho2_d)); }
-    out[2 * i] = (float)(mx_u / bz); out[2 * i + 1] = (float)(my_u / bz);
+    mei_lift_normalized(c, xy[2 * i], xy[2 * i + 1], out[2 * i], out[2 * i + 1]);
 }
 
 // setMask (feature_tracker.cpp:36-69): mask = 255, then cv::circle(mask, pt, MIN_DIST, 0, -1) around every kept point.  The

@@ -39,6 +39,8 @@ FMAT_SOURCES = ("lvi_fmat_capi.cpp",)
 GMAP_SOURCES = ("lvi_gmap_capi.cpp",)
 # the loop closer's (include/lvi_loop.h, the same restriction)
 LOOP_SOURCES = ("lvi_loop_capi.cpp",)
+# the keyframe describer's (include/lvi_kf.h, the same restriction)
+KF_SOURCES = ("lvi_kf_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -49,7 +51,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
         deps += [os.path.join(HOST_DIR, "lvi_depth_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_depth.h"),
                  os.path.join(HOST_DIR, "lvi_fmat_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmat.h"),
                  os.path.join(HOST_DIR, "lvi_gmap_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_gmap.h"),
-                 os.path.join(HOST_DIR, "lvi_loop_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_loop.h")]
+                 os.path.join(HOST_DIR, "lvi_loop_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_loop.h"),
+                 os.path.join(HOST_DIR, "lvi_kf_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_kf.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -125,6 +128,20 @@ class HostLibrary:
             d.lvh_loop_pop.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float)]
             d.lvh_loop_closed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
             d.lvh_loop_cloud.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        self.has_kf = hasattr(d, "lvh_kf_create")      # the HIP host library only
+        if self.has_kf:
+            ip = C.POINTER(C.c_int32)
+            d.lvh_kf_last_error.restype = C.c_char_p
+            d.lvh_kf_create.restype = C.c_void_p
+            d.lvh_kf_create.argtypes = [C.c_int32] * 6 + [ip] * 4
+            d.lvh_kf_destroy.argtypes = [C.c_void_p]
+            d.lvh_kf_handle.restype = C.c_void_p
+            d.lvh_kf_handle.argtypes = [C.c_void_p]
+            d.lvh_kf_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.POINTER(A.MeiParams), ip]
+            d.lvh_kf_remove.argtypes = [C.c_void_p, C.c_int32]
+            d.lvh_kf_connect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip]
+            d.lvh_kf_connection.argtypes = [C.c_void_p] * 8 + [C.c_int32]
         self.has_fmat = hasattr(d, "lvh_trk_use_device_fundamental")      # the HIP host library only
         if self.has_fmat:
             d.lvh_fmat_last_error.restype = C.c_char_p
@@ -479,3 +496,68 @@ class LoopCloser:
         out = np.zeros(max(n.value, 1), A.PT_DTYPE)
         self._check(self.hl.dll.lvh_loop_cloud(self._g, int(what), A._ptr(out), len(out), C.byref(n)), "lvh_loop_cloud")
         return out[:n.value].copy()
+
+
+class KeyFrameMatcher:
+    """lvi_host::KeyFrameDescriber (host/lvi_kf_host.hpp) with the host halves of its keyframes: the online KeyFrame
+    constructor (keyframe.cpp:14-73) and findConnection up to PnPRANSAC (:179-200).  HIP host library only."""
+
+    def __init__(self, hostlib, pattern, device=0, max_width=1024, max_height=576, max_keypoints=8192, max_window=1024, max_keyframes=16):
+        if not hostlib.has_kf:
+            raise RuntimeError("this host library has no keyframe describer (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        self.max_window = int(max_window)
+        pat = [np.ascontiguousarray(p, np.int32).reshape(-1) for p in pattern]
+        if len(pat) != 4 or any(len(p) != 256 for p in pat):
+            raise ValueError("the BRIEF pattern is four arrays of 256 ints")
+        self._m = hostlib.dll.lvh_kf_create(int(device), int(max_width), int(max_height), int(max_keypoints), self.max_window, int(max_keyframes),
+                                            *[p.ctypes.data_as(C.POINTER(C.c_int32)) for p in pat])
+        if not self._m:
+            raise A.LviError(-1, "lvh_kf_create", hostlib.dll.lvh_kf_last_error().decode(errors="replace"))
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_kf_last_error().decode(errors="replace"))
+        return code
+
+    def close(self):
+        if self._m:
+            self.hl.dll.lvh_kf_destroy(self._m)
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, slot, img, point_3d, point_2d_uv, point_2d_norm, point_id, cam=None):
+        """the online KeyFrame constructor into `slot` -> dict(n_keypoints_found, n_keypoints_stored)"""
+        from .kf import mei_params
+        img = np.ascontiguousarray(img, np.uint8)
+        p3 = np.ascontiguousarray(point_3d, np.float32).reshape(-1, 3)
+        uv = np.ascontiguousarray(point_2d_uv, np.float32).reshape(-1, 2)
+        nm = np.ascontiguousarray(point_2d_norm, np.float32).reshape(-1, 2)
+        ids = np.ascontiguousarray(point_id, np.float64).reshape(-1)
+        if not len(p3) == len(uv) == len(nm) == len(ids):
+            raise ValueError("the window vectors differ in length")
+        c = mei_params(cam)
+        info = (C.c_int32 * 2)()
+        self._check(self.hl.dll.lvh_kf_add(self._m, int(slot), A._ptr(img), img.shape[1], img.shape[0], img.shape[1], len(uv), A._ptr(p3), A._ptr(uv),
+                                           A._ptr(nm), A._ptr(ids), C.byref(c) if c is not None else None, info), "lvh_kf_add")
+        return dict(n_keypoints_found=info[0], n_keypoints_stored=info[1])
+
+    def remove(self, slot):
+        self._check(self.hl.dll.lvh_kf_remove(self._m, int(slot)), "lvh_kf_remove")
+
+    def findConnectionFront(self, cur_slot, old_slot):
+        """(passes the > MIN_LOOP_NUM gate, dict of the six compacted vectors PnPRANSAC would receive + searchByBRIEFDes's status)"""
+        n = C.c_int32(0)
+        ok = bool(self._check(self.hl.dll.lvh_kf_connect(self._m, int(cur_slot), int(old_slot), C.byref(n)), "lvh_kf_connect"))
+        k = max(n.value, 1)
+        v2 = [np.zeros((k, 2), np.float32) for _ in range(4)]
+        p3 = np.zeros((k, 3), np.float32); ids = np.zeros(k, np.float64); st = np.zeros(self.max_window, np.uint8)
+        self._check(self.hl.dll.lvh_kf_connection(self._m, *[A._ptr(a) for a in v2], A._ptr(p3), A._ptr(ids), A._ptr(st), len(st)), "lvh_kf_connection")
+        m = n.value
+        return ok, dict(matched_2d_cur=v2[0][:m].copy(), matched_2d_old=v2[1][:m].copy(), matched_2d_cur_norm=v2[2][:m].copy(),
+                        matched_2d_old_norm=v2[3][:m].copy(), matched_3d=p3[:m].copy(), matched_id=ids[:m].copy(), status=st)
