@@ -1013,6 +1013,7 @@ void lidar_allocate(LidarDev& d)
     { const char* e = getenv("LVI_KNN_NO_SKIP"); d.knn_skip = !(e && e[0] == '1'); }
     { const char* e = getenv("LVI_KNN_SLACK"); if (e) d.knn_slack = std::max(0.f, (float)atof(e)); }
     { const char* e = getenv("LVI_VB_BINS"); if (e) { int a = 0, b = 0; if (sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b > 0 && b <= VB_NB) { d.voxMap.bin_pts = a; d.voxMap.bin_max = b; } } }
+    { const char* e = getenv("LVI_VB_SLOT_ORDER"); d.voxMap.slot_major = !(e && e[0] == '0'); }
     if (d.P.batch_scans > 1) { d.icp_g1 = 4; d.icp_wide_from = 1; }      // (256 features per workgroup from iteration 1 on: 8 040 vs 7 930 scans/s; a single scan: 640 vs 612 us)
     // (lanes per feature after iteration 0: round 2's kernel preferred 2 in throughput mode; with the records in global memory both forms
     //  run four wavefronts per SIMD and 4 lanes win: 7 177 vs 7 090 scans/s)

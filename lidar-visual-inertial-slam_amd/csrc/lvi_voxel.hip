@@ -45,7 +45,22 @@ struct VoxArgs {
     int plan_spec;                                     // this run takes bbox and per-bin counts in one pass (vb_plan); vox_setup validates the counts
     unsigned* wprefix;                                 // [nseg][VB_WG][VB_NB] points of bin b in the ranges of workgroups < w (deterministic partition)
     int ch;                                            // points per accumulate chunk of this launch sequence: VB_CH, or a multiple of it when many slots fill the chip anyway (<= 32768: chunk-table counts are 16 bits)
+    int sx;                                            // slots of this launch folded into blockIdx.x (vb_block); 1: blockIdx.z is the slot
 };
+
+// Block decode of the passes over the raw local map.  Every slot of a batch reads the SAME map, and with the slot in blockIdx.z
+// slot z + 1 streams a line a whole 78 MB sweep after slot z did: long gone from the 4 MB L2 of the XCD, so S slots fetch the
+// map S times through the fabric.  Slot-major order instead: the S workgroups that own range w sit VB_XCD apart in dispatch
+// order — consecutive on ONE XCD — become resident together and stream the same tiles through that XCD's L2; one misses, the
+// others hit.  An affinity for speed only: every (range, segment, slot) is decoded exactly once for any placement, and no
+// workgroup waits for another.  nw = workgroups per slot; S = 1 is the identity (slot = blockIdx.z, w = blockIdx.x).
+static_assert(VB_WG % VB_XCD == 0, "the slot-major decode walks the ranges in groups of VB_XCD");
+struct VbBlock { int slot, w, nw; };
+__device__ __forceinline__ VbBlock vb_block(int S)
+{
+    const int L = blockIdx.x, group = L / (VB_XCD * S), r = L % (VB_XCD * S);
+    return VbBlock{(int)blockIdx.z + r / VB_XCD, group * VB_XCD + r % VB_XCD, (int)gridDim.x / S};
+}
 
 __device__ __forceinline__ int seg_len(const VoxArgs& a, int s)
 {
@@ -55,17 +70,18 @@ __device__ __forceinline__ int seg_len(const VoxArgs& a, int s)
 
 __global__ __launch_bounds__(256) void vox_minmax_kernel(Batch<VoxArgs> B_)
 {
-    const VoxArgs& a = B_.a[blockIdx.z];
+    const VbBlock k = vb_block(B_.a[0].sx);
+    const VoxArgs& a = B_.a[k.slot];
     const int s = blockIdx.y;
     const int n = seg_len(a, s);
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.d_n[s] = n;          // read by every later kernel of the batch
+    if (k.w == 0 && threadIdx.x == 0) a.d_n[s] = n;          // read by every later kernel of the batch
     const lvi_pt* __restrict__ in = a.st[s].in + a.dyn[s].in_off;
     const uint8_t* __restrict__ mask = a.st[s].mask ? a.st[s].mask + a.dyn[s].in_off : nullptr;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     float imn = INFINITY, imx = -INFINITY;
     int cnt = 0;
-    const int stride = gridDim.x * 256;
-    for (int i0 = blockIdx.x * 256 + threadIdx.x; i0 < n; i0 += 4 * stride) {
+    const int stride = k.nw * 256;
+    for (int i0 = k.w * 256 + threadIdx.x; i0 < n; i0 += 4 * stride) {
         lvi_pt p[4]; bool ok[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {               // four independent loads in flight per lane
@@ -105,7 +121,7 @@ __global__ __launch_bounds__(256) void vox_minmax_kernel(Batch<VoxArgs> B_)
 #pragma unroll
             for (int d = 0; d < 4; d++) { lo[d] = fminf(lo[d], smn[w][d]); hi[d] = fmaxf(hi[d], smx[w][d]); }
         }
-        float* rec = a.mmPartial + ((size_t)s * a.nblk_mm + blockIdx.x) * 12;
+        float* rec = a.mmPartial + ((size_t)s * a.nblk_mm + k.w) * 12;
         rec[0] = lo[0]; rec[1] = lo[1]; rec[2] = lo[2]; rec[3] = hi[0]; rec[4] = hi[1]; rec[5] = hi[2];
         rec[6] = __int_as_float(c); rec[7] = lo[3]; rec[8] = hi[3];
     }
@@ -585,11 +601,12 @@ __device__ __forceinline__ WaveRun wave_runs(unsigned v)
 
 __global__ __launch_bounds__(256) void vb_hist_kernel(Batch<VoxArgs> B_)
 {
-    const VoxArgs& a = B_.a[blockIdx.z];
+    const VbBlock k = vb_block(B_.a[0].sx);
+    const VoxArgs& a = B_.a[k.slot];
     const int s = blockIdx.y;
     const int n = a.d_n[s];
     const VoxGrid& g = a.grid[s];
-    if ((int)blockIdx.x * VB_TILE >= n || g.nbins == 0) return;
+    if (k.w * VB_TILE >= n || g.nbins == 0) return;
     __shared__ unsigned cnt[VB_NB];
     const int nbins = g.nbins, sh = g.bin_shift;
     for (int b = threadIdx.x; b < nbins; b += 256) cnt[b] = 0u;
@@ -599,7 +616,7 @@ __global__ __launch_bounds__(256) void vb_hist_kernel(Batch<VoxArgs> B_)
     const uint8_t* __restrict__ mask = a.st[s].mask ? a.st[s].mask + off : nullptr;
     // grid-stride over the tiles: one LDS histogram and one flush per workgroup, however many tiles it takes
     const VoxKeyK kk = vox_keyk_of(g);
-    for (int base = blockIdx.x * VB_TILE; base < n; base += gridDim.x * VB_TILE) {
+    for (int base = k.w * VB_TILE; base < n; base += k.nw * VB_TILE) {
         for (int u0 = 0; u0 < VB_TILE / 256; u0 += 8) {                  // eight unconditional loads in flight (clamped index, masked lanes)
             lvi_pt p[8]; bool keep[8];
             vox_load_pts<8, 256>(in, mask, base + u0 * 256 + threadIdx.x, n, p, keep);
@@ -629,8 +646,9 @@ __device__ __forceinline__ int vb_wg_points(int n) { const int k = (n + VB_STILE
 // (g.plan_ok); a point outside that grid, or a changed grid, sends the counts through vb_hist_w once more.
 __global__ __launch_bounds__(256) void vb_plan_kernel(Batch<VoxArgs> B_)
 {
-    const VoxArgs& a = B_.a[blockIdx.z];
-    const int s = blockIdx.y, w = blockIdx.x;
+    const VbBlock k = vb_block(B_.a[0].sx);
+    const VoxArgs& a = B_.a[k.slot];
+    const int s = blockIdx.y, w = k.w;
     const int n = seg_len(a, s);
     if (w == 0 && threadIdx.x == 0) { a.d_n[s] = n; }
     const VoxGrid& g = a.grid[s];
@@ -711,8 +729,9 @@ __global__ __launch_bounds__(256) void vb_plan_kernel(Batch<VoxArgs> B_)
 
 __global__ __launch_bounds__(256) void vb_hist_w_kernel(Batch<VoxArgs> B_)
 {
-    const VoxArgs& a = B_.a[blockIdx.z];
-    const int s = blockIdx.y, w = blockIdx.x;
+    const VbBlock k = vb_block(B_.a[0].sx);
+    const VoxArgs& a = B_.a[k.slot];
+    const int s = blockIdx.y, w = k.w;
     const int n = a.d_n[s];
     const VoxGrid& g = a.grid[s];
     if (a.plan_spec && g.plan_ok) return;           // vb_plan's counts stand
@@ -781,8 +800,9 @@ __global__ __launch_bounds__(256) void vb_colscan_kernel(Batch<VoxArgs> B_)
 
 __global__ __launch_bounds__(256) void vb_scatter_det_kernel(Batch<VoxArgs> B_)
 {
-    const VoxArgs& a = B_.a[blockIdx.z];
-    const int s = blockIdx.y, w = blockIdx.x;
+    const VbBlock k = vb_block(B_.a[0].sx);
+    const VoxArgs& a = B_.a[k.slot];
+    const int s = blockIdx.y, w = k.w;
     const int n = a.d_n[s];
     const VoxGrid& g = a.grid[s];
     const int K = vb_wg_points(n);
@@ -1376,7 +1396,7 @@ static VoxArgs make_args(const VoxelPlan& p)
                    p.d_binCount, p.d_binStart, p.d_cursor, p.d_binVox, p.d_binOut, p.d_bucketed, p.d_staging, p.d_stagingKC, p.h_ncells,
                    p.d_chunkStart, p.d_multiStart, p.d_chunkBin, p.max_chunks, p.d_lightBin, p.d_multiOwner, p.d_chunkTabV, p.d_chunkTabC, p.max_multi,
                    {p.n_host[0], p.n_host[1], p.n_host[2], p.n_host[3]}, (p.use_n_host && p.nseg <= 4) ? 1 : 0,
-                   {p.n_dev[0], p.n_dev[1], p.n_dev[2], p.n_dev[3]}, p.bin_pts, p.bin_max, ((p.plan_per_run && p.d_wprefix) || (p.bbox_cached && p.hist_cached)) ? p.d_binCountCached : nullptr, p.d_binCountCached, p.d_planMiss, (p.plan_per_run && p.d_wprefix) ? 1 : 0, p.d_wprefix, VB_CH};
+                   {p.n_dev[0], p.n_dev[1], p.n_dev[2], p.n_dev[3]}, p.bin_pts, p.bin_max, ((p.plan_per_run && p.d_wprefix) || (p.bbox_cached && p.hist_cached)) ? p.d_binCountCached : nullptr, p.d_binCountCached, p.d_planMiss, (p.plan_per_run && p.d_wprefix) ? 1 : 0, p.d_wprefix, VB_CH, 1};
 }
 
 void VoxelPlan::set_static(const Ctx& ctx, const VoxSegStatic* host_segs)
@@ -1701,7 +1721,8 @@ void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan& p, const char* tag,
     voxel_downsample_batch(ctx, &one, 1, tag, n_hint);
 }
 
-// S plans of identical shape (the same plan of S batch slots), one launch sequence: blockIdx.z = slot
+// S plans of identical shape (the same plan of S batch slots), one launch sequence: blockIdx.z = slot; the passes over the raw
+// map, which every slot reads from the same addresses, fold the slot into blockIdx.x instead (vb_block)
 void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, int S, const char* tag, double n_hint)
 {
     const VoxelPlan& p = *plans[0];
@@ -1724,6 +1745,15 @@ void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, int S
     for (int z = 0; z < S; z++) { B.a[z] = make_args(*plans[z]); B.a[z].ch = ch; plans[z]->last_mode = mode; }
     for (int z = S; z < MAX_BATCH; z++) B.a[z] = B.a[0];
     const VoxArgs& a = B.a[0];
+    // grid of a pass over the raw map (vb_block): the slots folded into x when the plans ask for it and the decode's groups fit
+    bool raw_map = S > 1;
+    for (int z = 0; z < S; z++) raw_map = raw_map && plans[z]->slot_major && plans[z]->use_n_host;
+    auto slot_grid = [&](int nx) {
+        const int sx = raw_map && nx % VB_XCD == 0 ? S : 1;
+        for (int z = 0; z < MAX_BATCH; z++) B.a[z].sx = sx;
+        return dim3(nx * sx, p.nseg, S / sx);
+    };
+    dim3 gs;                                            // (set in a statement of its own: B must hold sx before the launch copies it)
     char nm[16][48];
     const char* base[16] = {"vox_minmax", "vox_setup", "vox_keys", "vox_heads_count", "vox_heads_scan", "vox_heads_assign", "vox_centroid",
                             "vb_hist", "vb_scan", "vb_scatter", "vb_accum", "vb_outscan", "vb_copy", "vb_merge", "vb_light", ""};
@@ -1734,13 +1764,15 @@ void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, int S
     for (int z = 0; z < S; z++) { cached = cached && plans[z]->bbox_cached; per_run = per_run && B.a[z].plan_spec != 0; }
     if (per_run) {
         // reference-faithful raw map: bbox + per-bin counts inside this run, one pass (vb_plan), validated by vox_setup
-        LVI_LAUNCH(ctx, "vb_plan/map", 16.0 * n_hint, hipLaunchKernelGGL(vb_plan_kernel, dim3(VB_WG, p.nseg, S), dim3(256), 0, ctx.stream, B));
+        gs = slot_grid(VB_WG);
+        LVI_LAUNCH(ctx, "vb_plan/map", 16.0 * n_hint, hipLaunchKernelGGL(vb_plan_kernel, gs, dim3(256), 0, ctx.stream, B));
         LVI_LAUNCH(ctx, nm[1], 0, hipLaunchKernelGGL(vox_setup_kernel, dim3(p.nseg, 1, S), dim3(64), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, "vb_hist_w/map", 0, hipLaunchKernelGGL(vb_hist_w_kernel, dim3(VB_WG, p.nseg, S), dim3(256), 0, ctx.stream, B));
+        LVI_LAUNCH(ctx, "vb_hist_w/map", 0, hipLaunchKernelGGL(vb_hist_w_kernel, gs, dim3(256), 0, ctx.stream, B));
         LVI_LAUNCH(ctx, "vb_colscan/map", 0, hipLaunchKernelGGL(vb_colscan_kernel, dim3(VB_NB / 16, p.nseg, S), dim3(256), 0, ctx.stream, B));
     } else {
         for (int z = 0; z < S; z++) B.a[z].plan_spec = 0;
-        if (!cached) LVI_LAUNCH(ctx, nm[0], 16.0 * n_hint, hipLaunchKernelGGL(vox_minmax_kernel, dim3(p.nblk_mm, p.nseg, S), dim3(256), 0, ctx.stream, B));
+        gs = slot_grid(p.nblk_mm);
+        if (!cached) LVI_LAUNCH(ctx, nm[0], 16.0 * n_hint, hipLaunchKernelGGL(vox_minmax_kernel, gs, dim3(256), 0, ctx.stream, B));
         LVI_LAUNCH(ctx, nm[1], 0, hipLaunchKernelGGL(vox_setup_kernel, dim3(p.nseg, 1, S), dim3(64), 0, ctx.stream, B));
     }
     if (mode == VOX_BINNED) {
@@ -1751,10 +1783,12 @@ void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, int S
         for (int z = 0; z < S; z++) hist_cached = hist_cached && B.a[z].binCountCached != nullptr;
         if (!hist_cached) {
             for (int z = 0; z < S; z++) B.a[z].binCountCached = nullptr;                  // all slots the same way
-            LVI_LAUNCH(ctx, nm[7], 16.0 * n_hint, hipLaunchKernelGGL(vb_hist_kernel, gh2, dim3(256), 0, ctx.stream, B));
+            gs = slot_grid(gh2.x);
+            LVI_LAUNCH(ctx, nm[7], 16.0 * n_hint, hipLaunchKernelGGL(vb_hist_kernel, gs, dim3(256), 0, ctx.stream, B));
         }
         LVI_LAUNCH(ctx, nm[8], 0, hipLaunchKernelGGL(vb_scan_kernel, dim3(p.nseg, 1, S), dim3(256), 0, ctx.stream, B));
-        if (hist_cached) LVI_LAUNCH(ctx, nm[9], 32.0 * n_hint, hipLaunchKernelGGL(vb_scatter_det_kernel, dim3(VB_WG, p.nseg, S), dim3(256), 0, ctx.stream, B));
+        gs = slot_grid(VB_WG);
+        if (hist_cached) LVI_LAUNCH(ctx, nm[9], 32.0 * n_hint, hipLaunchKernelGGL(vb_scatter_det_kernel, gs, dim3(256), 0, ctx.stream, B));
         else LVI_LAUNCH(ctx, nm[9], 32.0 * n_hint, hipLaunchKernelGGL(vb_scatter_kernel, gt, dim3(256), 0, ctx.stream, B));
         // grid-stride over the chunks: at most ceil(n / VB_CH) + bins of them exist; a small plan (ring / scan grids: 64 bins) gets
         // a small grid — every workgroup of this kernel owns 40 KB of LDS, and thousands of idle ones cost 40 us of dispatch

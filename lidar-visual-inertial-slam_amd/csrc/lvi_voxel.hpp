@@ -51,6 +51,7 @@ constexpr int VB_TILE = 4096;    // binned path: points per tile of the histogra
 constexpr int VB_STILE = 4096;   // binned path: points per workgroup of the scatter kernel (2048: 62 us instead of 56 us for the 4.9 M-point map)
 constexpr int VB_PAD = 1;        // binned path: stride of the global bin counters / cursors (one per 64-B line, VB_PAD = 16, measured SLOWER: hist 36 vs 29 us, scatter 67 vs 56 us)
 constexpr int VB_WG = 512;       // deterministic partition: workgroups (= contiguous point ranges) per segment (256 / 512 / 1024: scatter 62 / 44 / 46 us on the 4.87 M-point map)
+constexpr int VB_XCD = 8;        // workgroups VB_XCD apart in dispatch order run on the same XCD (slot-major order of the raw-map passes, vb_block)
 constexpr int VB_WROW = VB_NB + 64;   // words per row of the per-(workgroup, bin) count table: NOT a power of two — vb_colscan walks columns, and rows 16 KB apart meet in the same memory channels
 constexpr int VB_CH = 8192;       // binned path: points per accumulate workgroup (chunk of a bin); with 32 scans in flight 4096 / 8192 / 16384: 7 050 / 7 400 / 7 460 scans/s (one rebuild alone: accum 33 / ~40 / 50 us)
 constexpr int VB_LIGHT = 256;     // binned path: a bin of at most this many points is accumulated by ONE wavefront (vb_light_kernel)
@@ -105,6 +106,7 @@ struct VoxelPlan {
                                               // pass for both, the histogram under the previous run's grid geometry, re-taken by vb_hist_w when the geometry moved)
     int* d_planMiss = nullptr;                // [nseg] a point fell outside the previous geometry (vb_plan)
     bool bbox_cached = false;                 // d_mmPartial holds the bbox partials of the CURRENT input (voxel_bbox_pass ran after the input was written)
+    bool slot_major = true;                   // batch launches of the raw-map passes fold the slot into blockIdx.x (vb_block; LVI_VB_SLOT_ORDER=0: blockIdx.z = slot)
 
     template <class AR> void allocate(AR& ar, int nseg_, int seg_cap_, bool concat)
     {
@@ -202,7 +204,8 @@ void incmap_emit(const Ctx& ctx, const IncMap& m, int n_active, const float leaf
 // 16.8 M cells (four sweeps per bin), SORTED for sparser ones.  d_dyn must have been written (on the same
 // stream) by the producer.  n_hint: nominal total input points, for byte accounting only.
 void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan& plan, const char* tag, double n_hint);
-// the same plan of S batch slots (identical shapes) in ONE launch sequence, blockIdx.z = slot; n_hint = points of all slots
+// the same plan of S batch slots (identical shapes) in ONE launch sequence, blockIdx.z = slot (raw-map passes: VoxelPlan::slot_major);
+// n_hint = points of all slots
 void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, int S, const char* tag, double n_hint);
 // the bbox partial records of the plan's current input, as a pass of its own (sets nothing on the plan: the caller owns
 // bbox_cached and clears it whenever the input changes)
