@@ -522,6 +522,14 @@ def test_scan_to_map_pose_parity(pkg, pair, scene):
     assert xo["status"] == xg["status"] == 0 and xo["iters"] == xg["iters"] and xo["degenerate"] == xg["degenerate"]
     np.testing.assert_array_equal(np.array(xo["n_sel"]), np.array(xg["n_sel"]))
     assert np.abs(xo["pose"] - xg["pose"]).max() < 2e-5, np.abs(xo["pose"] - xg["pose"])
+    # … and the 27 sums of EVERY recorded iteration (each one's solve is pinned to float64 in tests/test_gpu_step.py)
+    jo, jg = o.debug_get(A.DBG_ICP_JTJ, np.float32).reshape(-1, 27), g.debug_get(A.DBG_ICP_JTJ, np.float32).reshape(-1, 27)
+    assert jo.shape == jg.shape == (xo["iters"], 27)
+    to, tg = o.debug_get(A.DBG_ICP_POSE_TRACE, np.float32).reshape(-1, 6), g.debug_get(A.DBG_ICP_POSE_TRACE, np.float32).reshape(-1, 6)
+    for it in range(len(jo)):
+        print(f"identical-input leg, iteration {it}: |d pose| {np.abs(to[it] - tg[it]).max():.2e}  "
+              f"max |d sums| / (1e-2 + 2e-3 |sums|) = {(np.abs(jo[it] - jg[it]) / (1e-2 + 2e-3 * np.abs(jg[it]))).max():.3e}")
+        np.testing.assert_allclose(jo[it], jg[it], rtol=2e-3, atol=1e-2, err_msg=f"iteration {it}")
     for h in (o, g):
         h.map_set(scene["map_corner"], scene["map_surf"])
     # IMU hint path (transformUpdate slerp) and the one-call seam
