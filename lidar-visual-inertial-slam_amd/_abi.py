@@ -193,10 +193,18 @@ class Library:
                 "there is no CPU fallback for the HIP path")
         self.path = path
         self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(self.dll, name)          # AttributeError = missing export
-            fn.restype = res
-            fn.argtypes = args
+        self._bound = set()
+        self.bind(SIGNATURES)
+
+    def bind(self, table):
+        """set the signatures of a name -> (restype, argtypes) table on the loaded library, once per table"""
+        if id(table) not in self._bound:
+            for name, (res, args) in table.items():
+                fn = getattr(self.dll, name)      # AttributeError = missing export
+                fn.restype = res
+                fn.argtypes = args
+            self._bound.add(id(table))
+        return self
 
     @property
     def backend(self):

@@ -47,17 +47,9 @@ Profiler::~Profiler()
     for (auto e : pool) (void)hipEventDestroy(e);
 }
 
-// defined in lvi_voxel.hip
-void voxel_debug_fetch(const Ctx& ctx, const VoxelPlan& p, int n_in, std::vector<int32_t>& keys, std::vector<int32_t>& cells, std::vector<int32_t>& counts);
-
 }  // namespace lvi
 
 using namespace lvi;
-
-struct lvi_lidar;
-namespace lvi {
-LidarDev& lidar_slot0(lvi_lidar* h);                // the keyframe store's slot (lvi_gmap.hip)
-}
 
 struct lvi_lidar {
     LidarDev d;                                     // slot 0: owns the streams, the profiler, the keyframe store and the raw map
@@ -81,23 +73,6 @@ LidarDev& lvi::lidar_slot0(lvi_lidar* h) { return h->d; }
 namespace {
 
 std::mutex g_share_mu;                              // the sharer lists of lvi_map_share (handles may live on different host threads)
-
-int32_t fail(int32_t code, const std::string& msg) { set_error(msg); return code; }
-
-template <class F>
-int32_t guarded(lvi_lidar* h, F&& f)
-{
-    try {
-        if (h) LVI_HIP(hipSetDevice(h->d.device));
-        return f();
-    } catch (const HipError& e) {
-        char buf[512];
-        snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.e), e.file, e.line);
-        return fail(LVI_ERR_HIP, buf);
-    } catch (const std::exception& e) {
-        return fail(LVI_ERR_HIP, e.what());
-    }
-}
 
 void sync(LidarDev& d)
 {
@@ -221,7 +196,7 @@ int32_t lvi_lidar_create(const lvi_lidar_params* p, int32_t device, lvi_lidar** 
     h->d.P = *p; h->d.device = device;
     const int S = std::max(p->batch_scans, 1);
     if (S > 1 && !getenv("LVI_BATCH_TWO_STREAMS")) h->d.P.map_on_main_stream = 1;      // a batch fills the chip by itself; one stream keeps every slot's work in one order
-    int32_t st = guarded(h, [&]() -> int32_t {
+    int32_t st = guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
         LVI_HIP(hipStreamCreateWithFlags(&d.ctx.stream, hipStreamNonBlocking));
         LVI_HIP(hipStreamCreateWithFlags(&d.ctx2.stream, hipStreamNonBlocking));
@@ -245,7 +220,7 @@ int32_t lvi_lidar_create(const lvi_lidar_params* p, int32_t device, lvi_lidar** 
 
 static void release_slot(LidarDev& d)
 {
-    d.voxRing.release(); d.voxScan.release(); d.voxMap.release(); d.voxGen.release();
+    d.voxRing.release(); d.voxScan.release(); d.voxMap.release(); d.gen.release();
     d.arena.release();
     if (d.h_icp) (void)hipHostFree(d.h_icp);
     if (d.h_gn_feat) (void)hipHostFree(d.h_gn_feat);
@@ -298,14 +273,14 @@ void lvi_lidar_destroy(lvi_lidar* h)
 int32_t lvi_lidar_sync(lvi_lidar* h)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
-    return guarded(h, [&]() -> int32_t { sync(h->cur()); return LVI_OK; });
+    return guarded(h->d.device, [&]() -> int32_t { sync(h->cur()); return LVI_OK; });
 }
 
 int32_t lvi_lidar_mark(lvi_lidar* h, int32_t slot)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
     if (slot < 0 || slot >= LVI_LIDAR_MARKS) return fail(LVI_ERR_INVALID_ARG, "mark slot out of range");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
         if (!d.evMark[slot]) LVI_HIP(hipEventCreateWithFlags(&d.evMark[slot], hipEventDisableTiming));
         join_map(d);                                       // a map build still on its own stream is part of "everything enqueued so far"
@@ -318,7 +293,7 @@ int32_t lvi_lidar_wait_mark(lvi_lidar* h, int32_t slot)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
     if (slot < 0 || slot >= LVI_LIDAR_MARKS) return fail(LVI_ERR_INVALID_ARG, "mark slot out of range");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         if (h->d.evMark[slot]) LVI_HIP(hipEventSynchronize(h->d.evMark[slot]));
         return LVI_OK;
     });
@@ -329,7 +304,7 @@ int32_t lvi_scan_upload(lvi_lidar* h, const lvi_livox_pt* pts, int32_t n_raw)
 {
     if (!h || (n_raw > 0 && !pts)) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (n_raw > h->cur().raw_cap) return fail(LVI_ERR_CAPACITY, "n_raw exceeds max_raw_points");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         d.raw_bound = nullptr;                      // (a buffer bound by lvi_scan_batch_bind_device is no longer this slot's scan)
         d.n_raw = n_raw > 0 ? n_raw - 1 : 0;        // moveFromCustomMsg: i < point_num-1 (imageProjection.cpp:249)
@@ -349,7 +324,7 @@ int32_t lvi_scan_upload_device(lvi_lidar* h, const void* d_pts, int32_t n_raw)
 {
     if (!h || (n_raw > 0 && !d_pts)) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (n_raw > h->cur().raw_cap) return fail(LVI_ERR_CAPACITY, "n_raw exceeds max_raw_points");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         d.raw_bound = nullptr;
         d.n_raw = n_raw > 0 ? n_raw - 1 : 0;
@@ -403,7 +378,7 @@ int32_t lvi_map_share(lvi_lidar* h, lvi_lidar* owner)
     if (owner->d.mapCornerRaw != owner->d.mapCornerOwn) return fail(LVI_ERR_STATE, "the owner itself shares a map");
     if (h->shared_by > 0) return fail(LVI_ERR_STATE, "other handles read this handle's map: it cannot share another one's");
     if (owner->d.n_map_corner > h->d.map_cap || owner->d.n_map_surf > h->d.map_cap) return fail(LVI_ERR_CAPACITY, "map exceeds max_map_points");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         join_map(owner->d); sync(owner->d);                         // the owner's upload / assembly has landed
         join_map(h->d); sync(h->d);
         leave_owner(h);
@@ -422,7 +397,7 @@ int32_t lvi_map_upload_device(lvi_lidar* h, const void* c, int32_t nc, const voi
     if (!h || nc < 0 || ns < 0 || (nc > 0 && !c) || (ns > 0 && !s)) return fail(LVI_ERR_INVALID_ARG, "bad map arguments");
     if (nc > h->d.map_cap || ns > h->d.map_cap) return fail(LVI_ERR_CAPACITY, "map exceeds max_map_points");
     if (h->shared_by > 0) return fail(LVI_ERR_STATE, "other handles read this handle's map (lvi_map_share)");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
         unshare_map(h);
         drop_graph(h);
@@ -436,24 +411,24 @@ int32_t lvi_map_upload_device(lvi_lidar* h, const void* c, int32_t nc, const voi
 int32_t lvi_scan_organize(lvi_lidar* h)
 {
     if (!h || !h->cur().have_raw) return fail(LVI_ERR_STATE, "no scan uploaded");
-    return guarded(h, [&]() -> int32_t { stage_organize(h->cur()); h->cur().have_org = true; h->cur().have_feat = h->cur().have_ds = false; return LVI_OK; });
+    return guarded(h->d.device, [&]() -> int32_t { stage_organize(h->cur()); h->cur().have_org = true; h->cur().have_feat = h->cur().have_ds = false; return LVI_OK; });
 }
 int32_t lvi_scan_extract(lvi_lidar* h)
 {
     if (!h || !h->cur().have_org) return fail(LVI_ERR_STATE, "scan not organised");
-    return guarded(h, [&]() -> int32_t { stage_extract(h->cur()); h->cur().have_feat = true; h->cur().have_ds = false; return LVI_OK; });
+    return guarded(h->d.device, [&]() -> int32_t { stage_extract(h->cur()); h->cur().have_feat = true; h->cur().have_ds = false; return LVI_OK; });
 }
 int32_t lvi_scan_downsample(lvi_lidar* h)
 {
     if (!h || !h->cur().have_feat) return fail(LVI_ERR_STATE, "features not extracted");
-    return guarded(h, [&]() -> int32_t { stage_downsample(h->cur()); h->cur().have_ds = true; return LVI_OK; });
+    return guarded(h->d.device, [&]() -> int32_t { stage_downsample(h->cur()); h->cur().have_ds = true; return LVI_OK; });
 }
 int32_t lvi_map_upload(lvi_lidar* h, const lvi_pt* c, int32_t nc, const lvi_pt* s, int32_t ns)
 {
     if (!h || nc < 0 || ns < 0 || (nc > 0 && !c) || (ns > 0 && !s)) return fail(LVI_ERR_INVALID_ARG, "bad map arguments");
     if (nc > h->d.map_cap || ns > h->d.map_cap) return fail(LVI_ERR_CAPACITY, "map exceeds max_map_points");
     if (h->shared_by > 0) return fail(LVI_ERR_STATE, "other handles read this handle's map (lvi_map_share)");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
         unshare_map(h);
         drop_graph(h);
@@ -467,21 +442,21 @@ int32_t lvi_map_build(lvi_lidar* h)
 {
     if (!h || !h->d.have_map_raw) return fail(LVI_ERR_STATE, "no map uploaded");
     // a batch handle re-voxelises and re-indexes the (shared) raw map for every slot, in one launch sequence
-    return guarded(h, [&]() -> int32_t { stage_map_build(Slots{h->slots.data(), (int)h->slots.size()}); return LVI_OK; });
+    return guarded(h->d.device, [&]() -> int32_t { stage_map_build(Slots{h->slots.data(), (int)h->slots.size()}); return LVI_OK; });
 }
 
 int32_t lvi_scan_match_async(lvi_lidar* h, const float pose_init[6], void* d_record)
 {
     if (!h || !pose_init) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!h->cur().have_ds) return fail(LVI_ERR_STATE, "scan not downsampled");
-    return guarded(h, [&]() -> int32_t { set_pose_init(h->cur(), pose_init); stage_scan_match_enqueue(h->cur(), nullptr, d_record); h->have_icp_host = false; return LVI_OK; });
+    return guarded(h->d.device, [&]() -> int32_t { set_pose_init(h->cur(), pose_init); stage_scan_match_enqueue(h->cur(), nullptr, d_record); h->have_icp_host = false; return LVI_OK; });
 }
 
 int32_t lvi_scan_match(lvi_lidar* h, const lvi_imu_hint* imu, float pose[6], lvi_icp_result* out)
 {
     if (!h || !pose || !out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!h->cur().have_ds) return fail(LVI_ERR_STATE, "scan not downsampled");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         set_pose_init(d, pose);
         int nq[3] = {0, 0, 0}, dw[2] = {0, 0};
@@ -517,7 +492,7 @@ int32_t lvi_scan_replay_enqueue(lvi_lidar* h, const void* d_pts, int32_t n_raw, 
     if (n_raw > h->cur().raw_cap) return fail(LVI_ERR_CAPACITY, "n_raw exceeds max_raw_points");
     if (rebuild_map && !h->d.have_map_raw) return fail(LVI_ERR_STATE, "no map uploaded");
     if (h->sel != 0) return fail(LVI_ERR_STATE, "lvi_scan_replay_enqueue runs on slot 0; batches go through lvi_scan_batch_run");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         join_map(d);
         // per-call inputs go in eagerly; the captured graph only reads fixed buffers of the handle
@@ -598,7 +573,7 @@ int32_t lvi_scan_batch_upload(lvi_lidar* h, int32_t n_scans, const lvi_livox_pt*
         if (n_raw[z] < 0 || (n_raw[z] > 0 && !pts[z])) return fail(LVI_ERR_INVALID_ARG, "bad scan");
         if (n_raw[z] > h->d.raw_cap) return fail(LVI_ERR_CAPACITY, "n_raw exceeds max_raw_points");
     }
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         for (int z = 0; z < n_scans; z++) {
             LidarDev& q = *h->slots[z];
             q.raw_bound = nullptr;
@@ -619,7 +594,7 @@ int32_t lvi_scan_batch_run(lvi_lidar* h, int32_t n_scans, const float* pose_init
     if (!pose_init) return fail(LVI_ERR_INVALID_ARG, "null argument");
     for (int z = 0; z < n_scans; z++) if (!h->slots[z]->have_raw) return fail(LVI_ERR_STATE, "no scan bound / uploaded for a slot");
     if (rebuild_map && !h->d.have_map_raw) return fail(LVI_ERR_STATE, "no map uploaded");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         const Slots sl{h->slots.data(), n_scans};
         set_pose_init(sl, pose_init, true);
         if (rebuild_map) stage_map_build(sl);
@@ -636,7 +611,7 @@ int32_t lvi_scan_batch_get_records(lvi_lidar* h, int32_t n_scans, lvi_pose_recor
 {
     int32_t st = batch_check(h, n_scans); if (st) return st;
     if (!out) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         for (int z = 0; z < n_scans; z++) d2h(h->d, out + z, &h->slots[z]->icp->record, 1);
         sync(h->d);
         return LVI_OK;                                               // device errors travel in each record's status
@@ -648,7 +623,7 @@ int32_t lvi_get_scan_info(lvi_lidar* h, lvi_scan_info* out)
 {
     if (!h || !out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!h->cur().have_org) return fail(LVI_ERR_STATE, "scan not organised");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         const int n = read_int(d, d.d_n);
         out->n = n;
@@ -663,7 +638,7 @@ int32_t lvi_get_features(lvi_lidar* h, lvi_cloud* corner, lvi_cloud* surf)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!h->cur().have_feat) return fail(LVI_ERR_STATE, "features not extracted");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         int32_t st = check_dev_status(d); if (st) return st;
         const Counts c = read_counts(d);
@@ -675,7 +650,7 @@ int32_t lvi_get_scan_ds(lvi_lidar* h, lvi_cloud* c0, lvi_cloud* c1)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!h->cur().have_ds) return fail(LVI_ERR_STATE, "scan not downsampled");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         const Counts c = read_counts(d);
         int32_t st = fetch_cloud(d, d.cornerDS, c.ncds, c0); if (st) return st;
@@ -686,7 +661,7 @@ int32_t lvi_get_map_ds(lvi_lidar* h, lvi_cloud* c0, lvi_cloud* c1)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!h->cur().have_map) return fail(LVI_ERR_STATE, "map not built");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         int32_t st = check_dev_status(d); if (st) return st;
         const Counts c = read_counts(d);
@@ -697,7 +672,7 @@ int32_t lvi_get_map_ds(lvi_lidar* h, lvi_cloud* c0, lvi_cloud* c1)
 int32_t lvi_get_counts(lvi_lidar* h, int32_t counts[8])
 {
     if (!h || !counts) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         const Counts c = read_counts(h->cur());
         counts[0] = c.n; counts[1] = c.ncorner; counts[2] = c.nsurf; counts[3] = c.ncds; counts[4] = c.nsds; counts[5] = c.mcds; counts[6] = c.msds; counts[7] = 0;
         return LVI_OK;
@@ -707,7 +682,7 @@ int32_t lvi_get_counts(lvi_lidar* h, int32_t counts[8])
 int32_t lvi_get_pose_record(lvi_lidar* h, lvi_pose_record* out)
 {
     if (!h || !out) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         d2h(d, out, &d.icp->record, 1);
         sync(d);
@@ -738,7 +713,7 @@ int32_t lvi_keyframe_add(lvi_lidar* h, const lvi_pt* corner, int32_t nc, const l
 {
     if (!h || nc < 0 || ns < 0 || (nc > 0 && !corner) || (ns > 0 && !surf) || !pose) return fail(LVI_ERR_INVALID_ARG, "bad keyframe arguments");
     int32_t st = kf_reserve(h, nc, ns); if (st) return st;
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
         h2d(d, d.kfPool + d.kf_pool_used, corner, (size_t)nc);
         h2d(d, d.kfPool + d.kf_pool_used + nc, surf, (size_t)ns);
@@ -750,7 +725,7 @@ int32_t lvi_keyframe_add_current(lvi_lidar* h, const float pose[6], int32_t* ind
 {
     if (!h || !pose) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!h->cur().have_ds) return fail(LVI_ERR_STATE, "scan not downsampled");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;                                          // the store
         LidarDev& q = h->cur();                                      // the scan (selected batch slot)
         int nq[3] = {0, 0, 0};
@@ -778,7 +753,7 @@ int32_t lvi_keyframe_count(lvi_lidar* h, int32_t* n_keyframes, int32_t* n_points
 int32_t lvi_keyframes_clear(lvi_lidar* h)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
         join_map(d); sync(d);                                        // an assembly in flight still reads the pool
         gmap_join(d);                                                // … and so may a global-map build
@@ -800,7 +775,7 @@ int32_t lvi_map_assemble(lvi_lidar* h, const int32_t* key_indices, int32_t n_key
     }
     if (tc > h->d.map_cap || ts > h->d.map_cap) return fail(LVI_ERR_CAPACITY, "map exceeds max_map_points");
     if (h->shared_by > 0) return fail(LVI_ERR_STATE, "other handles read this handle's map (lvi_map_share)");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         unshare_map(h);
         drop_graph(h);
         stage_map_assemble(h->d, key_indices, n_keys);                                      // extractCloud's fuse loop into the raw map (slot 0)
@@ -816,7 +791,7 @@ int32_t lvi_map_update(lvi_lidar* h, const int32_t* key_indices, int32_t n_keys)
         if (key_indices[i] < 0 || key_indices[i] >= (int)h->d.kf_pose.size()) return fail(LVI_ERR_INVALID_ARG, "key index out of range");
     if (h->shared_by > 0) return fail(LVI_ERR_STATE, "other handles read this handle's map (lvi_map_share)");
     bool done = false;
-    int32_t st = guarded(h, [&]() -> int32_t {
+    int32_t st = guarded(h->d.device, [&]() -> int32_t {
         drop_graph(h);
         done = h->slots.size() == 1 && stage_map_update(h->d, key_indices, n_keys);
         return LVI_OK;
@@ -833,7 +808,7 @@ int32_t lvi_scan_set_deskew(lvi_lidar* h, const lvi_deskew_info* info)
     if (!info || !info->imu_available) return LVI_OK;
     if (info->imu_pointer_cur < 1 || info->imu_pointer_cur >= LVI_DESKEW_MAX_IMU || !info->imu_time || !info->imu_rot_x || !info->imu_rot_y || !info->imu_rot_z)
         return fail(LVI_ERR_INVALID_ARG, "bad deskew table");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         const size_t m = (size_t)info->imu_pointer_cur + 1;
         const double* src[4] = {info->imu_time, info->imu_rot_x, info->imu_rot_y, info->imu_rot_z};
@@ -864,7 +839,7 @@ int32_t lvi_extract_features(lvi_lidar* h, const lvi_scan_info* in, lvi_cloud* c
 {
     if (!h || !in) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (in->n < 0 || in->n > h->cur().ext_cap) return fail(LVI_ERR_CAPACITY, "scan_info.n exceeds capacity");
-    int32_t st = guarded(h, [&]() -> int32_t {
+    int32_t st = guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         const int n = in->n, NS = d.P.N_SCAN;
         // ring bases: start_ring_index[r] = count_r + 4 (imageProjection.cpp:630)
@@ -889,9 +864,9 @@ int32_t lvi_extract_features(lvi_lidar* h, const lvi_scan_info* in, lvi_cloud* c
 int32_t lvi_voxel_downsample(lvi_lidar* h, const lvi_pt* in, int32_t n, float leaf, lvi_pt* out, int32_t out_capacity, int32_t* n_out)
 {
     if (!h || n < 0 || (n > 0 && !in) || !(leaf > 0.f) || !n_out) return fail(LVI_ERR_INVALID_ARG, "bad voxel arguments");
-    if (n > h->d.voxGen.seg_cap) return fail(LVI_ERR_CAPACITY, "n exceeds capacity");
+    if (n > h->d.gen.cap) return fail(LVI_ERR_CAPACITY, "n exceeds capacity");
     const bool no_tiny = getenv("LVI_VOX_NO_TINY") != nullptr;                // tests: the general path for every size
-    if (n > 0 && n <= VOX_TINY && !no_tiny) return guarded(h, [&]() -> int32_t {
+    if (n > 0 && n <= VOX_TINY && !no_tiny) return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
         if (!h->vt_in) {
             LVI_HIP(hipHostMalloc((void**)&h->vt_in, sizeof(lvi_pt) * VOX_TINY, hipHostMallocDefault));
@@ -906,7 +881,7 @@ int32_t lvi_voxel_downsample(lvi_lidar* h, const lvi_pt* in, int32_t n, float le
         // them, and the local-map update that follows would start when the scan-side stages are over instead of beside them.
         // (The staging block is single; the previous call waited for its kernel.)
         std::memcpy(h->vt_in, in, sizeof(lvi_pt) * (size_t)n);
-        voxel_tiny(d.ctx2, h->vt_in, n, leaf, d.voxGen.seg_cap, d.voxGen.bin_pts, d.voxGen.bin_max, h->vt_out, h->vt_hdr, h->vt_cells, h->vt_counts, h->vt_keys);
+        voxel_tiny(d.ctx2, h->vt_in, n, leaf, d.gen.cap, d.gen.vox.bin_pts, d.gen.vox.bin_max, h->vt_out, h->vt_hdr, h->vt_cells, h->vt_counts, h->vt_keys);
         LVI_HIP(hipStreamSynchronize(d.ctx2.stream));
         const int m = h->vt_hdr[0];
         *n_out = m;
@@ -918,21 +893,16 @@ int32_t lvi_voxel_downsample(lvi_lidar* h, const lvi_pt* in, int32_t n, float le
         if (m > out_capacity) return fail(LVI_ERR_CAPACITY, "voxel output capacity too small");
         return LVI_OK;
     });
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
-        h2d(d, d.genIn, in, (size_t)n);
-        if (!d.gen_static_set || d.gen_leaf != leaf) {               // (the segment table is uploaded once per leaf size: the node calls this with one leaf for every scan)
-            VoxSegStatic st{d.genIn, nullptr, d.genOut, leaf};
-            d.voxGen.set_static(d.ctx, &st);
-            d.gen_static_set = true; d.gen_leaf = leaf;
-        }
-        d.voxGen.n_host[0] = n; d.voxGen.use_n_host = true;          // the length travels as a kernel argument
-        voxel_downsample_batch(d.ctx, d.voxGen, "gen", n);
+        h2d(d, d.gen.fused, in, (size_t)n);
+        d.gen.prepare(d.ctx, leaf);                                  // (the node calls this with one leaf for every scan)
+        d.gen.filter(d.ctx, n, "gen");
         // ONE wait: the count and (at most the caller's capacity of) the output travel together
         const int fetch = std::min(n, out_capacity);
         int m = 0;
-        d2h(d, &m, d.voxGen.d_nout, 1);
-        if (fetch > 0) d2h(d, out, d.genOut, (size_t)fetch);
+        d2h(d, &m, d.gen.vox.d_nout, 1);
+        if (fetch > 0) d2h(d, out, d.gen.out, (size_t)fetch);
         sync(d);
         *n_out = m;
         h->vdbg_pending = true; h->vdbg_n = n;                       // LVI_DBG_VOXEL_*: fetched when asked for (until the next call that uses the generic buffers)
@@ -952,7 +922,7 @@ int32_t lvi_scan_to_map(lvi_lidar* h, const lvi_pt* corner, int32_t nc, const lv
 {
     if (!h || nc < 0 || ns < 0 || (nc > 0 && !corner) || (ns > 0 && !surf)) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     if (nc > h->cur().ext_cap || ns > h->cur().ext_cap || (long long)nc + ns > h->cur().ext_cap) return fail(LVI_ERR_CAPACITY, "feature clouds exceed capacity (corner + surf <= N_SCAN * Horizon_SCAN)");
-    int32_t st = guarded(h, [&]() -> int32_t {
+    int32_t st = guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         h2d(d, d.corner, corner, (size_t)nc); h2d(d, d.surf, surf, (size_t)ns);
         h2d(d, d.d_ncorner, &nc, 1); h2d(d, d.voxRing.d_nout + d.P.N_SCAN, &ns, 1);
@@ -968,13 +938,13 @@ int32_t lvi_scan_to_map(lvi_lidar* h, const lvi_pt* corner, int32_t nc, const lv
 int32_t lvi_transform_cloud(lvi_lidar* h, const lvi_pt* in, int32_t n, const float pose6[6], lvi_pt* out)
 {
     if (!h || n < 0 || (n > 0 && (!in || !out)) || !pose6) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
-    if (n > h->d.voxGen.seg_cap) return fail(LVI_ERR_CAPACITY, "n exceeds capacity");
-    return guarded(h, [&]() -> int32_t {
+    if (n > h->d.gen.cap) return fail(LVI_ERR_CAPACITY, "n exceeds capacity");
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->d;
         h->vdbg_pending = false;
-        h2d(d, d.genIn, in, (size_t)n);
-        transform_cloud(d, d.genIn, n, pose6, d.genOut);
-        d2h(d, out, d.genOut, (size_t)n);
+        h2d(d, d.gen.fused, in, (size_t)n);
+        transform_cloud(d, d.gen.fused, n, pose6, d.gen.out);
+        d2h(d, out, d.gen.out, (size_t)n);
         sync(d);
         return LVI_OK;
     });
@@ -984,7 +954,7 @@ int32_t lvi_transform_cloud(lvi_lidar* h, const lvi_pt* in, int32_t n, const flo
 int32_t lvi_debug_get(lvi_lidar* h, int32_t what, void* dst, int64_t cap, int64_t* n_bytes)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         auto need_feat = [&]() { return d.have_feat && d.have_org; };
         switch (what) {
@@ -1028,7 +998,7 @@ int32_t lvi_debug_get(lvi_lidar* h, int32_t what, void* dst, int64_t cap, int64_
                 return dbg_out(v, 0, dst, cap, n_bytes);
             }
             case LVI_DBG_VOXEL_KEYS: case LVI_DBG_VOXEL_CELLS: case LVI_DBG_VOXEL_COUNTS:
-                if (h->vdbg_pending) { voxel_debug_fetch(h->d.ctx, h->d.voxGen, h->vdbg_n, h->vkeys, h->vcells, h->vcounts); h->vdbg_pending = false; }
+                if (h->vdbg_pending) { voxel_debug_fetch(h->d.ctx, h->d.gen.vox, h->vdbg_n, h->vkeys, h->vcells, h->vcounts); h->vdbg_pending = false; }
                 return dbg_out(what == LVI_DBG_VOXEL_KEYS ? h->vkeys : (what == LVI_DBG_VOXEL_CELLS ? h->vcells : h->vcounts), 0, dst, cap, n_bytes);
             case LVI_DBG_ICP_JTJ: {
                 if (!h->have_icp_host) return fail(LVI_ERR_STATE, "scan_match not run");
@@ -1052,7 +1022,7 @@ int32_t lvi_debug_knn(lvi_lidar* h, int32_t which, const lvi_pt* queries, int32_
 {
     if (!h || !queries || !idx || !sqd || nq < 0 || which < 0 || which > 1) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     if (!h->cur().have_map) return fail(LVI_ERR_STATE, "map not built");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         struct Scratch {                                   // freed on every way out, a throwing LVI_HIP included
             void* p[3] = {nullptr, nullptr, nullptr};
@@ -1075,7 +1045,7 @@ int32_t lvi_debug_residuals(lvi_lidar* h, int32_t which, const float pose[6], lv
 {
     if (!h || !pose || !coeff || !flag || !n || which < 0 || which > 1) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     if (!h->cur().have_map || !h->cur().have_ds) return fail(LVI_ERR_STATE, "map or scan DS missing");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         LidarDev& d = h->cur();
         int nq[3];
         d2h(d, nq, d.voxScan.d_nout, 3); sync(d);
@@ -1093,17 +1063,17 @@ int32_t lvi_debug_residuals(lvi_lidar* h, int32_t which, const float pose[6], lv
 int32_t lvi_prof_enable(lvi_lidar* h, int32_t on)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
-    return guarded(h, [&]() -> int32_t { sync(h->d); h->d.prof.collect(); h->d.prof.on = on != 0; return LVI_OK; });
+    return guarded(h->d.device, [&]() -> int32_t { sync(h->d); h->d.prof.collect(); h->d.prof.on = on != 0; return LVI_OK; });
 }
 int32_t lvi_prof_reset(lvi_lidar* h)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
-    return guarded(h, [&]() -> int32_t { sync(h->d); h->d.prof.reset(); return LVI_OK; });
+    return guarded(h->d.device, [&]() -> int32_t { sync(h->d); h->d.prof.reset(); return LVI_OK; });
 }
 int32_t lvi_prof_read(lvi_lidar* h, lvi_kernel_stat* stats, int32_t capacity, int32_t* n)
 {
     if (!h || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->d.device, [&]() -> int32_t {
         Profiler& p = h->d.prof;
         sync(h->d); p.collect();
         int k = 0;

@@ -16,15 +16,9 @@
 #include "../../include/lvi_depth.h"
 #include "lvi_voxel.hpp"
 
-namespace lvi {
-void voxel_debug_fetch(const Ctx& ctx, const VoxelPlan& p, int n_in, std::vector<int32_t>& keys, std::vector<int32_t>& cells, std::vector<int32_t>& counts);
-}
-
 using namespace lvi;
 
 namespace {
-
-int32_t fail(int32_t code, const std::string& msg) { set_error(msg); return code; }
 
 constexpr int NB = LVI_DEPTH_BINS;                 // num_bins
 constexpr int NBINS = NB * NB;
@@ -309,21 +303,6 @@ struct lvi_depth {
 
 namespace {
 
-template <class F>
-int32_t guarded(lvi_depth* h, F&& f)
-{
-    try {
-        if (h) LVI_HIP(hipSetDevice(h->device));
-        return f();
-    } catch (const HipError& e) {
-        char buf[512];
-        snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.e), e.file, e.line);
-        return fail(LVI_ERR_HIP, buf);
-    } catch (const std::exception& e) {
-        return fail(LVI_ERR_HIP, e.what());
-    }
-}
-
 template <class AR> void depth_layout(AR& ar, lvi_depth& h)
 {
     const size_t W = (size_t)h.C * h.P;
@@ -392,7 +371,7 @@ int32_t cloud_entry(lvi_depth* h, const lvi_pt* pts, bool device, int32_t n, con
     if (used) *used = 0;
     if (++h->lidar_count % (h->skip + 1) != 0) return LVI_OK;        // static int lidar_count = -1; ++ % (LIDAR_SKIP + 1)
     if (!pose6) return LVI_OK;                                        // no TF: nothing else changes
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         if (n > 0) LVI_HIP(hipMemcpyAsync(h->rawIn, pts, sizeof(lvi_pt) * (size_t)n, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->ctx.stream));
         return cloud_enqueue(h, n, pose6, stamp, used);
     });
@@ -418,7 +397,7 @@ int32_t lvi_depth_create(int32_t device, int32_t max_clouds, int32_t max_cloud_p
     h->device = device; h->C = max_clouds; h->P = max_cloud_points; h->F = max_features; h->skip = lidar_skip; h->window = window_s;
     // float dist_sq_threshold = pow(sin(bin_res / 180.0 * M_PI) * 5.0, 2)
     h->thr = (float)std::pow(std::sin((double)BIN_RES / 180.0 * M_PI) * 5.0, 2);
-    const int32_t st = guarded(h, [&]() -> int32_t {
+    const int32_t st = guarded(h->device, [&]() -> int32_t {
         LVI_HIP(hipStreamCreateWithFlags(&h->ctx.stream, hipStreamNonBlocking));
         ArenaSizer sz; depth_layout(sz, *h);
         h->arena.init(sz.used + (1 << 16));
@@ -469,7 +448,7 @@ int32_t lvi_depth_get(lvi_depth* h, const float pose6[6], const float* features_
     // 0.2 / 0.3: no depth cloud or no transform: the initial values, the GPU state is not touched
     if (!pose6) return LVI_OK;                                        // (the debug views keep the previous call's)
     if (h->cloud_n == 0 || n == 0) { h->searched = false; h->last_nf = 0; return LVI_OK; }
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         const Ctx& c = h->ctx;
         const Mat34 Minv = affine_inverse(get_transformation(pose6));
         std::memcpy(h->h_io, features_xyz, sizeof(float) * 3 * (size_t)n);
@@ -501,7 +480,7 @@ int32_t lvi_depth_set_cloud(lvi_depth* h, const lvi_pt* pts, int32_t n)
 {
     if (!h || n < 0 || (n > 0 && !pts)) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     if ((long long)n > (long long)h->C * h->P) return fail(LVI_ERR_CAPACITY, "n exceeds max_clouds * max_cloud_points");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         if (n > 0) LVI_HIP(hipMemcpyAsync(h->cloud, pts, sizeof(lvi_pt) * (size_t)n, hipMemcpyHostToDevice, h->ctx.stream));
         h->h_cnt[2] = n;
         LVI_HIP(hipMemcpyAsync(h->cloudN, h->h_cnt + 2, sizeof(int), hipMemcpyHostToDevice, h->ctx.stream));
@@ -517,7 +496,7 @@ int32_t lvi_depth_get_cloud(lvi_depth* h, lvi_pt* out, int32_t cap, int32_t* n_o
     *n_out = h->cloud_n;
     const int m = std::min(cap, h->cloud_n);
     if (m <= 0) return LVI_OK;
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         LVI_HIP(hipMemcpyAsync(out, h->cloud, sizeof(lvi_pt) * (size_t)m, hipMemcpyDeviceToHost, h->ctx.stream));
         wait(h);
         return LVI_OK;
@@ -528,7 +507,7 @@ int32_t lvi_depth_debug_voxel(lvi_depth* h, int32_t* cells, int32_t* counts, int
 {
     if (!h || !n_out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (h->used_total == 0) return fail(LVI_ERR_STATE, "no window fusion yet");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         std::vector<int32_t> k, cl, ct;
         voxel_debug_fetch(h->ctx, h->vox2, h->fused_n_last, k, cl, ct);
         *n_out = (int32_t)cl.size();
@@ -543,7 +522,7 @@ int32_t lvi_depth_debug_range(lvi_depth* h, int32_t* sel)
 {
     if (!h || !sel) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!h->searched) return fail(LVI_ERR_STATE, "no range image yet");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         std::vector<unsigned long long> k(NBINS);
         LVI_HIP(hipMemcpyAsync(k.data(), h->range, sizeof(unsigned long long) * NBINS, hipMemcpyDeviceToHost, h->ctx.stream));
         wait(h);
@@ -556,7 +535,7 @@ int32_t lvi_depth_debug_sphere(lvi_depth* h, lvi_pt* out, int32_t cap, int32_t* 
 {
     if (!h || !n_out || (cap > 0 && !out)) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     if (!h->searched) return fail(LVI_ERR_STATE, "no sphere cloud yet");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         int n = 0;
         LVI_HIP(hipMemcpyAsync(&n, h->nsph, sizeof(int), hipMemcpyDeviceToHost, h->ctx.stream));
         wait(h);
@@ -573,7 +552,7 @@ int32_t lvi_depth_debug_neighbors(lvi_depth* h, int32_t* idx, float* sqd, int32_
     *n_out = h->last_nf;
     const int m = std::min(cap, h->last_nf);
     if (m <= 0) return LVI_OK;
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         if (idx) LVI_HIP(hipMemcpyAsync(idx, h->nbr, sizeof(int32_t) * 3 * (size_t)m, hipMemcpyDeviceToHost, h->ctx.stream));
         if (sqd) LVI_HIP(hipMemcpyAsync(sqd, h->nsqd, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost, h->ctx.stream));
         wait(h);

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <string>
 #include <vector>
 
@@ -27,6 +28,25 @@ struct HipError { hipError_t e; const char* what; const char* file; int line; };
         hipError_t _e = (call);                                                               \
         if (_e != hipSuccess) throw ::lvi::HipError{_e, #call, __FILE__, __LINE__};           \
     } while (0)
+
+// The guard of every C-ABI entry point: no exception crosses extern "C".  A HIP failure or any std::exception becomes
+// LVI_ERR_HIP with its text in lvi_last_error(); a negative device skips hipSetDevice.
+inline int32_t fail(int32_t code, const std::string& msg) { set_error(msg); return code; }
+
+template <class F>
+int32_t guarded(int device, F&& f)
+{
+    try {
+        if (device >= 0) LVI_HIP(hipSetDevice(device));
+        return f();
+    } catch (const HipError& e) {
+        char buf[512];
+        snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.e), e.file, e.line);
+        return fail(LVI_ERR_HIP, buf);
+    } catch (const std::exception& e) {
+        return fail(LVI_ERR_HIP, e.what());
+    }
+}
 
 // one record per profiled launch
 struct ProfRec { int name_id; double bytes; hipEvent_t a, b; };

@@ -22,8 +22,6 @@ using namespace lvi;
 
 namespace {
 
-int32_t fail(int32_t code, const std::string& msg) { set_error(msg); return code; }
-
 constexpr int MODEL_POINTS = 7;
 constexpr int RANSAC_MAX_ATTEMPTS = 10000;   // RANSACPointSetRegistrator::run: getSubset(..., rng, 10000)
 constexpr int LMEDS_MAX_ATTEMPTS = 1000;     // LMeDSPointSetRegistrator::run: getSubset's default maxAttempts
@@ -420,25 +418,6 @@ struct lvi_fmat {
     std::vector<int> last_subsets;
 };
 
-namespace {
-
-template <class F>
-int32_t guarded(lvi_fmat* h, F&& f)
-{
-    try {
-        if (h) LVI_HIP(hipSetDevice(h->device));
-        return f();
-    } catch (const HipError& e) {
-        char buf[512];
-        snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.e), e.file, e.line);
-        return fail(LVI_ERR_HIP, buf);
-    } catch (const std::exception& e) {
-        return fail(LVI_ERR_HIP, e.what());
-    }
-}
-
-}  // namespace
-
 extern "C" {
 
 int32_t lvi_fmat_abi_version(void) { return LVI_FMAT_ABI_VERSION; }
@@ -458,7 +437,7 @@ int32_t lvi_fmat_create(int32_t device, int32_t max_points, int32_t max_iters, l
     h->off_log = h->off_sub + align256(sizeof(int) * 7 * (size_t)h->I);
     h->in_bytes = h->off_log + align256(sizeof(double) * ((size_t)h->P + 1));
     h->out_bytes = align256(sizeof(lvi_fmat_info)) + align256((size_t)h->P);
-    const int32_t st = guarded(h, [&]() -> int32_t {
+    const int32_t st = guarded(h->device, [&]() -> int32_t {
         LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         LVI_HIP(hipMalloc((void**)&h->d_in, h->in_bytes));
         LVI_HIP(hipMalloc((void**)&h->d_out, h->out_bytes));
@@ -503,7 +482,7 @@ int32_t lvi_fmat_find(lvi_fmat* h, const float* pts1_xy, const float* pts2_xy, i
     if (!h || !pts1_xy || !pts2_xy || !status_out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (n < MODEL_POINTS) return fail(LVI_ERR_INVALID_ARG, "n < 7: findFundamentalMat has no model");
     if (n > h->P) return fail(LVI_ERR_INVALID_ARG, "n > max_points");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         // findFundamentalMat's argument defaults
         if (threshold <= 0) threshold = 3;
         if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
@@ -563,7 +542,7 @@ int32_t lvi_fmat_find(lvi_fmat* h, const float* pts1_xy, const float* pts2_xy, i
 int32_t lvi_fmat_trace(lvi_fmat* h, int32_t* subsets, int32_t* nmodels, double* F, int32_t* score, int32_t cap, int32_t* n_out)
 {
     if (!h || cap < 0) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         const int m = std::min(cap, h->last_nsub);
         if (n_out) *n_out = h->last_nsub;
         if (m == 0) return LVI_OK;

@@ -1798,32 +1798,36 @@ void kf_assemble_launch(const Ctx& cx, const LidarDev::KfSeg* d_segs, int nseg, 
     }
 }
 
+void kf_pieces_add(const LidarDev& d, KfPieces& t, int key, int out_c, int out_s)
+{
+    float M[12];
+    kf_matrix(d.kf_pose[key].data(), M);
+    for (int w = 0; w < 2; w++) {
+        const int out = w ? out_s : out_c;
+        if (out < 0) continue;
+        KfSeg& sg = t.h[t.n++];
+        sg.which = out;
+        sg.in_off = w ? d.kf_off_s[key] : d.kf_off_c[key];
+        sg.n = w ? d.kf_n_s[key] : d.kf_n_c[key];
+        sg.out_off = t.off[out];
+        for (int q = 0; q < 12; q++) sg.A[q] = M[q];
+        t.off[out] += sg.n;
+        t.maxn = std::max(t.maxn, sg.n);
+    }
+}
+
 void stage_map_assemble(LidarDev& d, const int32_t* keys, int n_keys)
 {
     join_map(d);                                    // the previous build may still read the raw buffers
     // h_kfSeg is reused by every call: the previous assembly's H2D copy must have been consumed
     LVI_HIP(hipStreamSynchronize(d.ctx.stream));
-    int oc = 0, os = 0, nseg = 0, maxn = 1;
-    for (int i = 0; i < n_keys; i++) {
-        const int k = keys[i];
-        float M[12];
-        kf_matrix(d.kf_pose[k].data(), M);
-        for (int which = 0; which < 2; which++) {
-            LidarDev::KfSeg& sg = d.h_kfSeg[nseg++];
-            sg.which = which;
-            sg.in_off = which ? d.kf_off_s[k] : d.kf_off_c[k];
-            sg.n = which ? d.kf_n_s[k] : d.kf_n_c[k];
-            sg.out_off = which ? os : oc;
-            for (int q = 0; q < 12; q++) sg.A[q] = M[q];
-            (which ? os : oc) += sg.n;
-            maxn = std::max(maxn, sg.n);
-        }
+    KfPieces t{d.h_kfSeg};
+    for (int i = 0; i < n_keys; i++) kf_pieces_add(d, t, keys[i], 0, 1);       // corner -> mapCornerRaw, surf -> mapSurfRaw
+    if (t.n) {
+        LVI_HIP(hipMemcpyAsync(d.d_kfSeg, d.h_kfSeg, sizeof(KfSeg) * (size_t)t.n, hipMemcpyHostToDevice, d.ctx.stream));
+        kf_assemble_launch(d.ctx, d.d_kfSeg, t.n, t.maxn, d.kfPool, d.mapCornerRaw, d.mapSurfRaw, (double)t.off[0] + t.off[1]);
     }
-    if (nseg) {
-        LVI_HIP(hipMemcpyAsync(d.d_kfSeg, d.h_kfSeg, sizeof(LidarDev::KfSeg) * (size_t)nseg, hipMemcpyHostToDevice, d.ctx.stream));
-        kf_assemble_launch(d.ctx, d.d_kfSeg, nseg, maxn, d.kfPool, d.mapCornerRaw, d.mapSurfRaw, (double)oc + os);
-    }
-    d.n_map_corner = oc; d.n_map_surf = os; d.have_map_raw = true;
+    d.n_map_corner = t.off[0]; d.n_map_surf = t.off[1]; d.have_map_raw = true;
     d.voxMap.bbox_cached = false;
 }
 

@@ -22,8 +22,6 @@ using namespace lvi;
 
 namespace {
 
-int32_t fail(int32_t code, const std::string& msg) { set_error(msg); return code; }
-
 constexpr int TILE_W = 64, TILE_H = 16;      // output tile of the two stencil kernels: 256 threads, 4 rows per thread
 constexpr int BLUR_R = 4, FAST_R = 3;
 constexpr int MAX_SIDE = 8192;
@@ -297,21 +295,6 @@ struct lvi_kf {
 
 namespace {
 
-template <class F>
-int32_t guarded(lvi_kf* h, F&& f)
-{
-    try {
-        if (h) LVI_HIP(hipSetDevice(h->device));
-        return f();
-    } catch (const HipError& e) {
-        char buf[512];
-        snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.e), e.file, e.line);
-        return fail(LVI_ERR_HIP, buf);
-    } catch (const std::exception& e) {
-        return fail(LVI_ERR_HIP, e.what());
-    }
-}
-
 Slot* slot_of(lvi_kf* h, int32_t slot) { return h && slot >= 0 && slot < h->S ? &h->slots[slot] : nullptr; }
 
 }  // namespace
@@ -346,7 +329,7 @@ int32_t lvi_kf_create(int32_t device, int32_t max_width, int32_t max_height, int
     h->off_img = align256(sizeof(float) * 2 * (size_t)h->Wn);
     h->in_bytes = h->off_img + (size_t)h->W * h->H;
     h->match_bytes = 9 * (size_t)h->Wn;
-    const int32_t st = guarded(h, [&]() -> int32_t {
+    const int32_t st = guarded(h->device, [&]() -> int32_t {
         LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         ArenaSizer sz;
         h->layout(sz);
@@ -385,7 +368,7 @@ int32_t lvi_kf_describe(lvi_kf* h, int32_t slot, const uint8_t* img, int32_t w, 
     if (stride < w) return fail(LVI_ERR_INVALID_ARG, "stride < width");
     if (n_window < 0 || n_window > h->Wn) return fail(LVI_ERR_INVALID_ARG, "n_window must be 0..max_window");
     if (n_window > 0 && !window_xy) return fail(LVI_ERR_INVALID_ARG, "null window points");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         if (n_window > 0) std::memcpy(h->h_in, window_xy, sizeof(float) * 2 * (size_t)n_window);
         uint8_t* stage = reinterpret_cast<uint8_t*>(h->h_in + h->off_img);
         for (int y = 0; y < hgt; y++) std::memcpy(stage + (size_t)y * w, img + (size_t)y * stride, (size_t)w);
@@ -430,7 +413,7 @@ int32_t lvi_kf_get(lvi_kf* h, int32_t slot, int32_t counts[2], float* kp_xy, flo
     Slot* s = slot_of(h, slot);
     if (!s) return fail(LVI_ERR_INVALID_ARG, "null handle or slot out of range");
     if (!s->valid) return fail(LVI_ERR_INVALID_ARG, "empty slot");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         if (counts) { counts[0] = s->n_kp; counts[1] = s->n_win; }
         const size_t k = (size_t)s->n_kp, n = (size_t)s->n_win;
         bool any = false;
@@ -452,7 +435,7 @@ int32_t lvi_kf_put(lvi_kf* h, int32_t slot, int32_t n_keypoints, const float* kp
     Slot* s = slot_of(h, slot);
     if (!s) return fail(LVI_ERR_INVALID_ARG, "null handle or slot out of range");
     if (n_keypoints < 0 || n_keypoints > h->K || n_window < 0 || n_window > h->Wn) return fail(LVI_ERR_INVALID_ARG, "counts beyond the handle's capacity");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         const size_t k = (size_t)n_keypoints, n = (size_t)n_window;
         s->valid = false;
         auto up = [&](void* dst, const void* src, size_t bytes) {
@@ -483,7 +466,7 @@ int32_t lvi_kf_match(lvi_kf* h, int32_t cur_slot, int32_t old_slot, uint8_t* sta
     if (!c->valid || !o->valid) return fail(LVI_ERR_INVALID_ARG, "empty or released slot");
     const int n = c->n_win;
     if (n == 0) return LVI_OK;
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         int* d_index = reinterpret_cast<int*>(h->d_match);
         int* d_dist = d_index + h->Wn;
         uint8_t* d_status = reinterpret_cast<uint8_t*>(d_dist + h->Wn);
@@ -503,7 +486,7 @@ int32_t lvi_kf_debug_maps(lvi_kf* h, uint8_t* blur, uint8_t* score, int32_t wh_o
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
     if (h->last_w == 0) return fail(LVI_ERR_STATE, "no describe yet");
-    return guarded(h, [&]() -> int32_t {
+    return guarded(h->device, [&]() -> int32_t {
         const size_t n = (size_t)h->last_w * h->last_h;
         if (wh_out) { wh_out[0] = h->last_w; wh_out[1] = h->last_h; }
         if (blur) LVI_HIP(hipMemcpyAsync(blur, h->d_blur, n, hipMemcpyDeviceToHost, h->stream));

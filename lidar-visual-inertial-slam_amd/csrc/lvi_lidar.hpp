@@ -3,7 +3,7 @@
 #pragma once
 #include <array>
 
-#include "lvi_voxel.hpp"
+#include "lvi_kfjob.hpp"
 
 namespace lvi {
 
@@ -77,7 +77,7 @@ struct LidarDev {
     lvi_livox_pt* raw = nullptr; int n_raw = 0;            // after dropping the last point
     lvi_livox_pt* h_raw[2] = {nullptr, nullptr}; hipEvent_t ev_raw[2] = {nullptr, nullptr}; int raw_slot = 0;   // pinned staging ring of lvi_scan_upload
     // ---- f-4 (keyframe store): clouds in the sensor frame, packed in one pool; tables on the host
-    struct KfSeg { int in_off, n, out_off, which; float A[12]; };              // one (keyframe, corner|surf) piece of an assembly
+    using KfSeg = lvi::KfSeg;
     lvi_pt* kfPool = nullptr; int kf_pool_cap = 0, kf_pool_used = 0;
     std::vector<int> kf_off_c, kf_n_c, kf_off_s, kf_n_s;
     std::vector<std::array<float, 6>> kf_pose;
@@ -115,9 +115,7 @@ struct LidarDev {
     GridIndex grid[2];
 
     // ---- generic one-call voxel (lvi_voxel_downsample)
-    lvi_pt *genIn = nullptr, *genOut = nullptr;
-    VoxelPlan voxGen;                                      // 1 segment
-    unsigned* genKeysDbg = nullptr;
+    Submap gen;                                            // also lvi_transform_cloud's staging
     // ---- icp
     IcpState* icp = nullptr;
     unsigned long long* icpAcc = nullptr;                  // [3][8][56] exact fixed-point totals of the 28 sums of a GN launch (coarse, fine): 8 shards, 3 buffers in rotation
@@ -146,8 +144,6 @@ struct LidarDev {
     std::array<int, 8> graph_key = {-1, -1, -1, -1, -1, -1, -1, -1};   // what the capture froze (lvi_scan_replay_enqueue)
     // stage flags (host)
     bool have_raw = false, have_org = false, have_feat = false, have_ds = false, have_map_raw = false, have_map = false;
-    bool gen_valid = false; int gen_n = 0;
-    bool gen_static_set = false; float gen_leaf = 0.f;     // lvi_voxel_downsample: the segment table on the device is for this leaf size
     // ---- f-4: incremental local map (lvi_map_update); slot 0 of a non-batch handle only
     IncMap inc;
     bool inc_ready = false;                                // tables hold exactly inc_mult's keyframes at inc_pose's poses
@@ -197,6 +193,11 @@ void transform_cloud(LidarDev& d, const lvi_pt* d_in, int n, const float pose6[6
 void kf_matrix(const float* T, float M[12]);               // pcl::getTransformation of a keyframe pose (host libm)
 // kf_assemble_kernel over nseg pieces of the keyframe pool (launched in chunks of at most 65535 pieces)
 void kf_assemble_launch(const Ctx& cx, const LidarDev::KfSeg* d_segs, int nseg, int maxn, const lvi_pt* pool, lvi_pt* outC, lvi_pt* outS, double n_pts);
+// append the corner and the surf piece of one key to a piece table, each to output out_c / out_s (0 | 1; < 0: leave the cloud out).
+// The key's pose is read NOW: later lvi_keyframe_set_pose calls change later tables only.
+void kf_pieces_add(const LidarDev& d, KfPieces& t, int key, int out_c, int out_s);
+// lvi_capi.hip
+LidarDev& lidar_slot0(lvi_lidar* h);                       // the keyframe store's slot of a handle
 // lvi_gmap.hip
 void gmap_join(LidarDev& d);                               // wait for a global-map build in flight (lvi_keyframes_clear)
 void gmap_free(LidarDev& d);                               // … and free the arena (lvi_lidar_destroy)

@@ -3,7 +3,8 @@
 // store, on a stream of its own.
 //
 // Submaps: the global map's fuse (kf_assemble_kernel, one launch for both clouds: piece.which picks the output) and
-// two one-segment VoxelPlans in this arena — the same kernels as lvi_gmap_build, hence the same bits.
+// two Submaps in this arena — the same kernels as lvi_gmap_build, hence the same bits.  The stream, the arena, the
+// piece table and the fetch are the keyframe job of lvi_kfjob.hpp.
 //
 // ICP (restated in tests/loop_ref.py):
 //   index      a uniform grid over the filtered target: bbox (integer atomics on order-encoded floats), count, one
@@ -27,9 +28,6 @@
 
 namespace lvi {
 
-LidarDev& lidar_slot0(lvi_lidar* h);                       // lvi_capi.hip
-
-constexpr int LOOP_FETCH_CHUNK = 1 << 16;                  // points per pinned staging buffer of lvi_loop_fetch (1 MB)
 constexpr int LOOP_MAX_CELLS = 1 << 21;                    // cells of the nearest-neighbour grid
 constexpr int LOOP_MAX_DIM = 2048;                         // cells per axis
 constexpr int LOOP_MAX_SEARCH = 1024;                      // largest search_num (segment table: 2 + 2 (2 n + 1) pieces)
@@ -60,24 +58,17 @@ struct LoopState {                                         // device; copied who
     double dbgSums[NS];
 };
 
-struct LoopDev {
-    int cap_s = 0, cap_t = 0, req_s = 0, req_t = 0, seg_cap = 0, nblk_s = 0;
-    Arena arena;
-    Ctx ctx;                                               // own stream; prof = null: never profiled
-    hipEvent_t evMain = nullptr, evDone = nullptr;
-    hipEvent_t evBuf[2] = {nullptr, nullptr};
-    lvi_pt *fusedS = nullptr, *outS = nullptr, *fusedT = nullptr, *outT = nullptr, *aligned = nullptr;
-    VoxelPlan voxS, voxT;
-    LidarDev::KfSeg* d_seg = nullptr; LidarDev::KfSeg* h_seg = nullptr;
+struct LoopDev : KfJob {
+    int req_s = 0, req_t = 0, nblk_s = 0;                  // the reservations asked for (the submaps' capacities are at least 64)
+    Submap src, tgt;
+    lvi_pt* aligned = nullptr;                             // [src.cap]
     int *cellStart = nullptr, *cellCount = nullptr;        // [LOOP_MAX_CELLS + 2]
-    float4* sorted = nullptr;                              // [cap_t] xyz + original index (int bits)
-    int* nnIdx = nullptr; float* nnSqd = nullptr;          // [cap_s]
+    float4* sorted = nullptr;                              // [tgt.cap] xyz + original index (int bits)
+    int* nnIdx = nullptr; float* nnSqd = nullptr;          // [src.cap]
     double* partial = nullptr;                             // [nblk_s][NS]
     LoopState* st = nullptr; LoopState* h_st = nullptr;    // device / pinned
-    lvi_pt* h_buf[2] = {nullptr, nullptr};
-    bool static_set = false; float static_leaf = 0.f;
     // last job (host)
-    bool started = false, pending = false;
+    bool started = false;
     int nS_fused = 0, nT_fused = 0, key_cur = -1, key_pre = -1;
     lvi_loop_params P{};
 };
@@ -450,64 +441,29 @@ __global__ __launch_bounds__(64) void loop_dbgsum_kernel(LoopState* st, const do
 // ---------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------
-int32_t fail(int32_t code, const std::string& msg) { set_error(msg); return code; }
-
-template <class F>
-int32_t lp_guarded(LidarDev& d, F&& f)
-{
-    try {
-        LVI_HIP(hipSetDevice(d.device));
-        return f();
-    } catch (const HipError& e) {
-        char buf[512];
-        snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.e), e.file, e.line);
-        return fail(LVI_ERR_HIP, buf);
-    } catch (const std::exception& e) {
-        return fail(LVI_ERR_HIP, e.what());
-    }
-}
-
 void lp_destroy(LoopDev* g)
 {
     if (!g) return;
-    if (g->ctx.stream) (void)hipStreamSynchronize(g->ctx.stream);
-    g->voxS.release(); g->voxT.release();
-    g->arena.release();
-    if (g->h_seg) (void)hipHostFree(g->h_seg);
+    g->destroy();
+    g->src.release(); g->tgt.release();
     if (g->h_st) (void)hipHostFree(g->h_st);
-    for (int b = 0; b < 2; b++) {
-        if (g->h_buf[b]) (void)hipHostFree(g->h_buf[b]);
-        if (g->evBuf[b]) (void)hipEventDestroy(g->evBuf[b]);
-    }
-    if (g->evMain) (void)hipEventDestroy(g->evMain);
-    if (g->evDone) (void)hipEventDestroy(g->evDone);
-    if (g->ctx.stream) (void)hipStreamDestroy(g->ctx.stream);
     delete g;
 }
 
 template <class AR>
-void lp_layout(AR& ar, LoopDev& g)
+void lp_layout(AR& ar, LoopDev& g, int cap_s, int cap_t)
 {
-    g.fusedS = ar.template alloc<lvi_pt>(g.cap_s);
-    g.outS = ar.template alloc<lvi_pt>(g.cap_s);
-    g.aligned = ar.template alloc<lvi_pt>(g.cap_s);
-    g.fusedT = ar.template alloc<lvi_pt>(g.cap_t);
-    g.outT = ar.template alloc<lvi_pt>(g.cap_t);
-    g.voxS.allocate(ar, 1, g.cap_s, false);
-    g.voxT.allocate(ar, 1, g.cap_t, false);
-    g.d_seg = ar.template alloc<LidarDev::KfSeg>((size_t)g.seg_cap);
+    g.src.layout(ar, cap_s);
+    g.tgt.layout(ar, cap_t);
+    g.aligned = ar.template alloc<lvi_pt>(cap_s);
+    g.d_seg = ar.template alloc<KfSeg>((size_t)g.seg_cap);
     g.cellStart = ar.template alloc<int>((size_t)LOOP_MAX_CELLS + 2);
     g.cellCount = ar.template alloc<int>((size_t)LOOP_MAX_CELLS + 2);
-    g.sorted = ar.template alloc<float4>(g.cap_t);
-    g.nnIdx = ar.template alloc<int>(g.cap_s);
-    g.nnSqd = ar.template alloc<float>(g.cap_s);
+    g.sorted = ar.template alloc<float4>(cap_t);
+    g.nnIdx = ar.template alloc<int>(cap_s);
+    g.nnSqd = ar.template alloc<float>(cap_s);
     g.partial = ar.template alloc<double>((size_t)g.nblk_s * NS);
     g.st = ar.template alloc<LoopState>(1);
-}
-
-void lp_wait(LoopDev& g)
-{
-    if (g.pending) { LVI_HIP(hipEventSynchronize(g.evDone)); g.pending = false; }
 }
 
 void lp_launch_nn(LoopDev& g, int mode, double max2)
@@ -521,7 +477,7 @@ void lp_launch_nn(LoopDev& g, int mode, double max2)
 
 void loop_join(LidarDev& d)
 {
-    if (d.loop) lp_wait(*d.loop);
+    if (d.loop) d.loop->wait();
 }
 
 void loop_free(LidarDev& d)
@@ -560,30 +516,18 @@ int32_t lvi_loop_reserve(lvi_lidar* h, int32_t max_source_points, int32_t max_ta
         return fail(LVI_ERR_INVALID_ARG, "reservations must be 1..LVI_LOOP_MAX_POINTS");
     LidarDev& d = lidar_slot0(h);
     if (d.loop && d.loop->req_s >= max_source_points && d.loop->req_t >= max_target_points) return LVI_OK;
-    return lp_guarded(d, [&]() -> int32_t {
-        if (d.loop) lp_wait(*d.loop);
+    return guarded(d.device, [&]() -> int32_t {
+        loop_join(d);
         LoopDev* g = new LoopDev();
         try {
             g->req_s = std::max(max_source_points, d.loop ? d.loop->req_s : 0);
             g->req_t = std::max(max_target_points, d.loop ? d.loop->req_t : 0);
-            g->cap_s = std::max(g->req_s, 64); g->cap_t = std::max(g->req_t, 64);
-            g->nblk_s = div_up(g->cap_s, LOOP_NN_BLOCK);
-            g->seg_cap = 2 + 2 * (2 * LOOP_MAX_SEARCH + 1);
-            LVI_HIP(hipStreamCreateWithFlags(&g->ctx.stream, hipStreamNonBlocking));
-            LVI_HIP(hipEventCreateWithFlags(&g->evMain, hipEventDisableTiming));
-            LVI_HIP(hipEventCreateWithFlags(&g->evDone, hipEventDisableTiming));
-            for (int b = 0; b < 2; b++) {
-                LVI_HIP(hipEventCreateWithFlags(&g->evBuf[b], hipEventDisableTiming));
-                LVI_HIP(hipHostMalloc((void**)&g->h_buf[b], sizeof(lvi_pt) * LOOP_FETCH_CHUNK, hipHostMallocDefault));
-            }
-            LVI_HIP(hipHostMalloc((void**)&g->h_seg, sizeof(LidarDev::KfSeg) * (size_t)g->seg_cap, hipHostMallocDefault));
+            const int cap_s = std::max(g->req_s, 64), cap_t = std::max(g->req_t, 64);
+            g->nblk_s = div_up(cap_s, LOOP_NN_BLOCK);
+            g->create(2 + 2 * (2 * LOOP_MAX_SEARCH + 1));
             LVI_HIP(hipHostMalloc((void**)&g->h_st, sizeof(LoopState), hipHostMallocDefault));
-            ArenaSizer sz;
-            lp_layout(sz, *g);
-            g->arena.init(sz.used + (1 << 20));
-            lp_layout(g->arena, *g);
-            LVI_HIP(hipMemsetAsync(g->arena.base, 0, g->arena.size, g->ctx.stream));   // the plans' counters start at zero
-            g->voxS.mode = d.P.voxel_mode; g->voxT.mode = d.P.voxel_mode;
+            g->init_arena([&](auto& ar) { lp_layout(ar, *g, cap_s, cap_t); });
+            g->src.vox.mode = d.P.voxel_mode; g->tgt.vox.mode = d.P.voxel_mode;
             LVI_HIP(hipStreamSynchronize(g->ctx.stream));
         } catch (...) {
             lp_destroy(g);
@@ -599,7 +543,7 @@ int32_t lvi_loop_release(lvi_lidar* h)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null handle");
     LidarDev& d = lidar_slot0(h);
-    return lp_guarded(d, [&]() -> int32_t { loop_free(d); return LVI_OK; });
+    return guarded(d.device, [&]() -> int32_t { loop_free(d); return LVI_OK; });
 }
 
 int32_t lvi_loop_arena_bytes(lvi_lidar* h, int64_t* bytes)
@@ -631,46 +575,28 @@ int32_t lvi_loop_start(lvi_lidar* h, int32_t key_cur, int32_t key_pre, const lvi
     for (int k = k0; k <= k1; k++) totT += (long long)d.kf_n_c[k] + d.kf_n_s[k];
     if (totS > g.req_s) return fail(LVI_ERR_CAPACITY, "fused source submap exceeds the loop-closure reservation");
     if (totT > g.req_t) return fail(LVI_ERR_CAPACITY, "fused target submap exceeds the loop-closure reservation");
-    return lp_guarded(d, [&]() -> int32_t {
-        lp_wait(g);                                                    // the previous job still reads h_seg / writes the arena
+    return guarded(d.device, [&]() -> int32_t {
+        g.wait();                                                      // the previous job still reads h_seg / writes the arena
         const int nS = (int)totS, nT = (int)totT;
         const bool filtS = P.leaf > 0.f && nS > 0, filtT = P.leaf > 0.f && nT > 0;
-        if ((filtS || filtT) && (!g.static_set || g.static_leaf != P.leaf)) {   // (synchronises the job's stream: before the wait below is enqueued)
-            VoxSegStatic ss{g.fusedS, nullptr, g.outS, P.leaf}, stt{g.fusedT, nullptr, g.outT, P.leaf};
-            g.voxS.set_static(g.ctx, &ss);
-            g.voxT.set_static(g.ctx, &stt);
-            g.static_set = true; g.static_leaf = P.leaf;
+        if (filtS || filtT) {                                          // (synchronises the job's stream: before the fork below is enqueued)
+            g.src.prepare(g.ctx, P.leaf);
+            g.tgt.prepare(g.ctx, P.leaf);
         }
-        // pieces: the source (which = 0 -> fusedS), then the target (which = 1 -> fusedT); corner_k then surf_k per key
-        int ns = 0, offS = 0, offT = 0, maxn = 1;
-        auto piece = [&](int k, int which) {
-            float M[12];
-            kf_matrix(d.kf_pose[k].data(), M);                         // the pose of the store NOW
-            for (int w = 0; w < 2; w++) {
-                LidarDev::KfSeg& sg = g.h_seg[ns++];
-                sg.which = which;
-                sg.in_off = w ? d.kf_off_s[k] : d.kf_off_c[k];
-                sg.n = w ? d.kf_n_s[k] : d.kf_n_c[k];
-                sg.out_off = which ? offT : offS;
-                for (int q = 0; q < 12; q++) sg.A[q] = M[q];
-                (which ? offT : offS) += sg.n;
-                maxn = std::max(maxn, sg.n);
-            }
-        };
-        piece(key_cur, 0);
-        for (int k = k0; k <= k1; k++) piece(k, 1);
-        // everything enqueued on the main stream so far (keyframe copies into the store) before the fuse reads the pool
-        LVI_HIP(hipEventRecord(g.evMain, d.ctx.stream));
-        LVI_HIP(hipStreamWaitEvent(g.ctx.stream, g.evMain, 0));
+        // pieces: the source (output 0 -> src.fused), then the target (output 1 -> tgt.fused); corner_k then surf_k per key
+        KfPieces t{g.h_seg};
+        kf_pieces_add(d, t, key_cur, 0, 0);
+        for (int k = k0; k <= k1; k++) kf_pieces_add(d, t, k, 1, 1);
+        g.fork(d.ctx);
         hipStream_t s = g.ctx.stream;
-        LVI_HIP(hipMemcpyAsync(g.d_seg, g.h_seg, sizeof(LidarDev::KfSeg) * (size_t)ns, hipMemcpyHostToDevice, s));
-        kf_assemble_launch(g.ctx, g.d_seg, ns, maxn, d.kfPool, g.fusedS, g.fusedT, (double)(nS + nT));
-        if (filtS) { g.voxS.n_host[0] = nS; g.voxS.use_n_host = true; voxel_downsample_batch(g.ctx, g.voxS, "loop_src", nS); }
-        if (filtT) { g.voxT.n_host[0] = nT; g.voxT.use_n_host = true; voxel_downsample_batch(g.ctx, g.voxT, "loop_tgt", nT); }
+        LVI_HIP(hipMemcpyAsync(g.d_seg, g.h_seg, sizeof(KfSeg) * (size_t)t.n, hipMemcpyHostToDevice, s));
+        kf_assemble_launch(g.ctx, g.d_seg, t.n, t.maxn, d.kfPool, g.src.fused, g.tgt.fused, (double)(nS + nT));
+        if (filtS) g.src.filter(g.ctx, nS, "loop_src");
+        if (filtT) g.tgt.filter(g.ctx, nT, "loop_tgt");
         g.P = P;
         LoopJob j{};
-        j.srcFused = g.fusedS; j.srcOut = g.outS; j.tgtFused = g.fusedT; j.tgtOut = g.outT;
-        j.gS = g.voxS.d_grid; j.gT = g.voxT.d_grid; j.noutS = g.voxS.d_nout; j.noutT = g.voxT.d_nout;
+        j.srcFused = g.src.fused; j.srcOut = g.src.out; j.tgtFused = g.tgt.fused; j.tgtOut = g.tgt.out;
+        j.gS = g.src.vox.d_grid; j.gT = g.tgt.vox.d_grid; j.noutS = g.src.vox.d_nout; j.noutT = g.tgt.vox.d_nout;
         j.nS_fused = nS; j.nT_fused = nT; j.filtS = filtS; j.filtT = filtT;
         j.min_s = P.min_source; j.min_t = P.min_target;
         j.cell0 = P.leaf > 0.f ? std::max(4.f * P.leaf, 0.5f) : 1.f;
@@ -692,8 +618,8 @@ int32_t lvi_loop_start(lvi_lidar* h, int32_t key_cur, int32_t key_pre, const lvi
         hipLaunchKernelGGL(loop_finish_kernel, dim3(1), dim3(64), 0, s, g.st, g.partial);
         LVI_HIP(hipGetLastError());
         LVI_HIP(hipMemcpyAsync(g.h_st, g.st, sizeof(LoopState), hipMemcpyDeviceToHost, s));
-        LVI_HIP(hipEventRecord(g.evDone, s));
-        g.pending = true; g.started = true;
+        g.mark_done();
+        g.started = true;
         g.nS_fused = nS; g.nT_fused = nT; g.key_cur = key_cur; g.key_pre = key_pre;
         return LVI_OK;
     });
@@ -730,7 +656,7 @@ int32_t lvi_loop_result(lvi_lidar* h, lvi_loop_info* info)
 {
     if (!h || !info) return fail(LVI_ERR_INVALID_ARG, "null argument");
     LidarDev& d = lidar_slot0(h);
-    return lp_guarded(d, [&]() -> int32_t { return lp_result(d, info); });
+    return guarded(d.device, [&]() -> int32_t { return lp_result(d, info); });
 }
 
 int32_t lvi_loop_fetch(lvi_lidar* h, int32_t what, int32_t first, int32_t count, lvi_pt* out)
@@ -738,29 +664,14 @@ int32_t lvi_loop_fetch(lvi_lidar* h, int32_t what, int32_t first, int32_t count,
     if (!h || (count > 0 && !out) || first < 0 || count < 0) return fail(LVI_ERR_INVALID_ARG, "bad fetch arguments");
     if (what < LVI_LOOP_SOURCE || what > LVI_LOOP_ALIGNED) return fail(LVI_ERR_INVALID_ARG, "what must be LVI_LOOP_SOURCE, _TARGET or _ALIGNED");
     LidarDev& d = lidar_slot0(h);
-    return lp_guarded(d, [&]() -> int32_t {
+    return guarded(d.device, [&]() -> int32_t {
         lvi_loop_info r;
         const int32_t st = lp_result(d, &r);
         if (st) return st;
         LoopDev& g = *d.loop;
         const int n = what == LVI_LOOP_TARGET ? r.n_target : r.n_source;
         if ((long long)first + count > n) return fail(LVI_ERR_INVALID_ARG, "fetch range outside the cloud");
-        const lvi_pt* src = (what == LVI_LOOP_ALIGNED ? g.aligned : what == LVI_LOOP_TARGET ? g.h_st->tgt : g.h_st->src) + first;
-        // double buffer: chunk c is copied into h_buf[c & 1] while the host copies chunk c - 1 out of the other one
-        const int nch = (count + LOOP_FETCH_CHUNK - 1) / LOOP_FETCH_CHUNK;
-        for (int c = 0; c <= nch; c++) {
-            if (c < nch) {
-                const int len = std::min(LOOP_FETCH_CHUNK, count - c * LOOP_FETCH_CHUNK);
-                LVI_HIP(hipMemcpyAsync(g.h_buf[c & 1], src + (size_t)c * LOOP_FETCH_CHUNK, sizeof(lvi_pt) * (size_t)len, hipMemcpyDeviceToHost, g.ctx.stream));
-                LVI_HIP(hipEventRecord(g.evBuf[c & 1], g.ctx.stream));
-            }
-            if (c > 0) {
-                const int p = c - 1;
-                const int len = std::min(LOOP_FETCH_CHUNK, count - p * LOOP_FETCH_CHUNK);
-                LVI_HIP(hipEventSynchronize(g.evBuf[p & 1]));
-                std::memcpy(out + (size_t)p * LOOP_FETCH_CHUNK, g.h_buf[p & 1], sizeof(lvi_pt) * (size_t)len);
-            }
-        }
+        g.fetch((what == LVI_LOOP_ALIGNED ? g.aligned : what == LVI_LOOP_TARGET ? g.h_st->tgt : g.h_st->src) + first, count, out);
         return LVI_OK;
     });
 }
@@ -769,7 +680,7 @@ int32_t lvi_loop_debug_step(lvi_lidar* h, const float* T, int32_t* nn_idx, float
 {
     if (!h || !T || !nn_idx || !nn_sqd || !sums) return fail(LVI_ERR_INVALID_ARG, "null argument");
     LidarDev& d = lidar_slot0(h);
-    return lp_guarded(d, [&]() -> int32_t {
+    return guarded(d.device, [&]() -> int32_t {
         lvi_loop_info r;
         const int32_t st = lp_result(d, &r);
         if (st) return st;

@@ -956,9 +956,7 @@ void layout(AR& ar, LidarDev& d)
         d.grid[w].meta = ar.template alloc<GridIndex::Meta>(1);
     }
     const int gen_cap = d.map_owner ? 64 : std::max(d.raw_cap, d.map_cap);      // one-call voxel / transform entry points run on slot 0
-    d.genIn = ar.template alloc<lvi_pt>(gen_cap); d.genOut = ar.template alloc<lvi_pt>(gen_cap);
-    d.voxGen.allocate(ar, 1, gen_cap, false);
-    d.genKeysDbg = ar.template alloc<unsigned>(gen_cap);
+    d.gen.layout(ar, gen_cap);
     d.kfPool = ar.template alloc<lvi_pt>((size_t)std::max(d.kf_pool_cap, 1));
     if (d.kf_pool_cap > 0 && d.P.batch_scans <= 1) {
         // incremental local map: slots for 4x the voxels a full map of this capacity typically leaves (tombstones included; a
@@ -1058,7 +1056,7 @@ void lidar_allocate(LidarDev& d)
     st[0] = VoxSegStatic{d.mapCornerRaw, nullptr, d.mapCornerDS, d.P.mappingCornerLeafSize};
     st[1] = VoxSegStatic{d.mapSurfRaw, nullptr, d.mapSurfDS, d.P.mappingSurfLeafSize};
     d.voxMap.set_static(d.ctx, st.data());
-    d.voxRing.mode = d.voxScan.mode = d.voxMap.mode = d.voxGen.mode = d.P.voxel_mode;
+    d.voxRing.mode = d.voxScan.mode = d.voxMap.mode = d.gen.vox.mode = d.P.voxel_mode;
     // the scan grids take their input counts straight from the producers' device counters (no 1-thread launch in between)
     d.voxScan.n_dev[0] = d.d_ncorner; d.voxScan.n_dev[1] = d.voxRing.d_nout + d.P.N_SCAN;
     LVI_HIP(hipStreamSynchronize(d.ctx.stream));

@@ -807,8 +807,6 @@ __global__ __launch_bounds__(SORTLDS ? 1024 : 64) void gftt_pick_kernel(PickArgs
     if (SORTLDS && l == 0 && a.dbg) { a.dbg[0] = tq[1] - tq[0]; a.dbg[1] = tq[2]; a.dbg[2] = tq[3]; a.dbg[3] = clock64() - tq[0]; a.dbg[4] = nbands; a.dbg[5] = total; a.dbg[6] = nacc; }
 }
 
-int32_t tfail(int32_t code, const std::string& msg) { set_error(msg); return code; }
-
 }  // namespace
 
 }  // namespace lvi
@@ -857,19 +855,6 @@ struct lvi_tracker {
 };
 
 namespace {
-
-template <class F>
-int32_t tguard(lvi_tracker* t, F&& f)
-{
-    try {
-        if (t) LVI_HIP(hipSetDevice(t->device));
-        return f();
-    } catch (const HipError& e) {
-        char buf[512];
-        snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.e), e.file, e.line);
-        return tfail(LVI_ERR_HIP, buf);
-    }
-}
 
 template <class AR>
 void tracker_layout(AR& ar, lvi_tracker& t)
@@ -950,17 +935,17 @@ void lvi_tracker_params_default(lvi_tracker_params* p)
 
 int32_t lvi_tracker_create(const lvi_tracker_params* p, int32_t device, lvi_tracker** out)
 {
-    if (!p || !out) return tfail(LVI_ERR_INVALID_ARG, "null argument");
+    if (!p || !out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (p->lk_win < 3 || (p->lk_win & 1) == 0 || p->lk_win > LK_WIN_MAX || p->lk_max_level < 0 || p->lk_max_level >= MAX_LEVELS)
-        return tfail(LVI_ERR_INVALID_ARG, "bad LK parameters (odd window <= 21, maxLevel 0..7)");
-    if (p->max_width <= 0 || p->max_height <= 0 || p->max_features <= 0 || p->max_features > 4096) return tfail(LVI_ERR_INVALID_ARG, "bad capacities");
+        return fail(LVI_ERR_INVALID_ARG, "bad LK parameters (odd window <= 21, maxLevel 0..7)");
+    if (p->max_width <= 0 || p->max_height <= 0 || p->max_features <= 0 || p->max_features > 4096) return fail(LVI_ERR_INVALID_ARG, "bad capacities");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tfail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return tfail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
     lvi_tracker* t = new lvi_tracker();
     t->P = *p; t->device = device;
     { const char* e = getenv("LVI_GFTT_RADIX"); t->gftt_force_radix = e && e[0] == '1'; }
-    int32_t st = tguard(t, [&]() -> int32_t {
+    int32_t st = guarded(t->device, [&]() -> int32_t {
         LVI_HIP(hipStreamCreateWithFlags(&t->ctx.stream, hipStreamNonBlocking));
         t->ctx.prof = &t->prof;
         ArenaSizer sz; tracker_layout(sz, *t);
@@ -1016,15 +1001,15 @@ void lvi_tracker_destroy(lvi_tracker* t)
 
 int32_t lvi_tracker_sync(lvi_tracker* t)
 {
-    if (!t) return tfail(LVI_ERR_INVALID_ARG, "null handle");
-    return tguard(t, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(t->ctx.stream)); return LVI_OK; });
+    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return guarded(t->device, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(t->ctx.stream)); return LVI_OK; });
 }
 
 int32_t lvi_tracker_push_image(lvi_tracker* t, const uint8_t* img, int32_t w, int32_t h, int32_t stride)
 {
-    if (!t || !img || w <= 0 || h <= 0 || stride < w) return tfail(LVI_ERR_INVALID_ARG, "bad image");
-    if (w > t->P.max_width || h > t->P.max_height) return tfail(LVI_ERR_CAPACITY, "image exceeds capacity");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || !img || w <= 0 || h <= 0 || stride < w) return fail(LVI_ERR_INVALID_ARG, "bad image");
+    if (w > t->P.max_width || h > t->P.max_height) return fail(LVI_ERR_CAPACITY, "image exceeds capacity");
+    return guarded(t->device, [&]() -> int32_t {
         if (t->have_forw && (w != t->w || h != t->h)) { t->have_forw = t->have_cur = false; }
         if (t->have_forw) { std::swap(t->cur, t->forw); t->have_cur = true; }     // cur_img = forw_img (:203)
         t->w = w; t->h = h;
@@ -1050,10 +1035,10 @@ int32_t lvi_tracker_push_image(lvi_tracker* t, const uint8_t* img, int32_t w, in
 int32_t lvi_clahe(lvi_tracker* t, const uint8_t* img, int32_t w, int32_t h, int32_t stride, double clip_limit, int32_t tiles_x, int32_t tiles_y,
                   uint8_t* out, int32_t out_stride)
 {
-    if (!t || !img || !out || w <= 0 || h <= 0 || stride < w || out_stride < w) return tfail(LVI_ERR_INVALID_ARG, "bad image");
-    if (tiles_x < 1 || tiles_y < 1 || tiles_x > CLAHE_MAX_TILES || tiles_y > CLAHE_MAX_TILES) return tfail(LVI_ERR_INVALID_ARG, "bad tile grid");
-    if (w > t->P.max_width || h > t->P.max_height) return tfail(LVI_ERR_CAPACITY, "image exceeds capacity");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || !img || !out || w <= 0 || h <= 0 || stride < w || out_stride < w) return fail(LVI_ERR_INVALID_ARG, "bad image");
+    if (tiles_x < 1 || tiles_y < 1 || tiles_x > CLAHE_MAX_TILES || tiles_y > CLAHE_MAX_TILES) return fail(LVI_ERR_INVALID_ARG, "bad tile grid");
+    if (w > t->P.max_width || h > t->P.max_height) return fail(LVI_ERR_CAPACITY, "image exceeds capacity");
+    return guarded(t->device, [&]() -> int32_t {
         LVI_HIP(hipMemcpy2DAsync(t->d_stage, (size_t)w, img, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, t->ctx.stream));
         run_clahe(*t, t->d_stage, t->d_eq, w, h, clip_limit, tiles_x, tiles_y);
         LVI_HIP(hipMemcpy2DAsync(out, (size_t)out_stride, t->d_eq, (size_t)w, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, t->ctx.stream));
@@ -1064,18 +1049,18 @@ int32_t lvi_clahe(lvi_tracker* t, const uint8_t* img, int32_t w, int32_t h, int3
 
 int32_t lvi_tracker_set_equalize(lvi_tracker* t, int32_t on, double clip_limit, int32_t tiles_x, int32_t tiles_y)
 {
-    if (!t) return tfail(LVI_ERR_INVALID_ARG, "null handle");
-    if (on && (tiles_x < 1 || tiles_y < 1 || tiles_x > CLAHE_MAX_TILES || tiles_y > CLAHE_MAX_TILES)) return tfail(LVI_ERR_INVALID_ARG, "bad tile grid");
+    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    if (on && (tiles_x < 1 || tiles_y < 1 || tiles_x > CLAHE_MAX_TILES || tiles_y > CLAHE_MAX_TILES)) return fail(LVI_ERR_INVALID_ARG, "bad tile grid");
     t->equalize = on != 0; t->clahe_clip = clip_limit; t->clahe_tx = tiles_x; t->clahe_ty = tiles_y;
     return LVI_OK;
 }
 
 int32_t lvi_undistort_points(lvi_tracker* t, const lvi_mei_params* cam, const float* xy, int32_t n, float* un_xy)
 {
-    if (!t || !cam || n < 0 || (n > 0 && (!xy || !un_xy))) return tfail(LVI_ERR_INVALID_ARG, "bad arguments");
-    if (n > t->P.max_features) return tfail(LVI_ERR_CAPACITY, "too many points");
+    if (!t || !cam || n < 0 || (n > 0 && (!xy || !un_xy))) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
+    if (n > t->P.max_features) return fail(LVI_ERR_CAPACITY, "too many points");
     if (n == 0) return LVI_OK;
-    return tguard(t, [&]() -> int32_t {
+    return guarded(t->device, [&]() -> int32_t {
         LVI_HIP(hipMemcpyAsync(t->d_un_in, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, t->ctx.stream));
         LVI_LAUNCH(t->ctx, "mei_undistort", 16.0 * n, hipLaunchKernelGGL(mei_undistort_kernel, dim3(div_up(n, 64)), dim3(64), 0, t->ctx.stream, *cam, t->d_un_in, n, t->d_un_out, (const int*)nullptr));
         LVI_HIP(hipMemcpyAsync(un_xy, t->d_un_out, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, t->ctx.stream));
@@ -1086,9 +1071,9 @@ int32_t lvi_undistort_points(lvi_tracker* t, const lvi_mei_params* cam, const fl
 
 int32_t lvi_tracker_set_points(lvi_tracker* t, const float* cur_xy, int32_t n)
 {
-    if (!t || n < 0 || (n > 0 && !cur_xy)) return tfail(LVI_ERR_INVALID_ARG, "bad points");
-    if (n > t->P.max_features) return tfail(LVI_ERR_CAPACITY, "too many points");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || n < 0 || (n > 0 && !cur_xy)) return fail(LVI_ERR_INVALID_ARG, "bad points");
+    if (n > t->P.max_features) return fail(LVI_ERR_CAPACITY, "too many points");
+    return guarded(t->device, [&]() -> int32_t {
         if (n) {
             const int slot = (t->pts_slot ^= 1);
             LVI_HIP(hipEventSynchronize(t->ev_pts[slot]));
@@ -1102,8 +1087,8 @@ int32_t lvi_tracker_set_points(lvi_tracker* t, const float* cur_xy, int32_t n)
 
 int32_t lvi_tracker_run_lk(lvi_tracker* t)
 {
-    if (!t || !t->have_forw || !t->have_cur) return tfail(LVI_ERR_STATE, "no image pair");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || !t->have_forw || !t->have_cur) return fail(LVI_ERR_STATE, "no image pair");
+    return guarded(t->device, [&]() -> int32_t {
         LkArgs a{};
         a.prev = t->pyr[t->cur]; a.next = t->pyr[t->forw];
         const size_t F = (size_t)std::max(t->P.max_features, 64);
@@ -1125,11 +1110,11 @@ int32_t lvi_tracker_run_lk(lvi_tracker* t)
 
 int32_t lvi_tracker_get_lk(lvi_tracker* t, float* forw_xy, uint8_t* status, float* err, int32_t capacity, int32_t* n)
 {
-    if (!t || !n) return tfail(LVI_ERR_INVALID_ARG, "null argument");
-    if (!t->have_lk) return tfail(LVI_ERR_STATE, "LK not run");
+    if (!t || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    if (!t->have_lk) return fail(LVI_ERR_STATE, "LK not run");
     *n = t->n_pts;
-    if (capacity < *n) return tfail(LVI_ERR_CAPACITY, "capacity too small");
-    return tguard(t, [&]() -> int32_t {
+    if (capacity < *n) return fail(LVI_ERR_CAPACITY, "capacity too small");
+    return guarded(t->device, [&]() -> int32_t {
         const int m = *n;
         const size_t F = (size_t)std::max(t->P.max_features, 64);
         LVI_HIP(hipStreamSynchronize(t->ctx.stream));                      // lk_kernel wrote the results into pinned host memory
@@ -1142,10 +1127,10 @@ int32_t lvi_tracker_get_lk(lvi_tracker* t, float* forw_xy, uint8_t* status, floa
 
 int32_t lvi_tracker_set_mask(lvi_tracker* t, const uint8_t* mask, int32_t w, int32_t h, int32_t stride)
 {
-    if (!t) return tfail(LVI_ERR_INVALID_ARG, "null argument");
+    if (!t) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (!mask) { t->have_mask = false; return LVI_OK; }
-    if (!t->have_forw || w != t->w || h != t->h || stride < w) return tfail(LVI_ERR_INVALID_ARG, "mask size mismatch");
-    return tguard(t, [&]() -> int32_t {
+    if (!t->have_forw || w != t->w || h != t->h || stride < w) return fail(LVI_ERR_INVALID_ARG, "mask size mismatch");
+    return guarded(t->device, [&]() -> int32_t {
         LVI_HIP(hipMemcpy2DAsync(t->d_mask, (size_t)w, mask, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, t->ctx.stream));
         LVI_HIP(hipStreamSynchronize(t->ctx.stream));
         t->have_mask = true;
@@ -1182,8 +1167,8 @@ void enqueue_gftt(lvi_tracker* t, int32_t max_corners, bool lds_form)
 
 int32_t lvi_tracker_run_gftt(lvi_tracker* t, int32_t max_corners)
 {
-    if (!t || !t->have_forw) return tfail(LVI_ERR_STATE, "no image");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || !t->have_forw) return fail(LVI_ERR_STATE, "no image");
+    return guarded(t->device, [&]() -> int32_t {
         int res[2] = {0, 0};
         for (int attempt = 0; attempt < 2; attempt++) {
             enqueue_gftt(t, max_corners, attempt == 0 && !t->gftt_force_radix);
@@ -1193,8 +1178,8 @@ int32_t lvi_tracker_run_gftt(lvi_tracker* t, int32_t max_corners)
             if (res[0] != -2) break;                        // -2: more candidates than the LDS form holds -> once more, radix form
         }
         t->gftt_pending = false;
-        if (res[0] < 0) return tfail(LVI_ERR_CAPACITY, "more corners than the pick kernel's accepted-list capacity");
-        if (res[0] > t->P.max_features) return tfail(LVI_ERR_CAPACITY, "more corners than max_features");
+        if (res[0] < 0) return fail(LVI_ERR_CAPACITY, "more corners than the pick kernel's accepted-list capacity");
+        if (res[0] > t->P.max_features) return fail(LVI_ERR_CAPACITY, "more corners than max_features");
         t->gftt_n = res[0]; t->gftt_ncand = res[1]; t->have_gftt = true;
         return LVI_OK;
     });
@@ -1202,10 +1187,10 @@ int32_t lvi_tracker_run_gftt(lvi_tracker* t, int32_t max_corners)
 
 int32_t lvi_tracker_set_mask_circles(lvi_tracker* t, const float* centers_xy, int32_t n, int32_t radius)
 {
-    if (!t || n < 0 || (n > 0 && !centers_xy) || radius < 0 || radius > 120) return tfail(LVI_ERR_INVALID_ARG, "bad circle list");
-    if (!t->have_forw) return tfail(LVI_ERR_STATE, "no image");
-    if (n > t->P.max_features) return tfail(LVI_ERR_CAPACITY, "too many circles");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || n < 0 || (n > 0 && !centers_xy) || radius < 0 || radius > 120) return fail(LVI_ERR_INVALID_ARG, "bad circle list");
+    if (!t->have_forw) return fail(LVI_ERR_STATE, "no image");
+    if (n > t->P.max_features) return fail(LVI_ERR_CAPACITY, "too many circles");
+    return guarded(t->device, [&]() -> int32_t {
         CircleArgs a{t->d_mask, t->w, t->h, t->d_centers, n, radius};
         int slot = -1;
         if (n) {
@@ -1226,8 +1211,8 @@ int32_t lvi_tracker_set_mask_circles(lvi_tracker* t, const float* centers_xy, in
 
 int32_t lvi_tracker_run_gftt_async(lvi_tracker* t, int32_t max_corners)
 {
-    if (!t || !t->have_forw) return tfail(LVI_ERR_STATE, "no image");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || !t->have_forw) return fail(LVI_ERR_STATE, "no image");
+    return guarded(t->device, [&]() -> int32_t {
         enqueue_gftt(t, max_corners, !t->gftt_force_radix);
         t->gftt_pending = true; t->gftt_pending_max = max_corners; t->have_gftt = false;
         return LVI_OK;
@@ -1237,9 +1222,9 @@ int32_t lvi_tracker_run_gftt_async(lvi_tracker* t, int32_t max_corners)
 int32_t lvi_tracker_finish_frame(lvi_tracker* t, const lvi_mei_params* cam, const float* kept_xy, int32_t n_kept,
                                  float* new_xy, int32_t new_capacity, int32_t* n_new, float* un_xy)
 {
-    if (!t || n_kept < 0 || (n_kept > 0 && !kept_xy) || !n_new) return tfail(LVI_ERR_INVALID_ARG, "bad arguments");
-    if (n_kept > t->P.max_features) return tfail(LVI_ERR_CAPACITY, "too many points");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || n_kept < 0 || (n_kept > 0 && !kept_xy) || !n_new) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
+    if (n_kept > t->P.max_features) return fail(LVI_ERR_CAPACITY, "too many points");
+    return guarded(t->device, [&]() -> int32_t {
         const int F = t->P.max_features;
         for (int attempt = 0; attempt < 2; attempt++) {
             const bool with_gftt = t->gftt_pending;
@@ -1263,9 +1248,9 @@ int32_t lvi_tracker_finish_frame(lvi_tracker* t, const lvi_mei_params* cam, cons
             if (with_gftt && hdr[0] == -2 && attempt == 0) { enqueue_gftt(t, t->gftt_pending_max, false); continue; }   // beyond the LDS form: redo in the radix form
             t->gftt_pending = false;
             const int nn = with_gftt ? hdr[0] : 0;
-            if (nn < 0) return tfail(LVI_ERR_CAPACITY, "more corners than the pick kernel's accepted-list capacity");
-            if (nn > F || n_kept + nn > F) return tfail(LVI_ERR_CAPACITY, "more corners than max_features");
-            if (nn > new_capacity) return tfail(LVI_ERR_CAPACITY, "capacity too small");
+            if (nn < 0) return fail(LVI_ERR_CAPACITY, "more corners than the pick kernel's accepted-list capacity");
+            if (nn > F || n_kept + nn > F) return fail(LVI_ERR_CAPACITY, "more corners than max_features");
+            if (nn > new_capacity) return fail(LVI_ERR_CAPACITY, "capacity too small");
             *n_new = nn;
             if (with_gftt) { t->gftt_n = nn; t->gftt_ncand = hdr[1]; t->have_gftt = true; }
             if (nn && new_xy) std::memcpy(new_xy, t->h_frame_out + 4, sizeof(float) * 2 * (size_t)nn);
@@ -1278,11 +1263,11 @@ int32_t lvi_tracker_finish_frame(lvi_tracker* t, const lvi_mei_params* cam, cons
 
 int32_t lvi_tracker_get_gftt(lvi_tracker* t, float* xy, int32_t capacity, int32_t* n)
 {
-    if (!t || !n) return tfail(LVI_ERR_INVALID_ARG, "null argument");
-    if (!t->have_gftt) return tfail(LVI_ERR_STATE, "GFTT not run");
+    if (!t || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    if (!t->have_gftt) return fail(LVI_ERR_STATE, "GFTT not run");
     *n = t->gftt_n;
-    if (capacity < *n) return tfail(LVI_ERR_CAPACITY, "capacity too small");
-    return tguard(t, [&]() -> int32_t {
+    if (capacity < *n) return fail(LVI_ERR_CAPACITY, "capacity too small");
+    return guarded(t->device, [&]() -> int32_t {
         if (*n && xy) LVI_HIP(hipMemcpyAsync(xy, t->d_gftt_xy, sizeof(float) * 2 * *n, hipMemcpyDeviceToHost, t->ctx.stream));
         LVI_HIP(hipStreamSynchronize(t->ctx.stream));
         return LVI_OK;
@@ -1292,7 +1277,7 @@ int32_t lvi_tracker_get_gftt(lvi_tracker* t, float* xy, int32_t capacity, int32_
 int32_t lvi_lk_track(lvi_tracker* t, const uint8_t* prev, const uint8_t* next, int32_t w, int32_t h, int32_t stride,
                      const float* prev_xy, int32_t n, float* next_xy, uint8_t* status, float* err)
 {
-    if (!t || !prev || !next || n < 0) return tfail(LVI_ERR_INVALID_ARG, "bad arguments");
+    if (!t || !prev || !next || n < 0) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     t->have_forw = false; t->have_cur = false;
     int32_t st = lvi_tracker_push_image(t, prev, w, h, stride); if (st) return st;
     st = lvi_tracker_push_image(t, next, w, h, stride); if (st) return st;
@@ -1305,7 +1290,7 @@ int32_t lvi_lk_track(lvi_tracker* t, const uint8_t* prev, const uint8_t* next, i
 int32_t lvi_good_features(lvi_tracker* t, const uint8_t* img, const uint8_t* mask, int32_t w, int32_t h, int32_t stride,
                           int32_t max_corners, double quality, double min_dist, float* xy, int32_t xy_capacity, int32_t* n_out)
 {
-    if (!t || !img || !n_out) return tfail(LVI_ERR_INVALID_ARG, "bad arguments");
+    if (!t || !img || !n_out) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     t->have_forw = false; t->have_cur = false;
     int32_t st = lvi_tracker_push_image(t, img, w, h, stride); if (st) return st;
     st = lvi_tracker_set_mask(t, mask, w, h, stride); if (st) return st;
@@ -1319,36 +1304,36 @@ int32_t lvi_good_features(lvi_tracker* t, const uint8_t* img, const uint8_t* mas
 
 int32_t lvi_tracker_debug_get(lvi_tracker* t, int32_t what, void* dst, int64_t cap, int64_t* n_bytes)
 {
-    if (!t) return tfail(LVI_ERR_INVALID_ARG, "null handle");
-    return tguard(t, [&]() -> int32_t {
+    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return guarded(t->device, [&]() -> int32_t {
         const void* src = nullptr; int64_t bytes = 0; int32_t host_val = 0; bool host = false;
         switch (what) {
             case LVI_TDBG_PYRAMID_L1: case LVI_TDBG_PYRAMID_L2: case LVI_TDBG_PYRAMID_L3: {
                 const int l = what - LVI_TDBG_PYRAMID_L1 + 1;
-                if (!t->have_forw || l > t->pyr[t->forw].top) return tfail(LVI_ERR_STATE, "level not built");
+                if (!t->have_forw || l > t->pyr[t->forw].top) return fail(LVI_ERR_STATE, "level not built");
                 src = t->pyr[t->forw].lv[l].px; bytes = (int64_t)t->pyr[t->forw].lv[l].w * t->pyr[t->forw].lv[l].h;
                 break;
             }
             case LVI_TDBG_MINEIG:
-                if (!t->have_gftt) return tfail(LVI_ERR_STATE, "GFTT not run");
+                if (!t->have_gftt) return fail(LVI_ERR_STATE, "GFTT not run");
                 src = t->d_eig; bytes = (int64_t)t->w * t->h * 4;
                 break;
             case LVI_TDBG_GFTT_NCAND:
-                if (!t->have_gftt) return tfail(LVI_ERR_STATE, "GFTT not run");
+                if (!t->have_gftt) return fail(LVI_ERR_STATE, "GFTT not run");
                 host = true; host_val = t->gftt_ncand; bytes = 4;
                 break;
             case 7:                                  // phase stamps of gftt_sortpick (diagnostics, HIP only)
                 src = t->d_dbg; bytes = 64;
                 break;
             case LVI_TDBG_MASK:
-                if (!t->have_mask || !t->have_forw) return tfail(LVI_ERR_STATE, "no mask");
+                if (!t->have_mask || !t->have_forw) return fail(LVI_ERR_STATE, "no mask");
                 src = t->d_mask; bytes = (int64_t)t->w * t->h;
                 break;
-            default: return tfail(LVI_ERR_INVALID_ARG, "unknown debug item");
+            default: return fail(LVI_ERR_INVALID_ARG, "unknown debug item");
         }
         if (n_bytes) *n_bytes = bytes;
         if (!dst) return LVI_OK;
-        if (cap < bytes) return tfail(LVI_ERR_CAPACITY, "debug buffer too small");
+        if (cap < bytes) return fail(LVI_ERR_CAPACITY, "debug buffer too small");
         if (host) { memcpy(dst, &host_val, 4); return LVI_OK; }
         LVI_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, t->ctx.stream));
         LVI_HIP(hipStreamSynchronize(t->ctx.stream));
@@ -1358,18 +1343,18 @@ int32_t lvi_tracker_debug_get(lvi_tracker* t, int32_t what, void* dst, int64_t c
 
 int32_t lvi_tracker_prof_enable(lvi_tracker* t, int32_t on)
 {
-    if (!t) return tfail(LVI_ERR_INVALID_ARG, "null handle");
-    return tguard(t, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(t->ctx.stream)); t->prof.collect(); t->prof.on = on != 0; return LVI_OK; });
+    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return guarded(t->device, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(t->ctx.stream)); t->prof.collect(); t->prof.on = on != 0; return LVI_OK; });
 }
 int32_t lvi_tracker_prof_reset(lvi_tracker* t)
 {
-    if (!t) return tfail(LVI_ERR_INVALID_ARG, "null handle");
-    return tguard(t, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(t->ctx.stream)); t->prof.reset(); return LVI_OK; });
+    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return guarded(t->device, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(t->ctx.stream)); t->prof.reset(); return LVI_OK; });
 }
 int32_t lvi_tracker_prof_read(lvi_tracker* t, lvi_kernel_stat* stats, int32_t capacity, int32_t* n)
 {
-    if (!t || !n) return tfail(LVI_ERR_INVALID_ARG, "null argument");
-    return tguard(t, [&]() -> int32_t {
+    if (!t || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    return guarded(t->device, [&]() -> int32_t {
         Profiler& p = t->prof;
         LVI_HIP(hipStreamSynchronize(t->ctx.stream)); p.collect();
         int k = 0;

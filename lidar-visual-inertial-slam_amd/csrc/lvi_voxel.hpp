@@ -216,5 +216,7 @@ int voxel_resolve_mode(const VoxelPlan& plan);
 constexpr int VOX_TINY = 1024;
 void voxel_tiny(const Ctx& ctx, const lvi_pt* in_pinned, int n, float leaf, int seg_cap, int bin_pts, int bin_max, lvi_pt* out_pinned, int* hdr_pinned,
                 int* cells_pinned, int* counts_pinned, int* keys_pinned);
+// debug views of the plan's latest run over n_in points: per-point voxel idx, the occupied voxels and their point counts
+void voxel_debug_fetch(const Ctx& ctx, const VoxelPlan& p, int n_in, std::vector<int32_t>& keys, std::vector<int32_t>& cells, std::vector<int32_t>& counts);
 
 }  // namespace lvi

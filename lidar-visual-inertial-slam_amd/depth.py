@@ -35,13 +35,7 @@ DEPTH_SIGNATURES = {
 
 def bind(lib):
     """set the depth signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
-    if not getattr(lib, "_depth_bound", False):
-        for name, (res, args) in DEPTH_SIGNATURES.items():
-            fn = getattr(lib.dll, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._depth_bound = True
-    return lib
+    return lib.bind(DEPTH_SIGNATURES)
 
 
 def _pose(pose6):

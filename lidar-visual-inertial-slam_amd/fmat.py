@@ -34,13 +34,7 @@ FMAT_SIGNATURES = {
 
 def bind(lib):
     """set the fmat signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
-    if not getattr(lib, "_fmat_bound", False):
-        for name, (res, args) in FMAT_SIGNATURES.items():
-            fn = getattr(lib.dll, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._fmat_bound = True
-    return lib
+    return lib.bind(FMAT_SIGNATURES)
 
 
 def _info_dict(info):

@@ -36,13 +36,7 @@ GMAP_SIGNATURES = {
 
 def bind(lib):
     """set the global-map signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
-    if not getattr(lib, "_gmap_bound", False):
-        for name, (res, args) in GMAP_SIGNATURES.items():
-            fn = getattr(lib.dll, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._gmap_bound = True
-    return lib
+    return lib.bind(GMAP_SIGNATURES)
 
 
 class GlobalMap:

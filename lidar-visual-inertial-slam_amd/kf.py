@@ -37,13 +37,7 @@ KF_SIGNATURES = {
 
 def bind(lib):
     """set the keyframe signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
-    if not getattr(lib, "_kf_bound", False):
-        for name, (res, args) in KF_SIGNATURES.items():
-            fn = getattr(lib.dll, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._kf_bound = True
-    return lib
+    return lib.bind(KF_SIGNATURES)
 
 
 def mei_params(cam):

@@ -47,13 +47,7 @@ LOOP_SIGNATURES = {
 
 def bind(lib):
     """set the loop-closure signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
-    if not getattr(lib, "_loop_bound", False):
-        for name, (res, args) in LOOP_SIGNATURES.items():
-            fn = getattr(lib.dll, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._loop_bound = True
-    return lib
+    return lib.bind(LOOP_SIGNATURES)
 
 
 class LoopIcp:

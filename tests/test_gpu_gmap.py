@@ -168,6 +168,35 @@ def test_gmap_capacity(pkg, hip, ora, kfs):
     h.close()
 
 
+def test_gmap_fetch_windows(pkg, hip, ora, kfs):
+    """windows of a fused cloud of at least three fetch chunks (65 536 points each): empty, one point, one short of / exactly /
+    one past a chunk and two chunks, starts inside and on a chunk boundary, windows across boundaries, to the end — each
+    bit-equal to the slice of the whole fetch; a window past the end fails with the result and the cloud unchanged"""
+    CH = 65536
+    h = _store(pkg, hip, kfs)
+    g = pkg.GlobalMap(h)
+    per = sum(len(c) + len(s) for c, s, _ in kfs)
+    rep = -(-3 * CH // per)
+    g.reserve(rep * per)
+    N = g.build(list(range(N_KF)) * rep, G.CORNER_SURF, 0.0)
+    assert N == rep * per >= 3 * CH
+    before = g.result()
+    ref = g.fetch(pkg.gmap.FUSED).copy()
+    once = G.fuse(ora, [k[0] for k in kfs], [k[1] for k in kfs], [k[2] for k in kfs], list(range(N_KF)), G.CORNER_SURF)
+    np.testing.assert_array_equal(bits(xyzi(ref)), bits(np.tile(xyzi(once), (rep, 1))))
+    for first, count in ((0, 0), (0, 1), (0, CH - 1), (0, CH), (0, CH + 1), (1, CH), (CH - 1, 2), (CH - 1, CH + 1), (CH, CH), (0, 2 * CH),
+                         (0, 2 * CH + 1), (7, N - 7), (N, 0)):
+        got = g.fetch(pkg.gmap.FUSED, first, count)
+        assert len(got) == count
+        np.testing.assert_array_equal(bits(xyzi(got)), bits(xyzi(ref[first:first + count])), err_msg=f"first {first} count {count}")
+    with pytest.raises(pkg.LviError) as e:
+        g.fetch(pkg.gmap.FUSED, N - 1, 2)
+    assert e.value.code == -1
+    assert g.result() == before
+    np.testing.assert_array_equal(bits(xyzi(g.fetch(pkg.gmap.FUSED))), bits(xyzi(ref)))
+    h.close()
+
+
 SEQ_P = dict(N_SCAN=4, Horizon_SCAN=8192, max_raw_points=20000, max_map_points=600000, max_keyframes=64, max_keyframe_points=600000)
 
 

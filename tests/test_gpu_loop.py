@@ -237,6 +237,23 @@ def test_loop_reproducible(pkg, hip, passes):
             np.testing.assert_array_equal(a, b)
 
 
+def test_loop_fetch_windows(pkg, hip, passes):
+    """after one job, a window that starts inside each of the three clouds = that slice of the whole fetch"""
+    sc = SC.scene("revisit_a", passes)
+    h = _store(pkg, hip, sc["kfs"])
+    lp = _loop(pkg, h)
+    lp.start(SC.CUR, SC.PRE, _params(lp))
+    for what in (pkg.loop.SOURCE, pkg.loop.TARGET, pkg.loop.ALIGNED):
+        whole = lp.fetch(what).copy()
+        n = len(whole)
+        assert n > 16
+        first, count = n // 3, n - n // 3 - 5
+        got = lp.fetch(what, first, count)
+        assert len(got) == count
+        np.testing.assert_array_equal(bits(xyzi(got)), bits(xyzi(whole[first:first + count])), err_msg=f"what {what}")
+    h.close()
+
+
 SEQ_P = dict(N_SCAN=4, Horizon_SCAN=8192, max_raw_points=20000, max_map_points=600000, max_keyframes=64, max_keyframe_points=600000)
 
 
