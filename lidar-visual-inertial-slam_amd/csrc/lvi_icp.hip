@@ -841,7 +841,8 @@ __device__ void icp_finish_body(const IcpArgs& a)
     const bool ran = (status == LVI_OK);
     if (ran) {
         for (int k = 0; k < 6; k++) s.pose_trace[s.iters * 6 + k] = T[k];
-        if (a.imu_available && fabsf(a.imu_pitch) < 1.4f) {                       // transformUpdate :1347-1367
+        // transformUpdate :1347-1367.  The gate is std::abs(float) < 1.4, a double comparison: float32(1.4) = 1.39999997… passes it
+        if (a.imu_available && fabs((double)a.imu_pitch) < 1.4) {
             double r, p, y;
             q_to_rpy(q_slerp(q_rpy(T[0], 0, 0), q_rpy(a.imu_roll, 0, 0), a.imu_weight), r, p, y);
             T[0] = (float)r;
