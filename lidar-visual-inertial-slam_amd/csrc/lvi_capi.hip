@@ -113,11 +113,7 @@ int32_t check_dev_status(LidarDev& d)
     int w[2] = {0, 0};
     d2h(d, w, d.d_status, 2);
     sync(d);
-    const int st = w[0] | w[1];
-    if (st & DEV_ERR_SECTOR_TOO_LARGE) return fail(LVI_ERR_CAPACITY, "a ring sector exceeds FEAT_SEG_CAP points (Horizon_SCAN too large for the LDS-resident sector kernel)");
-    if (st & DEV_ERR_SECTOR_HANDOVER) return fail(LVI_ERR_HIP, "sector kernel: a workgroup never received its predecessor's hand-over word");
-    if (st & DEV_ERR_GRID_TOO_LARGE) return fail(LVI_ERR_CAPACITY, "local map extent too large for the KNN grid");
-    return LVI_OK;
+    return dev_status_code(w[0] | w[1]);
 }
 
 int32_t fetch_cloud(LidarDev& d, const lvi_pt* src, int n, lvi_cloud* dst)
@@ -366,7 +362,7 @@ static void unshare_map(lvi_lidar* h)
     leave_owner(h);
     join_map(h->d); sync(h->d);
     bind_raw_map(h, h->d.mapCornerOwn, h->d.mapSurfOwn);
-    h->d.have_map_raw = false; h->d.n_map_corner = h->d.n_map_surf = 0; h->d.voxMap.bbox_cached = false;
+    h->d.have_map_raw = false; h->d.n_map_corner = h->d.n_map_surf = 0; h->d.map_plan.invalidate();
     for (LidarDev* q : h->slots) q->have_map = false;
 }
 
@@ -385,7 +381,7 @@ int32_t lvi_map_share(lvi_lidar* h, lvi_lidar* owner)
         { std::lock_guard<std::mutex> lk(g_share_mu); h->share_owner = owner; owner->shared_by++; owner->sharers.push_back(h); }
         bind_raw_map(h, owner->d.mapCornerRaw, owner->d.mapSurfRaw);
         LidarDev& d = h->d;
-        d.n_map_corner = owner->d.n_map_corner; d.n_map_surf = owner->d.n_map_surf; d.have_map_raw = true; d.voxMap.bbox_cached = false;
+        d.n_map_corner = owner->d.n_map_corner; d.n_map_surf = owner->d.n_map_surf; d.have_map_raw = true; d.map_plan.invalidate();
         d.inc_ready = false;
         for (LidarDev* q : h->slots) q->have_map = false;
         return LVI_OK;
@@ -404,7 +400,7 @@ int32_t lvi_map_upload_device(lvi_lidar* h, const void* c, int32_t nc, const voi
         join_map(d);
         if (nc) LVI_HIP(hipMemcpyAsync(d.mapCornerRaw, c, sizeof(lvi_pt) * (size_t)nc, hipMemcpyDeviceToDevice, d.ctx.stream));
         if (ns) LVI_HIP(hipMemcpyAsync(d.mapSurfRaw, s, sizeof(lvi_pt) * (size_t)ns, hipMemcpyDeviceToDevice, d.ctx.stream));
-        d.n_map_corner = nc; d.n_map_surf = ns; d.have_map_raw = true; d.voxMap.bbox_cached = false; for (LidarDev* q : h->slots) q->have_map = false;
+        d.n_map_corner = nc; d.n_map_surf = ns; d.have_map_raw = true; d.map_plan.invalidate(); for (LidarDev* q : h->slots) q->have_map = false;
         return LVI_OK;
     });
 }
@@ -434,7 +430,7 @@ int32_t lvi_map_upload(lvi_lidar* h, const lvi_pt* c, int32_t nc, const lvi_pt* 
         drop_graph(h);
         h2d(d, d.mapCornerRaw, c, (size_t)nc); h2d(d, d.mapSurfRaw, s, (size_t)ns);
         sync(d);
-        d.n_map_corner = nc; d.n_map_surf = ns; d.have_map_raw = true; d.voxMap.bbox_cached = false; for (LidarDev* q : h->slots) q->have_map = false;
+        d.n_map_corner = nc; d.n_map_surf = ns; d.have_map_raw = true; d.map_plan.invalidate(); for (LidarDev* q : h->slots) q->have_map = false;
         return LVI_OK;
     });
 }
@@ -514,8 +510,9 @@ int32_t lvi_scan_replay_enqueue(lvi_lidar* h, const void* d_pts, int32_t n_raw, 
         } else {
             // everything the captured launch sequence froze: sizes, whether a map index exists (icp_init's argument) and the
             // realisation AUTO picked for each voxel plan (unknown = sorted on a plan's first batch, binned afterwards)
-            const std::array<int, 8> key = {d.n_raw, d.n_map_corner, d.n_map_surf, (rebuild_map ? 1 : 0) | (d.voxMap.bbox_cached ? 2 : 0) | (d.voxMap.hist_cached ? 4 : 0), (d.have_map || rebuild_map) ? 1 : 0,
-                                            voxel_resolve_mode(d.voxRing), voxel_resolve_mode(d.voxScan), voxel_resolve_mode(d.voxMap)};
+            const VoxPlanState vs[3] = {voxel_plan_state(d.voxRing), voxel_plan_state(d.voxScan), map_vox_state(d, d.voxMap)};
+            const std::array<int, 8> key = {d.n_raw, d.n_map_corner, d.n_map_surf, rebuild_map ? 1 : 0, (d.have_map || rebuild_map) ? 1 : 0,
+                                            vox_schedule(&vs[0], 1).key(), vox_schedule(&vs[1], 1).key(), vox_schedule(&vs[2], 1).key()};
             const bool stale = !d.graphExec || key != d.graph_key;
             if (stale) {
                 if (d.graphExec) { (void)hipGraphExecDestroy(d.graphExec); d.graphExec = nullptr; }

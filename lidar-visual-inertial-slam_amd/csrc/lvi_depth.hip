@@ -353,7 +353,7 @@ int32_t cloud_enqueue(lvi_depth* h, int n, const float pose6[6], double stamp, i
     for (int q = 0; q < a.nq; q++) a.slot[q] = h->slots[q];
     LVI_LAUNCH(c, "depth_concat", 32.0 * h->P * a.nq, hipLaunchKernelGGL(concat_kernel, dim3(div_up(h->P, 256 * 4), a.nq), dim3(256), 0, c.stream, a, h->ring, h->ringN,
                                                                           h->P, h->fused, h->fusedN));
-    voxel_downsample_batch(c, h->vox2, "depth_vox_window", (double)h->P * a.nq);
+    h->vox2.last_mode = voxel_downsample_batch(c, h->vox2, "depth_vox_window", (double)h->P * a.nq).mode;
     LVI_HIP(hipMemcpyAsync(h->cloudN, h->vox2.d_nout, sizeof(int), hipMemcpyDeviceToDevice, c.stream));
     LVI_HIP(hipMemcpyAsync(h->h_cnt, h->vox2.d_nout, sizeof(int), hipMemcpyDeviceToHost, c.stream));
     LVI_HIP(hipMemcpyAsync(h->h_cnt + 1, h->fusedN, sizeof(int), hipMemcpyDeviceToHost, c.stream));

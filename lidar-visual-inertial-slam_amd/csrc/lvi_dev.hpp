@@ -190,6 +190,16 @@ __device__ __forceinline__ float wave_max(float v)
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// LDS written by some lanes of a wavefront is read by others: order the accesses (a wavefront's LDS operations complete in order)
+__device__ __forceinline__ void wave_lds_fence() { __threadfence_block(); __builtin_amdgcn_wave_barrier(); }
+
+// round-to-nearest-even of |x| < 2^51 to an integer: one f64 add (the sum's ulp is 1) instead of the ~20 instructions of the
+// general f64 -> i64 conversion, which gfx950 does not have; the same value for every such x
+__device__ __forceinline__ long long d2ll_rn_small(double x)
+{
+    const double M = 6755399441055744.0;                            // 2^52 + 2^51
+    return __double_as_longlong(x + M) - __double_as_longlong(M);
+}
 
 // workgroup exclusive scan of one int per thread; BLOCK threads (multiple of 64, <= 1024).
 // `ws` = shared scratch of BLOCK/64 + 1 ints.  Returns the exclusive prefix; *total = sum.

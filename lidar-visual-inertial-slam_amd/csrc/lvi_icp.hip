@@ -384,7 +384,6 @@ __device__ __forceinline__ int wave_max_i(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v; }
-__device__ __forceinline__ void wave_lds_fence() { __threadfence_block(); __builtin_amdgcn_wave_barrier(); }
 
 // every lane of the wavefront calls this (act: the lane's feature searches).  true: the tile is built and `acc` reads it.
 template <int TP, int TC>
@@ -1126,19 +1125,13 @@ __device__ __forceinline__ void icp_take_sums(const IcpArgs& a, int iter, int la
 
 constexpr int ICP_QPB = ICP_BLOCK / KNN_G;        // features per workgroup of lvi_debug_residuals' kernel
 
-// round-to-nearest-even of |x| < 2^51 to an integer with one f64 add (as in lvi_voxel.hip)
-__device__ __forceinline__ long long d2ll_rn_small_icp(double x)
-{
-    const double M = 6755399441055744.0;                            // 2^52 + 2^51
-    return __double_as_longlong(x + M) - __double_as_longlong(M);
-}
 // exact fixed point of one partial sum: v = coarse 2^-16 + fine 2^-60, |v| < 2^45 (beyond: saturated)
 __device__ __forceinline__ void fx_split(double v, long long& coarse, long long& fine)
 {
     v = fmin(fmax(v, -3.5184372088832e13), 3.5184372088832e13);                 // +-2^45
     const double c = rint(ldexp(v, 16));
     coarse = (long long)c;
-    fine = d2ll_rn_small_icp(ldexp(v - ldexp(c, -16), 60));                      // |v - c 2^-16| <= 2^-17: the product is below 2^44
+    fine = d2ll_rn_small(ldexp(v - ldexp(c, -16), 60));                      // |v - c 2^-16| <= 2^-17: the product is below 2^44
 }
 
 // One launch = one Gauss-Newton iteration of every scan of the batch (blockIdx.z): the end of the PREVIOUS iteration (solve,
@@ -1647,28 +1640,27 @@ void stage_map_build(const Slots& sl)
         LVI_HIP(hipEventRecord(d.evMain, d.ctx.stream));
         LVI_HIP(hipStreamWaitEvent(cx.stream, d.evMain, 0));
     }
-    const bool cache_plan = d.P.map_plan_cache != 0;
     // map_plan_cache = 1: bbox of the raw map, per-bin counts and partition offsets are taken once, when the map was (re)written (PCL's
     // getMinMax3D is a pure function of the unchanged input).  Default (0): every re-voxelisation takes them again, per slot, as
     // the reference's VoxelGrid::filter does for every scan (mapOptimization.cpp:958-965) — in one pass (vb_plan).
-    if (cache_plan && (!d.voxMap.bbox_cached || (!d.voxMap.hist_cached && voxel_resolve_mode(d.voxMap) == VOX_BINNED))) {      // (AUTO: the first build of a plan is sorted)
+    // d.map_plan advances HERE, where the stages are enqueued (or captured), never when a captured sequence is replayed:
+    // lvi_scan_replay_enqueue keys its graph on the schedule that follows from it.
+    if (d.P.map_plan_cache && (!d.map_plan.bbox || (!d.map_plan.counts && voxel_resolve_mode(d.voxMap) == VOX_BINNED))) {      // (AUTO: the first build of a plan is sorted)
         d.voxMap.n_host[0] = d.n_map_corner; d.voxMap.n_host[1] = d.n_map_surf; d.voxMap.use_n_host = true;
-        voxel_bbox_pass(cx, d.voxMap, "map", (double)d.n_map_corner + (double)d.n_map_surf);
-        d.voxMap.bbox_cached = true;
+        d.map_plan.counts = voxel_bbox_pass(cx, d.voxMap, "map", (double)d.n_map_corner + (double)d.n_map_surf);
+        d.map_plan.bbox = true;
     }
-    // raw map counts are host-known here; the voxel plan wants them in device memory
     const VoxelPlan* plans[MAX_BATCH];
+    VoxPlanState st[MAX_BATCH];
     for (int z = 0; z < sl.n; z++) {
         LidarDev& q = sl[z];
         q.n_map_corner = d.n_map_corner; q.n_map_surf = d.n_map_surf;
-        q.voxMap.n_host[0] = d.n_map_corner; q.voxMap.n_host[1] = d.n_map_surf; q.voxMap.use_n_host = true;       // instead of a 1-thread launch writing d_dyn
-        q.voxMap.plan_per_run = !cache_plan;
-        q.voxMap.bbox_cached = cache_plan; q.voxMap.hist_cached = cache_plan && d.voxMap.hist_cached;
-        plans[z] = &q.voxMap;
+        q.voxMap.n_host[0] = d.n_map_corner; q.voxMap.n_host[1] = d.n_map_surf; q.voxMap.use_n_host = true;       // raw map counts are host-known here: kernel arguments instead of a 1-thread launch writing d_dyn
+        plans[z] = &q.voxMap; st[z] = map_vox_state(d, q.voxMap);
         q.have_map = true;
     }
     const double n = ((double)d.n_map_corner + (double)d.n_map_surf) * sl.n;
-    voxel_downsample_batch(cx, plans, sl.n, "map", n);
+    voxel_downsample_batch(cx, plans, st, sl.n, "map", n);
     stage_map_index(sl, cx);
     if (forked) {
         LVI_HIP(hipEventRecord(d.evMap, cx.stream));
@@ -1676,6 +1668,14 @@ void stage_map_build(const Slots& sl)
     }
 }
 void stage_map_build(LidarDev& d) { stage_map_build(OneSlot(d).s); }
+
+VoxPlanState map_vox_state(const LidarDev& owner, const VoxelPlan& slot_plan)
+{
+    const bool cache = owner.P.map_plan_cache != 0;
+    VoxPlanState st = voxel_plan_state(slot_plan);
+    st.per_run = !cache; st.bbox_valid = cache && owner.map_plan.bbox; st.counts_valid = cache && owner.map_plan.counts;
+    return st;
+}
 
 // the replacement of the two KdTreeFLANN::setInputCloud calls (mapOptimization.cpp:1322-1323) over every slot's DS map
 void stage_map_index(const Slots& sl, const Ctx& cx)
@@ -1701,7 +1701,8 @@ void kf_matrix(const float* T, float M[12])
 
 // f-4, incremental form.  The key list of this scan against the keyframes the tables already hold: whole keyframes enter
 // (+1) or leave (-1), with multiplicity (the reference's list may name a key twice, :921-927); then the live voxels are
-// emitted for the current bounding box and indexed.  Everything is enqueued on the main stream; one 16-byte read tells
+// emitted for the current bounding box and indexed.  Everything is enqueued on the handle's second stream (the main one under
+// map_on_main_stream), beside the scan-side stages; one 12-byte read tells
 // the host whether the device accepted (range, table size, PCL's overflow rule) — a sequential node reads the pose of
 // every scan anyway.
 bool stage_map_update(LidarDev& d, const int32_t* keys, int n_keys)
@@ -1774,7 +1775,7 @@ bool stage_map_update(LidarDev& d, const int32_t* keys, int n_keys)
     if (m.h_status[0] != 0) { d.inc_ready = false; return false; } // the tables are rebuilt next time; this list goes the full way
     d.inc_ready = true;
     d.have_map = true; d.have_map_raw = false;                     // no fused raw cloud exists in this form
-    d.voxMap.bbox_cached = false;
+    d.map_plan.invalidate();
     return true;
 }
 
@@ -1829,7 +1830,7 @@ void stage_map_assemble(LidarDev& d, const int32_t* keys, int n_keys)
         kf_assemble_launch(d.ctx, d.d_kfSeg, t.n, t.maxn, d.kfPool, d.mapCornerRaw, d.mapSurfRaw, (double)t.off[0] + t.off[1]);
     }
     d.n_map_corner = t.off[0]; d.n_map_surf = t.off[1]; d.have_map_raw = true;
-    d.voxMap.bbox_cached = false;
+    d.map_plan.invalidate();
 }
 
 void set_pose_init(const Slots& sl, const float* p, bool clear_status)
@@ -1888,8 +1889,7 @@ void stage_scan_match_enqueue(const Slots& sl, const lvi_imu_hint* imu, void* d_
     const int it_last = it_end < 0 ? a.max_iters : std::min(it_end, a.max_iters);
     const int ext_cap_l = gn_grid_features(sl);
     for (int it = it_begin; it < it_last; it++) {
-        // (the grid covers ext_cap features; the ~1 200 workgroups beyond the actual count exit at once — measured: launching
-        // exactly the occupied 360 instead changes nothing)
+        // (the grid covers gn_grid_features(): the features of the last finished matches plus a margin, the capacity while none reported)
         // iteration 0 searches the unit ball; later iterations search the (much smaller) ball of the previous neighbours, where
         // the per-lane fixed cost dominates: fewer lanes per feature (d.icp_g1).  The solve and the pose update of an iteration run at
         // the head of the NEXT launch, in every workgroup: ONE launch per Gauss-Newton iteration, no workgroup waits for another.

@@ -40,7 +40,7 @@ struct Submap {
     void filter(const Ctx& ctx, int n, const char* tag)
     {
         vox.n_host[0] = n; vox.use_n_host = true;
-        voxel_downsample_batch(ctx, vox, tag, n);
+        vox.last_mode = voxel_downsample_batch(ctx, vox, tag, n).mode;
     }
 };
 

@@ -112,6 +112,12 @@ struct LidarDev {
     lvi_pt *mapCornerOwn = nullptr, *mapSurfOwn = nullptr;     // slot 0: the handle's own raw-map memory (mapCornerRaw / mapSurfRaw point elsewhere while lvi_map_share is in force)
     int n_map_corner = 0, n_map_surf = 0;
     VoxelPlan voxMap;                                      // 2 segments
+    // slot 0: what voxel_bbox_pass took of the raw map's CURRENT contents (map_plan_cache = 1).  Whatever rewrites or rebinds
+    // the raw map calls invalidate(); stage_map_build tells every slot's run through its VoxPlanState (map_vox_state)
+    struct RawMapPlan {
+        bool bbox = false, counts = false;                 // bbox partial records / per-bin counts and prefixes are valid
+        void invalidate() { bbox = counts = false; }
+    } map_plan;
     GridIndex grid[2];
 
     // ---- generic one-call voxel (lvi_voxel_downsample)
@@ -183,6 +189,7 @@ void stage_extract(LidarDev& d);
 void stage_downsample(LidarDev& d);
 // lvi_icp.hip
 void stage_map_build(LidarDev& d);
+VoxPlanState map_vox_state(const LidarDev& owner, const VoxelPlan& slot_plan);   // of one slot's next map rebuild; owner = slot 0 (policy, validity)
 void join_map(LidarDev& d);                                // make the main stream wait for a pending map build
 void mark_map_deps(LidarDev& d);                           // record: a later map update on the second stream waits for everything enqueued on the main stream so far
 void set_pose_init(LidarDev& d, const float pose_init[6]);  // enqueue: d_pose_init <- pose_init

@@ -1098,7 +1098,7 @@ void stage_extract(const Slots& sl)
     if (std::min(d.P.Horizon_SCAN, n_max) / 6 + 12 > FEAT_SEG_CAP)
         LVI_LAUNCH(cx, "feat_sector_big", 8.0 * n, hipLaunchKernelGGL(feat_sector_big_kernel, dim3(d.P.N_SCAN, 1, sl.n), dim3(FEAT_THREADS), 0, cx.stream, B));
     LVI_LAUNCH(cx, "feat_finalize", 0, hipLaunchKernelGGL(feat_finalize_kernel, dim3(1, 1, sl.n), dim3(256), 0, cx.stream, B));
-    voxel_downsample_batch(cx, plans, sl.n, "ring", n);
+    voxel_downsample_batch(cx, plans, nullptr, sl.n, "ring", n);
 }
 
 void stage_downsample(const Slots& sl)
@@ -1106,7 +1106,7 @@ void stage_downsample(const Slots& sl)
     const VoxelPlan* plans[MAX_BATCH];
     double n = 0;
     for (int z = 0; z < sl.n; z++) { plans[z] = &sl[z].voxScan; n += 0.4 * sl[z].n_raw; }
-    voxel_downsample_batch(sl.first().ctx, plans, sl.n, "scan", n);
+    voxel_downsample_batch(sl.first().ctx, plans, nullptr, sl.n, "scan", n);
 }
 
 void stage_organize(LidarDev& d) { stage_organize(OneSlot(d).s); }

@@ -1,15 +1,23 @@
 // pcl::VoxelGrid<PointXYZI>::applyFilter for gfx950.
 //
-// Per batch, all segments at once (blockIdx.y = segment), nothing returns to the host:
-//   vox_minmax (bbox partials per workgroup) → vox_setup (grid dims, overflow rule, key width, bins,
-//   fixed-point scales), then one of
+// Per batch, all segments at once (blockIdx.y = segment), nothing returns to the host.  A run is: the bounding box, vox_setup
+// (grid dims, overflow rule, key width, bins, fixed-point scales), then one of two realisations with the same bits:
 //   SORTED: vox_keys (i32 voxel idx per point, exact PCL arithmetic, no FMA) → stable radix sort of
 //           (idx, point index) → vox_heads_* (ordered compaction of the first entry of every distinct
 //           idx) → vox_centroid (gathers the voxel's points);
-//   BINNED: vb_hist → vb_scan → vb_scatter (partition of the POINTS into bins of consecutive idx,
-//           LDS histogram + one global reservation per occupied bin and tile) → vb_accum (one
-//           workgroup per bin, LDS-resident accumulators, ordered compaction of the occupied
-//           voxels) → vb_outscan → vb_copy.
+//   BINNED: a partition of the POINTS into bins of consecutive idx → vb_accum (one workgroup per bin,
+//           LDS-resident accumulators, ordered compaction of the occupied voxels) → vb_merge → vb_outscan → vb_copy.
+// Where the bounding box comes from and how a BINNED run partitions is the run's VoxSchedule (lvi_vox_schedule.hpp),
+// computed once on the host from the VoxPlanState of every slot:
+//   MINMAX + RESERVE          vox_minmax → vox_setup → vb_hist → vb_scan → vb_scatter: LDS histogram + one global reservation
+//                             per occupied bin and tile.  Every plan but the raw local map (ring, scan, depth, Submap).
+//   WITH_PLAN + DET_PER_RUN   vb_plan (bbox AND per-(workgroup, bin) counts under the previous run's geometry, one pass) →
+//                             vox_setup (validates them) → vb_hist_w (re-takes them if the geometry moved) → vb_colscan →
+//                             vb_scan → vb_scatter_det: contiguous ranges, no global atomics.  The raw local map by default.
+//   CACHED + DET_CACHED       vox_setup → vb_scan → vb_scatter_det on the records and counts voxel_bbox_pass (vox_minmax →
+//                             vox_setup → vb_hist_w → vb_colscan) left when the map was written.  The raw local map under
+//                             map_plan_cache; CACHED + RESERVE / the sort while the counts are not taken yet.
+// SORTED runs take MINMAX or CACHED and no partition.
 // Voxel idx, voxel set and output order are PCL's, bit for bit.  The centroid is the exact mean of the
 // voxel's points in fixed point (integer sums, so independent of visiting order and identical in both
 // paths), rounded once to f32; PCL sums in f32 in the order its unstable sort leaves the points, which
@@ -68,6 +76,36 @@ __device__ __forceinline__ int seg_len(const VoxArgs& a, int s)
     return n < 0 ? 0 : (n > a.seg_cap ? a.seg_cap : n);
 }
 
+// Workgroup (256 threads) reduction of a bbox pass to ONE partial record per workgroup; vox_setup folds the records.  (Atomics on
+// the seven bbox words serialise: ~15 ns each, 0.1 ms for a 5M-point map with 1024 workgroups.)  Every thread calls
+// vox_box_wave_partials, then — after a workgroup barrier — thread 0 stores the record: min xyz, max xyz, count, min / max intensity.
+struct VoxBoxFold { float smn[4][4], smx[4][4]; int scnt[4]; };
+__device__ __forceinline__ void vox_box_wave_partials(VoxBoxFold& F, float mn[3], float mx[3], float imn, float imx, int cnt)
+{
+    cnt = wave_sum(cnt);
+#pragma unroll
+    for (int d = 0; d < 3; d++) { mn[d] = wave_min(mn[d]); mx[d] = wave_max(mx[d]); }
+    imn = wave_min(imn); imx = wave_max(imx);
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) { F.smn[wave_id()][d] = mn[d]; F.smx[wave_id()][d] = mx[d]; }
+        F.smn[wave_id()][3] = imn; F.smx[wave_id()][3] = imx;
+        F.scnt[wave_id()] = cnt;
+    }
+}
+__device__ __forceinline__ void vox_box_store(const VoxBoxFold& F, float* rec)
+{
+    int c = 0;
+    float lo[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, hi[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int w = 0; w < 4; w++) {
+        c += F.scnt[w];
+#pragma unroll
+        for (int d = 0; d < 4; d++) { lo[d] = fminf(lo[d], F.smn[w][d]); hi[d] = fmaxf(hi[d], F.smx[w][d]); }
+    }
+    rec[0] = lo[0]; rec[1] = lo[1]; rec[2] = lo[2]; rec[3] = hi[0]; rec[4] = hi[1]; rec[5] = hi[2];
+    rec[6] = __int_as_float(c); rec[7] = lo[3]; rec[8] = hi[3];
+}
+
 __global__ __launch_bounds__(256) void vox_minmax_kernel(Batch<VoxArgs> B_)
 {
     const VbBlock k = vb_block(B_.a[0].sx);
@@ -98,33 +136,10 @@ __global__ __launch_bounds__(256) void vox_minmax_kernel(Batch<VoxArgs> B_)
             cnt++;
         }
     }
-    // workgroup reduction to one partial record per workgroup; vox_setup folds the records.  (Atomics on the
-    // seven bbox words serialise: ~15 ns each, 0.1 ms for a 5M-point map with 1024 workgroups.)
-    __shared__ float smn[4][4], smx[4][4];
-    __shared__ int scnt[4];
-    cnt = wave_sum(cnt);
-#pragma unroll
-    for (int d = 0; d < 3; d++) { mn[d] = wave_min(mn[d]); mx[d] = wave_max(mx[d]); }
-    imn = wave_min(imn); imx = wave_max(imx);
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) { smn[wave_id()][d] = mn[d]; smx[wave_id()][d] = mx[d]; }
-        smn[wave_id()][3] = imn; smx[wave_id()][3] = imx;
-        scnt[wave_id()] = cnt;
-    }
+    __shared__ VoxBoxFold F;
+    vox_box_wave_partials(F, mn, mx, imn, imx, cnt);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int c = 0;
-        float lo[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, hi[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        for (int w = 0; w < 4; w++) {
-            c += scnt[w];
-#pragma unroll
-            for (int d = 0; d < 4; d++) { lo[d] = fminf(lo[d], smn[w][d]); hi[d] = fmaxf(hi[d], smx[w][d]); }
-        }
-        float* rec = a.mmPartial + ((size_t)s * a.nblk_mm + k.w) * 12;
-        rec[0] = lo[0]; rec[1] = lo[1]; rec[2] = lo[2]; rec[3] = hi[0]; rec[4] = hi[1]; rec[5] = hi[2];
-        rec[6] = __int_as_float(c); rec[7] = lo[3]; rec[8] = hi[3];
-    }
+    if (threadIdx.x == 0) vox_box_store(F, a.mmPartial + ((size_t)s * a.nblk_mm + k.w) * 12);
 }
 
 // fixed-point scales of the centroid sums (VoxGrid): from the leaf size and the intensity range only
@@ -406,13 +421,7 @@ __global__ __launch_bounds__(256) void vox_heads_assign_kernel(Batch<VoxArgs> B_
 }
 
 // Fixed-point image of one coordinate relative to its voxel's own origin / the exact mean back in f32 (VoxGrid, lvi_voxel.hpp)
-// round-to-nearest-even of |x| < 2^51 to an integer: one f64 add (the sum's ulp is 1) instead of the ~20 instructions of the
-// general f64 -> i64 conversion, which gfx950 does not have; the same value for every such x
-__device__ __forceinline__ long long d2ll_rn_small(double x)
-{
-    const double M = 6755399441055744.0;                            // 2^52 + 2^51
-    return __double_as_longlong(x + M) - __double_as_longlong(M);
-}
+// (d2ll_rn_small, lvi_dev.hpp: round to nearest even with one f64 add)
 __device__ __forceinline__ unsigned long long fx_xyz(float v, int cell, double leaf, int k)
 {
     return (unsigned long long)d2ll_rn_small(ldexp((double)v - (double)cell * leaf, k));        // |.| < 2^38 (vox_fx_setup); two's complement: sums wrap correctly
@@ -692,33 +701,12 @@ __global__ __launch_bounds__(256) void vb_plan_kernel(Batch<VoxArgs> B_)
         }
     }
     // bbox partial record of this workgroup (vox_setup folds the records; those of ranges beyond the input stay empty)
-    __shared__ float smn[4][4], smx[4][4];
-    __shared__ int scnt[4];
-    c = wave_sum(c);
-#pragma unroll
-    for (int d = 0; d < 3; d++) { mn[d] = wave_min(mn[d]); mx[d] = wave_max(mx[d]); }
-    imn = wave_min(imn); imx = wave_max(imx);
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) { smn[wave_id()][d] = mn[d]; smx[wave_id()][d] = mx[d]; }
-        smn[wave_id()][3] = imn; smx[wave_id()][3] = imx;
-        scnt[wave_id()] = c;
-    }
+    __shared__ VoxBoxFold F;
+    vox_box_wave_partials(F, mn, mx, imn, imx, c);
     if (miss) smiss = 1;
     __syncthreads();
     if (threadIdx.x == 0) {
-        int cc = 0;
-        float lo[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, hi[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        for (int q = 0; q < 4; q++) {
-            cc += scnt[q];
-#pragma unroll
-            for (int d = 0; d < 4; d++) { lo[d] = fminf(lo[d], smn[q][d]); hi[d] = fmaxf(hi[d], smx[q][d]); }
-        }
-        if (w < a.nblk_mm) {                        // (a range that holds points always has w < nblk_mm)
-            float* rec = a.mmPartial + ((size_t)s * a.nblk_mm + w) * 12;
-            rec[0] = lo[0]; rec[1] = lo[1]; rec[2] = lo[2]; rec[3] = hi[0]; rec[4] = hi[1]; rec[5] = hi[2];
-            rec[6] = __int_as_float(cc); rec[7] = lo[3]; rec[8] = hi[3];
-        }
+        if (w < a.nblk_mm) vox_box_store(F, a.mmPartial + ((size_t)s * a.nblk_mm + w) * 12);       // (a range that holds points always has w < nblk_mm)
         if (w + VB_WG < a.nblk_mm) (a.mmPartial + ((size_t)s * a.nblk_mm + w + VB_WG) * 12)[6] = __int_as_float(0);   // records another realisation's bbox pass may have left
         if (smiss && i0 < i1) atomicOr(&a.planMiss[s], 1);
         if (!spec && w == 0) atomicOr(&a.planMiss[s], 1);
@@ -1024,8 +1012,6 @@ struct VbLight {
     unsigned long long sx[VB_LIGHT], sy[VB_LIGHT], sz[VB_LIGHT], si[VB_LIGHT];
     unsigned cn[VB_LIGHT]; unsigned short cell[VB_LIGHT];
 };
-// LDS written by some lanes of a wavefront is read by others: order the accesses (a wavefront's LDS operations complete in order)
-__device__ __forceinline__ void wave_lds_sync() { __threadfence_block(); __builtin_amdgcn_wave_barrier(); }
 
 // (the second role of the workgroups of vb_accum_kernel: called by all 256 threads, after a workgroup barrier)
 __device__ __forceinline__ void vb_light_items(const VoxArgs& a, int s, const VoxGrid& g, VbLight* LW)
@@ -1047,7 +1033,7 @@ __device__ __forceinline__ void vb_light_items(const VoxArgs& a, int s, const Vo
         const int p0 = bs[b], p1 = bs[b + 1];
         const unsigned kbase = (unsigned)b << sh;
         if (ln < 16) L.bm[ln] = 0ull;
-        wave_lds_sync();
+        wave_lds_fence();
         lvi_pt p[PP]; unsigned c[PP]; bool ok[PP]; unsigned long long v[PP][4];
 #pragma unroll
         for (int u = 0; u < PP; u++) { const int i = p0 + ln + 64 * u; ok[u] = i < p1; p[u] = pts[min(i, p1 - 1)]; }      // p0 < p1 for a listed bin
@@ -1056,13 +1042,13 @@ __device__ __forceinline__ void vb_light_items(const VoxArgs& a, int s, const Vo
             c[u] = (vox_fx_point(f, p[u], v[u]) - kbase) & (unsigned)(VB_TAB - 1);
             if (ok[u]) atomicOr(&L.bm[c[u] >> 6], 1ull << (c[u] & 63u));
         }
-        wave_lds_sync();
+        wave_lds_fence();
         const int pc = ln < 16 ? __popcll(L.bm[ln]) : 0;
         const int incl = wave_incl_scan(pc);
         if (ln < 16) L.base[ln] = (unsigned)(incl - pc);
         const int nd = __shfl(incl, 15, 64);            // occupied cells of the bin (<= its points <= VB_LIGHT)
         for (int r = ln; r < nd; r += 64) { L.sx[r] = 0ull; L.sy[r] = 0ull; L.sz[r] = 0ull; L.si[r] = 0ull; L.cn[r] = 0u; }
-        wave_lds_sync();
+        wave_lds_fence();
 #pragma unroll
         for (int u = 0; u < PP; u++) {
             if (!ok[u]) continue;
@@ -1072,14 +1058,14 @@ __device__ __forceinline__ void vb_light_items(const VoxArgs& a, int s, const Vo
             atomicAdd(&L.cn[slot], 1u);
             L.cell[slot] = (unsigned short)c[u];        // every point of the cell writes the same value
         }
-        wave_lds_sync();
+        wave_lds_fence();
         for (int r = ln; r < nd; r += 64) {
             const unsigned key = kbase + (unsigned)L.cell[r];
             const unsigned m = L.cn[r];
             stg[p0 + r] = fx_centroid(g, key, L.sx[r], L.sy[r], L.sz[r], L.si[r], m); skc[p0 + r] = make_uint2(key, m);
         }
         if (ln == 0) a.binVox[(size_t)s * VB_NB + b] = nd;
-        wave_lds_sync();
+        wave_lds_fence();
     }
 }
 
@@ -1389,6 +1375,8 @@ __global__ __launch_bounds__(VOX_TINY) void vox_tiny_kernel(VoxTinyArgs a)
 
 }  // namespace
 
+// every field of the plan, as it is.  The three that depend on the run's schedule (plan_spec, binCountCached, sx) start as "nothing
+// per-run, nothing cached, blockIdx.z = slot"; VoxRun::set_sched_args is the one place that sets them.
 static VoxArgs make_args(const VoxelPlan& p)
 {
     return VoxArgs{p.d_static, p.d_dyn, p.d_grid, p.d_n, p.d_nbits, p.sort.keysA, p.sort.valsA, p.sort.keysB, p.sort.valsB,
@@ -1396,7 +1384,7 @@ static VoxArgs make_args(const VoxelPlan& p)
                    p.d_binCount, p.d_binStart, p.d_cursor, p.d_binVox, p.d_binOut, p.d_bucketed, p.d_staging, p.d_stagingKC, p.h_ncells,
                    p.d_chunkStart, p.d_multiStart, p.d_chunkBin, p.max_chunks, p.d_lightBin, p.d_multiOwner, p.d_chunkTabV, p.d_chunkTabC, p.max_multi,
                    {p.n_host[0], p.n_host[1], p.n_host[2], p.n_host[3]}, (p.use_n_host && p.nseg <= 4) ? 1 : 0,
-                   {p.n_dev[0], p.n_dev[1], p.n_dev[2], p.n_dev[3]}, p.bin_pts, p.bin_max, ((p.plan_per_run && p.d_wprefix) || (p.bbox_cached && p.hist_cached)) ? p.d_binCountCached : nullptr, p.d_binCountCached, p.d_planMiss, (p.plan_per_run && p.d_wprefix) ? 1 : 0, p.d_wprefix, VB_CH, 1};
+                   {p.n_dev[0], p.n_dev[1], p.n_dev[2], p.n_dev[3]}, p.bin_pts, p.bin_max, nullptr, p.d_binCountCached, p.d_planMiss, 0, p.d_wprefix, VB_CH, 1};
 }
 
 void VoxelPlan::set_static(const Ctx& ctx, const VoxSegStatic* host_segs)
@@ -1674,32 +1662,11 @@ void incmap_emit(const Ctx& ctx, const IncMap& m, int n_active, const float leaf
     LVI_LAUNCH(ctx, "inc_out", 0, hipLaunchKernelGGL(inc_out_kernel, gk, dim3(256), 0, ctx.stream, a));
 }
 
-// What depends on the plan's INPUT alone and is produced where the input is written (upload / assembly) instead of once per
-// re-voxelisation: the bbox partial records and — the grid geometry following from the bbox — the points per bin.
 void voxel_tiny(const Ctx& ctx, const lvi_pt* in_pinned, int n, float leaf, int seg_cap, int bin_pts, int bin_max, lvi_pt* out_pinned, int* hdr_pinned,
                 int* cells_pinned, int* counts_pinned, int* keys_pinned)
 {
     VoxTinyArgs a{in_pinned, n, leaf, seg_cap, bin_pts, bin_max, out_pinned, hdr_pinned, cells_pinned, counts_pinned, keys_pinned};
     LVI_LAUNCH(ctx, "vox_tiny", 32.0 * n, hipLaunchKernelGGL(vox_tiny_kernel, dim3(1), dim3(VOX_TINY), 0, ctx.stream, a));
-}
-
-void voxel_bbox_pass(const Ctx& ctx, const VoxelPlan& p, const char* tag, double n_hint)
-{
-    Batch<VoxArgs> B;
-    B.a[0] = make_args(p);
-    B.a[0].binCountCached = nullptr;
-    for (int z = 1; z < MAX_BATCH; z++) B.a[z] = B.a[0];
-    char nm[3][48];
-    snprintf(nm[0], sizeof(nm[0]), "vox_minmax/%s", tag); snprintf(nm[1], sizeof(nm[1]), "vox_setup/%s", tag); snprintf(nm[2], sizeof(nm[2]), "vb_hist/%s", tag);
-    LVI_LAUNCH(ctx, nm[0], 16.0 * n_hint, hipLaunchKernelGGL(vox_minmax_kernel, dim3(p.nblk_mm, p.nseg, 1), dim3(256), 0, ctx.stream, B));
-    p.hist_cached = false;
-    if (voxel_resolve_mode(p) == VOX_BINNED && p.d_binCountCached) {
-        LVI_LAUNCH(ctx, nm[1], 0, hipLaunchKernelGGL(vox_setup_kernel, dim3(p.nseg, 1, 1), dim3(64), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, nm[2], 16.0 * n_hint, hipLaunchKernelGGL(vb_hist_w_kernel, dim3(VB_WG, p.nseg, 1), dim3(256), 0, ctx.stream, B));
-        hipLaunchKernelGGL(vb_colscan_kernel, dim3(VB_NB / 16, p.nseg, 1), dim3(256), 0, ctx.stream, B);
-        LVI_HIP(hipGetLastError());
-        p.hist_cached = true;
-    }
 }
 
 int voxel_resolve_mode(const VoxelPlan& p)
@@ -1715,103 +1682,161 @@ int voxel_resolve_mode(const VoxelPlan& p)
     return mode;
 }
 
-void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan& p, const char* tag, double n_hint)
+VoxPlanState voxel_plan_state(const VoxelPlan& p)
 {
-    const VoxelPlan* one = &p;
-    voxel_downsample_batch(ctx, &one, 1, tag, n_hint);
+    return VoxPlanState{voxel_resolve_mode(p), p.d_wprefix && p.d_binCountCached, false, false, false, p.use_n_host, p.slot_major};
 }
 
-// S plans of identical shape (the same plan of S batch slots), one launch sequence: blockIdx.z = slot; the passes over the raw
-// map, which every slot reads from the same addresses, fold the slot into blockIdx.x instead (vb_block)
-void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, int S, const char* tag, double n_hint)
-{
-    const VoxelPlan& p = *plans[0];
-    // the realisation must be the same for the whole launch: sorted as soon as one slot asks for it
-    int mode = VOX_BINNED;
-    for (int z = 0; z < S; z++) if (voxel_resolve_mode(*plans[z]) == VOX_SORTED) mode = VOX_SORTED;
-    if (mode == VOX_SORTED && S > 1) {
-        // the radix sort is not batched over slots (sparse outdoor grids only): slot by slot
-        for (int z = 0; z < S; z++) {
-            const int keep = plans[z]->mode;
-            const_cast<VoxelPlan*>(plans[z])->mode = VOX_SORTED;
-            voxel_downsample_batch(ctx, plans + z, 1, tag, n_hint / S);
-            const_cast<VoxelPlan*>(plans[z])->mode = keep;
-        }
-        return;
-    }
+namespace {
+
+// One launch sequence over S plans of identical shape: the argument blocks, the schedule they were set for, and the stages the
+// schedule is made of.  blockIdx.z = slot; the passes over the raw map, which every slot reads from the same addresses, fold
+// the slot into blockIdx.x instead (vb_block).
+struct VoxRun {
+    const Ctx& ctx; const VoxelPlan& p; const int S; const char* tag; const double n_hint; const VoxSchedule sc;
     Batch<VoxArgs> B;
-    static const int ch_env = getenv("LVI_VB_CH") ? atoi(getenv("LVI_VB_CH")) : 0;
-    const int ch = ch_env >= VB_CH && ch_env <= 32768 ? ch_env : VB_CH;
-    for (int z = 0; z < S; z++) { B.a[z] = make_args(*plans[z]); B.a[z].ch = ch; plans[z]->last_mode = mode; }
-    for (int z = S; z < MAX_BATCH; z++) B.a[z] = B.a[0];
-    const VoxArgs& a = B.a[0];
-    // grid of a pass over the raw map (vb_block): the slots folded into x when the plans ask for it and the decode's groups fit
-    bool raw_map = S > 1;
-    for (int z = 0; z < S; z++) raw_map = raw_map && plans[z]->slot_major && plans[z]->use_n_host;
-    auto slot_grid = [&](int nx) {
-        const int sx = raw_map && nx % VB_XCD == 0 ? S : 1;
-        for (int z = 0; z < MAX_BATCH; z++) B.a[z].sx = sx;
-        return dim3(nx * sx, p.nseg, S / sx);
-    };
-    dim3 gs;                                            // (set in a statement of its own: B must hold sx before the launch copies it)
-    char nm[16][48];
-    const char* base[16] = {"vox_minmax", "vox_setup", "vox_keys", "vox_heads_count", "vox_heads_scan", "vox_heads_assign", "vox_centroid",
-                            "vb_hist", "vb_scan", "vb_scatter", "vb_accum", "vb_outscan", "vb_copy", "vb_merge", "vb_light", ""};
-    for (int i = 0; i < 15; i++) snprintf(nm[i], sizeof(nm[i]), "%s/%s", base[i], tag);
-    // the bbox pass is skipped when every plan of the batch holds the partial records of its (unchanged) input: the raw
-    // local map gets them where its points are touched anyway — upload / assembly — instead of once per re-voxelisation
-    bool cached = true, per_run = mode == VOX_BINNED;
-    for (int z = 0; z < S; z++) { cached = cached && plans[z]->bbox_cached; per_run = per_run && B.a[z].plan_spec != 0; }
-    if (per_run) {
-        // reference-faithful raw map: bbox + per-bin counts inside this run, one pass (vb_plan), validated by vox_setup
-        gs = slot_grid(VB_WG);
-        LVI_LAUNCH(ctx, "vb_plan/map", 16.0 * n_hint, hipLaunchKernelGGL(vb_plan_kernel, gs, dim3(256), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, nm[1], 0, hipLaunchKernelGGL(vox_setup_kernel, dim3(p.nseg, 1, S), dim3(64), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, "vb_hist_w/map", 0, hipLaunchKernelGGL(vb_hist_w_kernel, gs, dim3(256), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, "vb_colscan/map", 0, hipLaunchKernelGGL(vb_colscan_kernel, dim3(VB_NB / 16, p.nseg, S), dim3(256), 0, ctx.stream, B));
-    } else {
-        for (int z = 0; z < S; z++) B.a[z].plan_spec = 0;
-        gs = slot_grid(p.nblk_mm);
-        if (!cached) LVI_LAUNCH(ctx, nm[0], 16.0 * n_hint, hipLaunchKernelGGL(vox_minmax_kernel, gs, dim3(256), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, nm[1], 0, hipLaunchKernelGGL(vox_setup_kernel, dim3(p.nseg, 1, S), dim3(64), 0, ctx.stream, B));
+    char nm[48];
+
+    VoxRun(const Ctx& ctx_, const VoxelPlan* const* plans, int S_, const VoxSchedule& sc_, const char* tag_, double n_hint_)
+        : ctx(ctx_), p(*plans[0]), S(S_), tag(tag_), n_hint(n_hint_), sc(sc_)
+    {
+        static const int ch_env = getenv("LVI_VB_CH") ? atoi(getenv("LVI_VB_CH")) : 0;
+        for (int z = 0; z < S; z++) { B.a[z] = make_args(*plans[z]); B.a[z].ch = ch_env >= VB_CH && ch_env <= 32768 ? ch_env : VB_CH; }
+        for (int z = S; z < MAX_BATCH; z++) B.a[z] = B.a[0];
+        set_sched_args(1);
     }
-    if (mode == VOX_BINNED) {
-        const dim3 gt(div_up(p.seg_cap, VB_STILE), p.nseg, S);
-        const dim3 gb(std::max(512, std::min(div_up(p.seg_cap, 2048), VB_ACC_BLOCKS)), p.nseg, S);      // grid-stride over the bins (a workgroup per bin or two: a bin is three dependent steps)
-        const dim3 gh2(std::min(div_up(p.seg_cap, VB_TILE), 512), p.nseg, S);
-        bool hist_cached = true;
-        for (int z = 0; z < S; z++) hist_cached = hist_cached && B.a[z].binCountCached != nullptr;
-        if (!hist_cached) {
-            for (int z = 0; z < S; z++) B.a[z].binCountCached = nullptr;                  // all slots the same way
-            gs = slot_grid(gh2.x);
-            LVI_LAUNCH(ctx, nm[7], 16.0 * n_hint, hipLaunchKernelGGL(vb_hist_kernel, gs, dim3(256), 0, ctx.stream, B));
+    // what the kernels read of the schedule, the same in every block: vox_setup / vb_hist_w / vb_colscan ask plan_spec whether
+    // vb_plan ran, vb_scan takes its counts from binCountCached when set, vb_block unfolds sx slots from blockIdx.x
+    void set_sched_args(int sx)
+    {
+        for (int z = 0; z < MAX_BATCH; z++) {
+            B.a[z].plan_spec = sc.part == VOX_PART_DET_PER_RUN ? 1 : 0;
+            B.a[z].binCountCached = sc.part == VOX_PART_DET_PER_RUN || sc.part == VOX_PART_DET_CACHED ? B.a[z].binCountOut : nullptr;
+            B.a[z].sx = sx;
         }
-        LVI_LAUNCH(ctx, nm[8], 0, hipLaunchKernelGGL(vb_scan_kernel, dim3(p.nseg, 1, S), dim3(256), 0, ctx.stream, B));
-        gs = slot_grid(VB_WG);
-        if (hist_cached) LVI_LAUNCH(ctx, nm[9], 32.0 * n_hint, hipLaunchKernelGGL(vb_scatter_det_kernel, gs, dim3(256), 0, ctx.stream, B));
-        else LVI_LAUNCH(ctx, nm[9], 32.0 * n_hint, hipLaunchKernelGGL(vb_scatter_kernel, gt, dim3(256), 0, ctx.stream, B));
+    }
+    // grid of a pass over the raw map (vb_block): the slots folded into x when the schedule says so and the decode's groups fit.
+    // A statement of its own before the launch: B must hold sx before the launch copies it.
+    dim3 slot_grid(int nx)
+    {
+        const int sx = sc.fold_slots && nx % VB_XCD == 0 ? S : 1;
+        set_sched_args(sx);
+        return dim3(nx * sx, p.nseg, S / sx);
+    }
+    const char* name(const char* base) { snprintf(nm, sizeof(nm), "%s/%s", base, tag); return nm; }      // (LaunchScope copies it)
+#define VOX_LAUNCH(base, bytes, kernel, grid) LVI_LAUNCH(ctx, name(base), bytes, hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx.stream, B))
+    void setup() { LVI_LAUNCH(ctx, name("vox_setup"), 0, hipLaunchKernelGGL(vox_setup_kernel, dim3(p.nseg, 1, S), dim3(64), 0, ctx.stream, B)); }
+
+    // bbox partial records by a pass of their own (skipped when every plan holds those of its unchanged input), grid geometry
+    void bbox_and_setup()
+    {
+        const dim3 gs = slot_grid(p.nblk_mm);
+        if (sc.bbox == VOX_BBOX_MINMAX) VOX_LAUNCH("vox_minmax", 16.0 * n_hint, vox_minmax_kernel, gs);
+        setup();
+    }
+    // deterministic partition: per-(workgroup, bin) counts of every workgroup's contiguous range, their prefixes and the bins' totals
+    void det_counts(const char* hist_name, double hist_bytes)
+    {
+        const dim3 gs = slot_grid(VB_WG);
+        VOX_LAUNCH(hist_name, hist_bytes, vb_hist_w_kernel, gs);
+        VOX_LAUNCH("vb_colscan", 0, vb_colscan_kernel, dim3(VB_NB / 16, p.nseg, S));
+    }
+    // reference-faithful raw map: bbox + per-bin counts inside this run, in one pass under the previous run's geometry; vox_setup
+    // validates the counts and vb_hist_w takes them again (else returns at once) when the geometry moved
+    void plan_and_counts()
+    {
+        const dim3 gs = slot_grid(VB_WG);
+        VOX_LAUNCH("vb_plan", 16.0 * n_hint, vb_plan_kernel, gs);
+        setup();
+        det_counts("vb_hist_w", 0);
+    }
+    void reserve_counts()
+    {
+        const dim3 gs = slot_grid(std::min(div_up(p.seg_cap, VB_TILE), 512));
+        VOX_LAUNCH("vb_hist", 16.0 * n_hint, vb_hist_kernel, gs);
+    }
+    // bin offsets, the partition itself, then vb_accum … vb_copy
+    void binned_tail()
+    {
+        const dim3 gb(std::max(512, std::min(div_up(p.seg_cap, 2048), VB_ACC_BLOCKS)), p.nseg, S);      // grid-stride over the bins (a workgroup per bin or two: a bin is three dependent steps)
+        VOX_LAUNCH("vb_scan", 0, vb_scan_kernel, dim3(p.nseg, 1, S));
+        const dim3 gs = slot_grid(VB_WG);
+        if (sc.part == VOX_PART_RESERVE) VOX_LAUNCH("vb_scatter", 32.0 * n_hint, vb_scatter_kernel, dim3(div_up(p.seg_cap, VB_STILE), p.nseg, S));
+        else VOX_LAUNCH("vb_scatter", 32.0 * n_hint, vb_scatter_det_kernel, gs);
         // grid-stride over the chunks: at most ceil(n / VB_CH) + bins of them exist; a small plan (ring / scan grids: 64 bins) gets
         // a small grid — every workgroup of this kernel owns 40 KB of LDS, and thousands of idle ones cost 40 us of dispatch
         const dim3 ga(std::max(64, std::min(2 * div_up(p.seg_cap, VB_CH) + 64, 2048)), p.nseg, S);
         // 256 threads: 128 / 512 / 1024 measured 172 / 163 / 231 us instead of 136 for four slots of the 4.87 M-point map
-        LVI_LAUNCH(ctx, nm[10], 16.0 * n_hint, hipLaunchKernelGGL(vb_accum_kernel<256>, ga, dim3(256), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, nm[13], 0, hipLaunchKernelGGL(vb_merge_kernel, dim3(std::max(1, std::min(p.max_multi, VB_ACC_BLOCKS)), p.nseg, S), dim3(256), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, nm[11], 0, hipLaunchKernelGGL(vb_outscan_kernel, dim3(1, 1, S), dim3(256), 0, ctx.stream, B));
-        LVI_LAUNCH(ctx, nm[12], 0, hipLaunchKernelGGL(vb_copy_kernel, gb, dim3(256), 0, ctx.stream, B));
-        return;
+        VOX_LAUNCH("vb_accum", 16.0 * n_hint, vb_accum_kernel<256>, ga);
+        VOX_LAUNCH("vb_merge", 0, vb_merge_kernel, dim3(std::max(1, std::min(p.max_multi, VB_ACC_BLOCKS)), p.nseg, S));
+        VOX_LAUNCH("vb_outscan", 0, vb_outscan_kernel, dim3(1, 1, S));
+        VOX_LAUNCH("vb_copy", 0, vb_copy_kernel, gb);
     }
-    (void)a;
-    const dim3 gp(div_up(p.seg_cap, 256), p.nseg), gh(p.nblk_h, p.nseg);
-    LVI_LAUNCH(ctx, nm[2], 24.0 * n_hint, hipLaunchKernelGGL(vox_keys_kernel, gp, dim3(256), 0, ctx.stream, B));
-    radix_sort_pairs(ctx, p.sort, p.d_n, p.d_nbits, 4, tag, n_hint);
-    LVI_LAUNCH(ctx, nm[3], 4.0 * n_hint, hipLaunchKernelGGL(vox_heads_count_kernel, gh, dim3(256), 0, ctx.stream, B));
-    LVI_LAUNCH(ctx, nm[4], 0, hipLaunchKernelGGL(vox_heads_scan_kernel, dim3(1), dim3(256), 0, ctx.stream, B));
-    LVI_LAUNCH(ctx, nm[5], 4.0 * n_hint, hipLaunchKernelGGL(vox_heads_assign_kernel, gh, dim3(256), 0, ctx.stream, B));
-    const dim3 gc(std::max(1, std::min(div_up(p.seg_cap, 256 / 8), 8192)), p.nseg);
-    if (p.centroid_lanes >= 32)
-        LVI_LAUNCH(ctx, nm[6], 20.0 * n_hint, hipLaunchKernelGGL(vox_centroid_kernel<32>, gc, dim3(256), 0, ctx.stream, B));
-    else
-        LVI_LAUNCH(ctx, nm[6], 20.0 * n_hint, hipLaunchKernelGGL(vox_centroid_kernel<8>, gc, dim3(256), 0, ctx.stream, B));
+    void sorted_tail()                                   // S = 1
+    {
+        const dim3 gp(div_up(p.seg_cap, 256), p.nseg), gh(p.nblk_h, p.nseg);
+        VOX_LAUNCH("vox_keys", 24.0 * n_hint, vox_keys_kernel, gp);
+        radix_sort_pairs(ctx, p.sort, p.d_n, p.d_nbits, 4, tag, n_hint);
+        VOX_LAUNCH("vox_heads_count", 4.0 * n_hint, vox_heads_count_kernel, gh);
+        VOX_LAUNCH("vox_heads_scan", 0, vox_heads_scan_kernel, dim3(1));
+        VOX_LAUNCH("vox_heads_assign", 4.0 * n_hint, vox_heads_assign_kernel, gh);
+        const dim3 gc(std::max(1, std::min(div_up(p.seg_cap, 256 / 8), 8192)), p.nseg);
+        if (p.centroid_lanes >= 32) VOX_LAUNCH("vox_centroid", 20.0 * n_hint, vox_centroid_kernel<32>, gc);
+        else VOX_LAUNCH("vox_centroid", 20.0 * n_hint, vox_centroid_kernel<8>, gc);
+    }
+#undef VOX_LAUNCH
+};
+
+}  // namespace
+
+// What depends on the plan's INPUT alone and is produced where the input is written (upload / assembly) instead of once per
+// re-voxelisation: the bbox partial records and — the grid geometry following from the bbox — the points per bin.
+bool voxel_bbox_pass(const Ctx& ctx, const VoxelPlan& p, const char* tag, double n_hint)
+{
+    const VoxPlanState st = voxel_plan_state(p);
+    const VoxelPlan* one = &p;
+    VoxRun r(ctx, &one, 1, VoxSchedule{st.mode, VOX_BBOX_MINMAX, VOX_PART_NONE, false, false}, tag, n_hint);      // (nothing is partitioned here)
+    const dim3 gs = r.slot_grid(p.nblk_mm);
+    LVI_LAUNCH(ctx, r.name("vox_minmax"), 16.0 * n_hint, hipLaunchKernelGGL(vox_minmax_kernel, gs, dim3(256), 0, ctx.stream, r.B));
+    if (st.mode != VOX_BINNED || !st.det_tables) return false;
+    r.setup();
+    r.det_counts("vb_hist", 16.0 * n_hint);
+    return true;
+}
+
+VoxSchedule voxel_downsample_batch(const Ctx& ctx, const VoxelPlan& p, const char* tag, double n_hint)
+{
+    const VoxelPlan* one = &p;
+    return voxel_downsample_batch(ctx, &one, nullptr, 1, tag, n_hint);
+}
+
+VoxSchedule voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, const VoxPlanState* st, int S, const char* tag, double n_hint)
+{
+    VoxPlanState own[MAX_BATCH];
+    if (!st) { for (int z = 0; z < S; z++) own[z] = voxel_plan_state(*plans[z]); st = own; }
+    const VoxSchedule sc = vox_schedule(st, S);
+    if (sc.slot_by_slot) {
+        // the radix sort is not batched over slots (sparse outdoor grids only): every slot alone, the sorted realisation forced
+        for (int z = 0; z < S; z++) {
+            VoxPlanState one = st[z];
+            one.mode = VOX_SORTED;
+            voxel_downsample_batch(ctx, plans + z, &one, 1, tag, n_hint / S);
+        }
+        return sc;
+    }
+    VoxRun r(ctx, plans, S, sc, tag, n_hint);
+    switch (sc.bbox) {
+    case VOX_BBOX_WITH_PLAN: r.plan_and_counts(); break;           // (always with VOX_PART_DET_PER_RUN)
+    case VOX_BBOX_MINMAX:
+    case VOX_BBOX_CACHED: r.bbox_and_setup(); break;
+    }
+    switch (sc.part) {
+    case VOX_PART_NONE: r.sorted_tail(); break;
+    case VOX_PART_RESERVE: r.reserve_counts(); r.binned_tail(); break;
+    case VOX_PART_DET_CACHED:
+    case VOX_PART_DET_PER_RUN: r.binned_tail(); break;
+    }
+    return sc;
 }
 
 }  // namespace lvi

@@ -3,6 +3,7 @@
 // mapOptimization.cpp:987-999 and the corner+surf pair of :958-965 are one batch each).
 #pragma once
 #include "lvi_sort.hpp"
+#include "lvi_vox_schedule.hpp"
 
 namespace lvi {
 
@@ -58,7 +59,6 @@ constexpr int VB_LIGHT = 256;     // binned path: a bin of at most this many poi
 constexpr int VB_TAB = 1 << VB_CL_LOG;      // entries per compacted chunk table
 constexpr int VB_TABC = VB_TAB + 32;         // u32 words per chunk table: entries, then the entry count
 constexpr int VB_ACC_BLOCKS = 1024;
-enum VoxMode { VOX_AUTO = 0, VOX_SORTED = 1, VOX_BINNED = 2 };
 
 struct VoxelPlan {
     int nseg = 0, seg_cap = 0, nblk_h = 0;
@@ -97,15 +97,13 @@ struct VoxelPlan {
     unsigned* d_chunkTabC = nullptr;             // [nseg][max_multi][VB_TABC]: (cell << 16 | count) per entry, entry count at [VB_TAB]
     int max_multi = 0;
     unsigned long long* h_ncells = nullptr;   // pinned host, [nseg]: div_b product of the latest run (AUTO's hint)
-    mutable int last_mode = VOX_SORTED;       // what the latest voxel_downsample_batch enqueued
+    int last_mode = VOX_SORTED;               // the realisation of the latest run, stored by callers that serve voxel_debug_fetch
     int bin_pts = 2048, bin_max = 1024;       // binned path: points aimed at per bin, most bins (<= VB_NB)
-    unsigned* d_wprefix = nullptr;            // [nseg][VB_WG][VB_NB] per-(workgroup, bin) prefix of the deterministic partition, plans that cache only
-    unsigned* d_binCountCached = nullptr;     // [nseg][VB_NB] points per bin of the current input (voxel_bbox_pass), plans that cache only
-    mutable bool hist_cached = false;         // … valid (binned realisation was the resolved one when the pass ran)
-    bool plan_per_run = false;                // the raw local map in its reference-faithful form: bbox and per-bin counts are taken inside EVERY run (vb_plan: one
-                                              // pass for both, the histogram under the previous run's grid geometry, re-taken by vb_hist_w when the geometry moved)
+    // tables of the deterministic partition (the raw local map only).  Whether a run takes them itself or finds them valid is
+    // not the plan's to know: the caller says so in the VoxPlanState it passes (lvi_vox_schedule.hpp)
+    unsigned* d_wprefix = nullptr;            // [nseg][VB_WG][VB_WROW] per-(workgroup, bin) prefix
+    unsigned* d_binCountCached = nullptr;     // [nseg][VB_NB] points per bin of the current input (vb_colscan)
     int* d_planMiss = nullptr;                // [nseg] a point fell outside the previous geometry (vb_plan)
-    bool bbox_cached = false;                 // d_mmPartial holds the bbox partials of the CURRENT input (voxel_bbox_pass ran after the input was written)
     bool slot_major = true;                   // batch launches of the raw-map passes fold the slot into blockIdx.x (vb_block; LVI_VB_SLOT_ORDER=0: blockIdx.z = slot)
 
     template <class AR> void allocate(AR& ar, int nseg_, int seg_cap_, bool concat)
@@ -200,16 +198,23 @@ void incmap_emit(const Ctx& ctx, const IncMap& m, int n_active, const float leaf
 //           accumulates its voxels in LDS; ~2.5x less HBM traffic and 8 launches instead of 19 when the grid is
 //           compact (div_b product <= VB_NB << VB_CL_LOG); still correct, but sweeping each bin several times,
 //           when it is not.
-// AUTO enqueues BINNED when the previous run's grids (read from pinned host memory, no sync) had at most
-// 16.8 M cells (four sweeps per bin), SORTED for sparser ones.  d_dyn must have been written (on the same
+// AUTO resolves to BINNED when the previous run's grids (read from pinned host memory, no sync) had at most
+// 16.8 M cells (four sweeps per bin), to SORTED for sparser ones (voxel_resolve_mode).  Where the bounding box comes from
+// and which of the three partitions a BINNED run takes is vox_schedule's answer (lvi_vox_schedule.hpp) to the
+// VoxPlanState of every slot; the schedule that was enqueued is returned.  d_dyn must have been written (on the same
 // stream) by the producer.  n_hint: nominal total input points, for byte accounting only.
-void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan& plan, const char* tag, double n_hint);
-// the same plan of S batch slots (identical shapes) in ONE launch sequence, blockIdx.z = slot (raw-map passes: VoxelPlan::slot_major);
-// n_hint = points of all slots
-void voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, int S, const char* tag, double n_hint);
-// the bbox partial records of the plan's current input, as a pass of its own (sets nothing on the plan: the caller owns
-// bbox_cached and clears it whenever the input changes)
-void voxel_bbox_pass(const Ctx& ctx, const VoxelPlan& plan, const char* tag, double n_hint);
+//   st = null: voxel_plan_state of every plan — MINMAX, then RESERVE or the sort (ring, scan, depth, Submap plans);
+//   the raw local map passes its own states (stage_map_build): WITH_PLAN + DET_PER_RUN, or CACHED + DET_CACHED.
+// S plans of identical shape (the same plan of S batch slots) are ONE launch sequence, blockIdx.z = slot (raw-map passes
+// under VoxSchedule::fold_slots: the slot folded into blockIdx.x); n_hint = points of all slots.
+VoxSchedule voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, const VoxPlanState* st, int S, const char* tag, double n_hint);
+VoxSchedule voxel_downsample_batch(const Ctx& ctx, const VoxelPlan& plan, const char* tag, double n_hint);
+// what the plan itself tells about its next run: the resolved mode, the tables it owns, its lengths' source; not per-run, nothing valid
+VoxPlanState voxel_plan_state(const VoxelPlan& plan);
+// the bbox partial records of the plan's current input as a pass of its own, and — when the plan resolves to BINNED and owns
+// the tables — the per-bin counts of the deterministic partition.  Returns whether the counts were taken; the caller
+// owns both validity bits and clears them whenever the input changes.
+bool voxel_bbox_pass(const Ctx& ctx, const VoxelPlan& plan, const char* tag, double n_hint);
 // the realisation the next voxel_downsample_batch of this plan will enqueue (AUTO resolved from the previous batch's hint)
 int voxel_resolve_mode(const VoxelPlan& plan);
 // a cloud of at most VOX_TINY points, one workgroup, one launch, pinned host memory in and out (the node's key-pose grid)
