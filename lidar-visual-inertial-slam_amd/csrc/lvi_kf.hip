@@ -16,7 +16,7 @@
 // Everything but kf_norm is integer arithmetic (the BRIEF coordinates are one f32 addition and a truncation), so the
 // results equal tests/kfdesc_ref.py bit for bit.
 #include "lvi_mei.hpp"
-#include "../../include/lvi_kf.h"
+#include "lvi_kf_store.hpp"
 
 using namespace lvi;
 
@@ -253,6 +253,7 @@ struct Slot {
     int n_kp = 0, n_win = 0;
     float *kp_xy = nullptr, *kp_norm = nullptr, *win_xy = nullptr;
     ulonglong2 *kp_desc = nullptr, *win_desc = nullptr;
+    uint64_t generation = 0;               // bumped by every call that changes the slot (lvi_kf_store.hpp)
 };
 
 }  // namespace
@@ -298,6 +299,25 @@ namespace {
 Slot* slot_of(lvi_kf* h, int32_t slot) { return h && slot >= 0 && slot < h->S ? &h->slots[slot] : nullptr; }
 
 }  // namespace
+
+namespace lvi {
+
+bool kf_store_view(lvi_kf* h, KfStoreView* out)
+{
+    if (!h) return false;
+    out->device = h->device; out->max_keypoints = h->K; out->stream = h->stream;
+    return true;
+}
+
+bool kf_slot_view(lvi_kf* h, int32_t slot, KfSlotView* out)
+{
+    const Slot* s = slot_of(h, slot);
+    if (!s) return false;
+    out->valid = s->valid; out->n_kp = s->n_kp; out->kp_desc = s->kp_desc; out->generation = s->generation;
+    return true;
+}
+
+}  // namespace lvi
 
 extern "C" {
 
@@ -375,7 +395,7 @@ int32_t lvi_kf_describe(lvi_kf* h, int32_t slot, const uint8_t* img, int32_t w, 
         LVI_HIP(hipMemcpyAsync(h->d_in, h->h_in, h->off_img + (size_t)w * hgt, hipMemcpyHostToDevice, h->stream));
         const uint8_t* d_img = reinterpret_cast<const uint8_t*>(h->d_in + h->off_img);
         const float* d_win = reinterpret_cast<const float*>(h->d_in);
-        s->valid = false;
+        s->valid = false; s->generation++;
         const dim3 tiles(div_up(w, TILE_W), div_up(hgt, TILE_H));
         hipLaunchKernelGGL(kf_blur_kernel, tiles, dim3(256), 0, h->stream, d_img, h->d_blur, w, hgt);
         LVI_HIP(hipGetLastError());
@@ -437,7 +457,7 @@ int32_t lvi_kf_put(lvi_kf* h, int32_t slot, int32_t n_keypoints, const float* kp
     if (n_keypoints < 0 || n_keypoints > h->K || n_window < 0 || n_window > h->Wn) return fail(LVI_ERR_INVALID_ARG, "counts beyond the handle's capacity");
     return guarded(h->device, [&]() -> int32_t {
         const size_t k = (size_t)n_keypoints, n = (size_t)n_window;
-        s->valid = false;
+        s->valid = false; s->generation++;
         auto up = [&](void* dst, const void* src, size_t bytes) {
             if (!bytes) return;
             if (src) LVI_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
@@ -455,7 +475,7 @@ int32_t lvi_kf_release(lvi_kf* h, int32_t slot)
 {
     Slot* s = slot_of(h, slot);
     if (!s) return fail(LVI_ERR_INVALID_ARG, "null handle or slot out of range");
-    s->valid = false; s->n_kp = 0; s->n_win = 0;
+    s->valid = false; s->n_kp = 0; s->n_win = 0; s->generation++;
     return LVI_OK;
 }
 

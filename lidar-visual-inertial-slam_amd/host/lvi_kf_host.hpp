@@ -5,9 +5,10 @@
 //                                                         > MIN_LOOP_NUM gate                           -> KeyFrameDescriber::findConnectionFront
 //
 // What follows the gate in the reference (PnPRANSAC, the 4-DoF check, the match image) stays with the caller: it receives
-// the compacted vectors PnPRANSAC would.  The DBoW2 query needs the keypoint descriptors on the host: KeyFrameDescriber::
-// descriptors downloads them.  Only liblvi_hip.so exports this ABI, so only code linked against it may include this
-// header.  Parity is against DESIGN §14's restatement of OpenCV 4.5.x and DVision, not OpenCV itself.
+// the compacted vectors PnPRANSAC would.  The DBoW2 query runs on the device over the slot's descriptors (lvi_bow_host.hpp,
+// DESIGN §15; the vocabulary file is not shipped, the user supplies it); KeyFrameDescriber::descriptors downloads them for
+// savePoseGraph.  Only liblvi_hip.so exports this ABI, so only code linked against it may include this header.  Parity is
+// against DESIGN §14's restatement of OpenCV 4.5.x and DVision, not OpenCV itself.
 #pragma once
 #include <array>
 #include <vector>
@@ -22,6 +23,7 @@ constexpr int MIN_LOOP_NUM = 25;             // keyframe.h:16
 // the host half of a KeyFrame: what findConnection reads besides the descriptors (which stay in the device slot)
 struct KeyFrame {
     int slot = -1;
+    int index = -1;                                       // KeyFrame::index: the LoopDetector's key (lvi_bow_host.hpp)
     std::vector<Point3f> point_3d;
     std::vector<Point2f> point_2d_uv, point_2d_norm;
     std::vector<double> point_id;
@@ -70,7 +72,8 @@ public:
         return kf;
     }
 
-    // brief_descriptors of a slot for the DBoW2 query and savePoseGraph: [n][4] words, bit i of a descriptor in word i >> 6
+    // brief_descriptors of a slot for savePoseGraph (the DBoW2 query reads them on the device): [n][4] words, bit i of a
+    // descriptor in word i >> 6
     std::vector<std::array<uint64_t, 4>> descriptors(int slot)
     {
         int32_t cnt[2] = {0, 0};

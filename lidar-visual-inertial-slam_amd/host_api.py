@@ -41,6 +41,8 @@ GMAP_SOURCES = ("lvi_gmap_capi.cpp",)
 LOOP_SOURCES = ("lvi_loop_capi.cpp",)
 # the keyframe describer's (include/lvi_kf.h, the same restriction)
 KF_SOURCES = ("lvi_kf_capi.cpp",)
+# the loop detector's (include/lvi_bow.h, the same restriction)
+BOW_SOURCES = ("lvi_bow_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -52,7 +54,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
                  os.path.join(HOST_DIR, "lvi_fmat_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmat.h"),
                  os.path.join(HOST_DIR, "lvi_gmap_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_gmap.h"),
                  os.path.join(HOST_DIR, "lvi_loop_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_loop.h"),
-                 os.path.join(HOST_DIR, "lvi_kf_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_kf.h")]
+                 os.path.join(HOST_DIR, "lvi_kf_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_kf.h"),
+                 os.path.join(HOST_DIR, "lvi_bow_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_bow.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -142,6 +145,21 @@ class HostLibrary:
             d.lvh_kf_remove.argtypes = [C.c_void_p, C.c_int32]
             d.lvh_kf_connect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip]
             d.lvh_kf_connection.argtypes = [C.c_void_p] * 8 + [C.c_int32]
+        self.has_bow = hasattr(d, "lvh_bow_create")      # the HIP host library only
+        if self.has_bow:
+            ip = C.POINTER(C.c_int32)
+            d.lvh_bow_last_error.restype = C.c_char_p
+            d.lvh_bow_create.restype = C.c_void_p
+            d.lvh_bow_create.argtypes = [C.c_int32] * 6 + [ip] * 4 + [C.c_int32]
+            d.lvh_bow_destroy.argtypes = [C.c_void_p]
+            d.lvh_bow_kf_handle.restype = C.c_void_p
+            d.lvh_bow_kf_handle.argtypes = [C.c_void_p]
+            d.lvh_bow_db_handle.restype = C.c_void_p
+            d.lvh_bow_db_handle.argtypes = [C.c_void_p]
+            d.lvh_bow_load_vocabulary.argtypes = [C.c_void_p, C.c_char_p]
+            d.lvh_bow_add_keyframe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int32, C.c_void_p, C.c_void_p, ip, C.c_void_p]
+            d.lvh_bow_connection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self.has_fmat = hasattr(d, "lvh_trk_use_device_fundamental")      # the HIP host library only
         if self.has_fmat:
             d.lvh_fmat_last_error.restype = C.c_char_p
@@ -561,3 +579,76 @@ class KeyFrameMatcher:
         m = n.value
         return ok, dict(matched_2d_cur=v2[0][:m].copy(), matched_2d_old=v2[1][:m].copy(), matched_2d_cur_norm=v2[2][:m].copy(),
                         matched_2d_old_norm=v2[3][:m].copy(), matched_3d=p3[:m].copy(), matched_id=ids[:m].copy(), status=st)
+
+
+class LoopDetector:
+    """lvi_host::LoopDetector (host/lvi_bow_host.hpp) with a keyframe store of its own: LoopDetector::loadVocabulary and
+    addKeyFrame of pose_graph/src/loop_detector.cpp (:6-40, 56-154) over the device database of include/lvi_bow.h.  HIP
+    host library only.  `store` is a kf.KeyframeDescriber view of the store the C++ side owns: fill a slot through it
+    (describe or put), then hand the keyframe's host half to addKeyFrame."""
+
+    def __init__(self, hostlib, abi_lib, pattern, max_entries=4096, device=0, max_width=1024, max_height=576, max_keypoints=8192, max_window=1024,
+                 max_keyframes=16):
+        from .kf import KeyframeDescriber, bind as kf_bind
+        if not hostlib.has_bow:
+            raise RuntimeError("this host library has no loop detector (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        pat = [np.ascontiguousarray(p, np.int32).reshape(-1) for p in pattern]
+        if len(pat) != 4 or any(len(p) != 256 for p in pat):
+            raise ValueError("the BRIEF pattern is four arrays of 256 ints")
+        self._d = hostlib.dll.lvh_bow_create(int(device), int(max_width), int(max_height), int(max_keypoints), int(max_window), int(max_keyframes),
+                                             *[p.ctypes.data_as(C.POINTER(C.c_int32)) for p in pat], int(max_entries))
+        if not self._d:
+            raise A.LviError(-1, "lvh_bow_create", hostlib.dll.lvh_bow_last_error().decode(errors="replace"))
+        # a KeyframeDescriber view of the store the C++ side owns (never destroyed from here)
+        self.store = KeyframeDescriber.__new__(KeyframeDescriber)
+        self.store.lib = kf_bind(abi_lib)
+        self.store.max_width, self.store.max_height = int(max_width), int(max_height)
+        self.store.max_keypoints, self.store.max_window, self.store.max_keyframes = int(max_keypoints), int(max_window), int(max_keyframes)
+        self.store._h = C.c_void_p(hostlib.dll.lvh_bow_kf_handle(self._d))
+        self.store.close = lambda: None
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_bow_last_error().decode(errors="replace"))
+        return code
+
+    def close(self):
+        if self._d:
+            self.hl.dll.lvh_bow_destroy(self._d)
+            self._d = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def loadVocabulary(self, path):
+        """the vocabulary file in the VINSLoop layout (pose_graph_node.cpp:300-304); it is not shipped with the project"""
+        self._check(self.hl.dll.lvh_bow_load_vocabulary(self._d, os.fsencode(str(path))), "lvh_bow_load_vocabulary")
+
+    def addKeyFrame(self, slot, index, flag_detect_loop=True, point_3d=None, point_2d_uv=None, point_2d_norm=None, point_id=None, keypoints=None,
+                    keypoints_norm=None):
+        """-> dict(loop_index, connected, ids int32 [n], scores float64 [n]) of this frame's query and gates"""
+        from .bow import RESULT_DTYPE
+
+        def arr(a, dt, width):
+            return np.zeros((0, width), dt) if a is None else np.ascontiguousarray(a, dt).reshape(-1, width)
+        p3, uv, nm = arr(point_3d, np.float32, 3), arr(point_2d_uv, np.float32, 2), arr(point_2d_norm, np.float32, 2)
+        ids = arr(point_id, np.float64, 1).reshape(-1)
+        kp, kn = arr(keypoints, np.float32, 2), arr(keypoints_norm, np.float32, 2)
+        if not len(p3) == len(uv) == len(nm) == len(ids) or len(kp) != len(kn):
+            raise ValueError("the vectors of one group differ in length")
+        out = (C.c_int32 * 3)()
+        ret = np.zeros(4, RESULT_DTYPE)
+        self._check(self.hl.dll.lvh_bow_add_keyframe(self._d, int(slot), int(index), 1 if flag_detect_loop else 0, len(uv), A._ptr(p3), A._ptr(uv), A._ptr(nm),
+                                                     A._ptr(ids), len(kp), A._ptr(kp), A._ptr(kn), out, A._ptr(ret)), "lvh_bow_add_keyframe")
+        return dict(loop_index=out[0], connected=bool(out[1]), ids=ret["entry_id"][:out[2]].copy(), scores=ret["score"][:out[2]].copy())
+
+    def connection(self):
+        """matched_2d_cur, matched_2d_old [n, 2] and matched_id [n] of the last hit's findConnectionFront"""
+        n = self._check(self.hl.dll.lvh_bow_connection(self._d, None, None, None), "lvh_bow_connection")
+        cur = np.zeros((max(n, 1), 2), np.float32); old = np.zeros((max(n, 1), 2), np.float32); ids = np.zeros(max(n, 1), np.float64)
+        self._check(self.hl.dll.lvh_bow_connection(self._d, A._ptr(cur), A._ptr(old), A._ptr(ids)), "lvh_bow_connection")
+        return cur[:n].copy(), old[:n].copy(), ids[:n].copy()
