@@ -3,19 +3,13 @@
 // is linked into host/liblvi_host_hip.so alone (build.py), never into a host library built against the CPU oracle.
 #include <string>
 
-#include "lvi_bow_host.hpp"
+#include "lvi_bow_capi_detail.hpp"
 
 using namespace lvi_host;
+using lvi_host_capi::Detector;
 
 namespace {
 thread_local std::string g_err;
-
-struct Detector {
-    KeyFrameDescriber kd;
-    LoopDetector ld;
-    LoopResult last;
-    template <class... A> explicit Detector(int max_entries, A... a) : kd(a...), ld(kd, max_entries) {}
-};
 
 template <class F>
 int32_t guarded(F&& f)

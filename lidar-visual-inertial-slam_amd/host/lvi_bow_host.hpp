@@ -10,7 +10,8 @@
 //
 // The database works on the descriptors where the describer left them: nothing is downloaded for the query.  What the
 // reference does with a confirmed connection (the match message) and the DEBUG_IMAGE code stay with the caller / are not
-// restated; findConnection is the front half of lvi_kf_host.hpp (up to PnPRANSAC).  Like the reference, detectLoop
+// restated.  findConnection is the front half of lvi_kf_host.hpp (up to PnPRANSAC) unless usePnP installed a PnPRansac
+// (lvi_pnp_host.hpp): then it is the whole of KeyFrame::findConnection and `connected` is the reference's boolean.  Like the reference, detectLoop
 // assumes that the database's entry id of a keyframe equals its index: keyframes arrive with index 0, 1, 2, ...
 // Only liblvi_hip.so exports this ABI, so only code linked against it may include this header.
 #pragma once
@@ -21,13 +22,14 @@
 
 #include "../../include/lvi_bow.h"
 #include "lvi_kf_host.hpp"
+#include "lvi_pnp_host.hpp"
 
 namespace lvi_host {
 
 struct LoopResult {
     int loop_index = -1;                       // detectLoop's return value
-    bool connected = false;                    // findConnectionFront passed its > MIN_LOOP_NUM gate
-    Connection connection;                     // valid when loop_index != -1
+    bool connected = false;                    // findConnectionFront passed its > MIN_LOOP_NUM gate; with usePnP: findConnection's return value
+    Connection connection;                     // valid when loop_index != -1; with usePnP it carries PnPRANSAC's status
     std::vector<lvi_bow_result> ret;           // QueryResults of this frame's query (empty without flag_detect_loop)
 };
 
@@ -38,6 +40,10 @@ public:
     LoopDetector(const LoopDetector&) = delete;
     LoopDetector& operator=(const LoopDetector&) = delete;
     lvi_bow* db() const { return db_; }
+
+    // KeyFrame::findConnection's second half (PnPRANSAC and the second > MIN_LOOP_NUM gate, keyframe.cpp:200-211) :=
+    // this PnPRansac, which must outlive its use; nullptr (the default) = the front half alone, as before
+    void usePnP(PnPRansac* pnp) { pnp_ = pnp; }
 
     // loop_detector.cpp:6-10 (pose_graph_node.cpp:300-304 calls it with pkg_path + vocabulary_file).  The file is not
     // shipped with this library.
@@ -71,7 +77,7 @@ public:
         if (r.loop_index != -1) {
             const KeyFrame* old_kf = getKeyFrame(r.loop_index);
             // the reference dereferences a NULL here when no keyframe has that index; with entry id == index one always has
-            if (old_kf) r.connected = kd_.findConnectionFront(cur_kf, *old_kf, r.connection);
+            if (old_kf) r.connected = pnp_ ? findConnection(kd_, *pnp_, cur_kf, *old_kf, r.connection) : kd_.findConnectionFront(cur_kf, *old_kf, r.connection);
         }
         keyframelist.push_back(cur_kf);
         return r;
@@ -122,6 +128,7 @@ private:
     KeyFrameDescriber& kd_;
     int max_entries_;
     lvi_bow* db_ = nullptr;
+    PnPRansac* pnp_ = nullptr;
 };
 
 }  // namespace lvi_host

@@ -4,8 +4,8 @@
 //   KeyFrame::findConnection        keyframe.cpp:179-200  searchByBRIEFDes, the six reduceVector compactions and the
 //                                                         > MIN_LOOP_NUM gate                           -> KeyFrameDescriber::findConnectionFront
 //
-// What follows the gate in the reference (PnPRANSAC, the 4-DoF check, the match image) stays with the caller: it receives
-// the compacted vectors PnPRANSAC would.  The DBoW2 query runs on the device over the slot's descriptors (lvi_bow_host.hpp,
+// What follows the gate in the reference is PnPRANSAC and the second gate: lvi_pnp_host.hpp's findConnection runs them on
+// the device over the compacted vectors left here; the match image stays with the caller.  The DBoW2 query runs on the device over the slot's descriptors (lvi_bow_host.hpp,
 // DESIGN §15; the vocabulary file is not shipped, the user supplies it); KeyFrameDescriber::descriptors downloads them for
 // savePoseGraph.  Only liblvi_hip.so exports this ABI, so only code linked against it may include this header.  Parity is
 // against DESIGN §14's restatement of OpenCV 4.5.x and DVision, not OpenCV itself.
@@ -37,6 +37,10 @@ struct Connection {
     std::vector<Point3f> matched_3d;
     std::vector<double> matched_id;
     std::vector<uint8_t> status;                          // searchByBRIEFDes's, before the compaction
+    // filled by lvi_pnp_host.hpp's findConnection only: PnPRANSAC's answer, and matched_3d / matched_2d_old_norm as it received them
+    std::vector<uint8_t> pnp_status;
+    std::vector<Point3f> front_3d;
+    std::vector<Point2f> front_2d_old_norm;
 };
 
 class KeyFrameDescriber {
@@ -113,7 +117,6 @@ public:
         return (int)c.matched_2d_cur.size() > MIN_LOOP_NUM;
     }
 
-private:
     template <class T>
     static void reduceVector(std::vector<T>& v, const std::vector<uint8_t>& status)       // keyframe.cpp:3-11
     {
@@ -123,6 +126,7 @@ private:
         v.resize(j);
     }
 
+private:
     lvi_kf* h_ = nullptr;
 };
 

@@ -43,6 +43,8 @@ LOOP_SOURCES = ("lvi_loop_capi.cpp",)
 KF_SOURCES = ("lvi_kf_capi.cpp",)
 # the loop detector's (include/lvi_bow.h, the same restriction)
 BOW_SOURCES = ("lvi_bow_capi.cpp",)
+# the loop confirmation's (include/lvi_pnp.h, the same restriction; it hooks into the loop detector, so BOW_SOURCES go with it)
+PNP_SOURCES = ("lvi_pnp_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -55,7 +57,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
                  os.path.join(HOST_DIR, "lvi_gmap_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_gmap.h"),
                  os.path.join(HOST_DIR, "lvi_loop_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_loop.h"),
                  os.path.join(HOST_DIR, "lvi_kf_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_kf.h"),
-                 os.path.join(HOST_DIR, "lvi_bow_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_bow.h")]
+                 os.path.join(HOST_DIR, "lvi_bow_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_bow.h"),
+                 os.path.join(HOST_DIR, "lvi_bow_capi_detail.hpp"), os.path.join(HOST_DIR, "lvi_pnp_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pnp.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -160,6 +163,17 @@ class HostLibrary:
             d.lvh_bow_add_keyframe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int32, C.c_void_p, C.c_void_p, ip, C.c_void_p]
             d.lvh_bow_connection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.has_pnp = hasattr(d, "lvh_pnp_create")      # the HIP host library only
+        if self.has_pnp:
+            d.lvh_pnp_last_error.restype = C.c_char_p
+            d.lvh_pnp_create.restype = C.c_void_p
+            d.lvh_pnp_create.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+            d.lvh_pnp_destroy.argtypes = [C.c_void_p]
+            d.lvh_pnp_handle.restype = C.c_void_p
+            d.lvh_pnp_handle.argtypes = [C.c_void_p]
+            d.lvh_pnp_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+            d.lvh_bow_use_pnp.argtypes = [C.c_void_p, C.c_void_p]
+            d.lvh_bow_pnp_connection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self.has_fmat = hasattr(d, "lvh_trk_use_device_fundamental")      # the HIP host library only
         if self.has_fmat:
             d.lvh_fmat_last_error.restype = C.c_char_p
@@ -646,9 +660,66 @@ class LoopDetector:
                                                      A._ptr(ids), len(kp), A._ptr(kp), A._ptr(kn), out, A._ptr(ret)), "lvh_bow_add_keyframe")
         return dict(loop_index=out[0], connected=bool(out[1]), ids=ret["entry_id"][:out[2]].copy(), scores=ret["score"][:out[2]].copy())
 
+    def usePnP(self, pnp):
+        """LoopDetector::usePnP: addKeyFrame's `connected` becomes the whole KeyFrame::findConnection (PnPRANSAC and the
+        second > MIN_LOOP_NUM gate, keyframe.cpp:200-211) through this HostPnPRansac; None removes the hook"""
+        if not self.hl.has_pnp:
+            raise RuntimeError("this host library has no loop confirmation (only the one linked against liblvi_hip.so has)")
+        code = self.hl.dll.lvh_bow_use_pnp(self._d, pnp._p if pnp is not None else None)
+        if code < 0:
+            raise A.LviError(code, "lvh_bow_use_pnp", self.hl.dll.lvh_pnp_last_error().decode(errors="replace"))
+        self._pnp = pnp                                                  # keeps it alive while installed
+
+    def pnp_connection(self):
+        """matched_3d [n, 3], matched_2d_old_norm [n, 2] as PnPRANSAC received them in the last addKeyFrame and its
+        status [n]; n == 0 when PnPRANSAC did not run (no hook, no loop, or the first gate failed)"""
+        n = self.hl.dll.lvh_bow_pnp_connection(self._d, None, None, None)
+        if n < 0:
+            raise A.LviError(n, "lvh_bow_pnp_connection", self.hl.dll.lvh_pnp_last_error().decode(errors="replace"))
+        p3 = np.zeros((max(n, 1), 3), np.float32); p2 = np.zeros((max(n, 1), 2), np.float32); st = np.zeros(max(n, 1), np.uint8)
+        self.hl.dll.lvh_bow_pnp_connection(self._d, A._ptr(p3), A._ptr(p2), A._ptr(st))
+        return p3[:n].copy(), p2[:n].copy(), st[:n].copy()
+
     def connection(self):
-        """matched_2d_cur, matched_2d_old [n, 2] and matched_id [n] of the last hit's findConnectionFront"""
+        """matched_2d_cur, matched_2d_old [n, 2] and matched_id [n] of the last hit's findConnectionFront (with usePnP:
+        of findConnection, after PnPRANSAC's compaction)"""
         n = self._check(self.hl.dll.lvh_bow_connection(self._d, None, None, None), "lvh_bow_connection")
         cur = np.zeros((max(n, 1), 2), np.float32); old = np.zeros((max(n, 1), 2), np.float32); ids = np.zeros(max(n, 1), np.float64)
         self._check(self.hl.dll.lvh_bow_connection(self._d, A._ptr(cur), A._ptr(old), A._ptr(ids)), "lvh_bow_connection")
         return cur[:n].copy(), old[:n].copy(), ids[:n].copy()
+
+
+class HostPnPRansac:
+    """lvi_host::PnPRansac (host/lvi_pnp_host.hpp): KeyFrame::PnPRANSAC (keyframe.cpp:135-176) with the reference's
+    arguments (100 iterations, 10.0 / 460.0, 0.99).  HIP host library only.  Install it with LoopDetector.usePnP."""
+
+    def __init__(self, hostlib, device=0, max_points=2048, max_iters=100):
+        if not hostlib.has_pnp:
+            raise RuntimeError("this host library has no loop confirmation (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        self._p = hostlib.dll.lvh_pnp_create(int(device), int(max_points), int(max_iters))
+        if not self._p:
+            raise A.LviError(-1, "lvh_pnp_create", hostlib.dll.lvh_pnp_last_error().decode(errors="replace"))
+
+    def close(self):
+        if self._p:
+            self.hl.dll.lvh_pnp_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def status(self, matched_2d_old_norm, matched_3d):
+        """the status vector of keyframe.cpp:167-174"""
+        p2 = np.ascontiguousarray(matched_2d_old_norm, np.float32).reshape(-1, 2)
+        p3 = np.ascontiguousarray(matched_3d, np.float32).reshape(-1, 3)
+        if len(p2) != len(p3):
+            raise ValueError("the vectors differ in length")
+        st = np.zeros(max(len(p2), 1), np.uint8)
+        code = self.hl.dll.lvh_pnp_status(self._p, A._ptr(p2), A._ptr(p3), len(p2), A._ptr(st))
+        if code < 0:
+            raise A.LviError(code, "lvh_pnp_status", self.hl.dll.lvh_pnp_last_error().decode(errors="replace"))
+        return st[:len(p2)].copy()
