@@ -19,6 +19,7 @@
 
 #include "lvi_mei.hpp"
 #include "lvi_sort.hpp"
+#include "../../include/lvi_tbatch.h"
 
 namespace lvi {
 
@@ -38,7 +39,7 @@ __device__ __forceinline__ int reflect101(int p, int len)
 }
 
 // ------------------------------------------------------------------------------------------- pyrDown
-__global__ __launch_bounds__(256) void pyrdown_kernel(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh)
+__device__ __forceinline__ void pyrdown_body(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh)
 {
     const int x = blockIdx.x * 32 + (threadIdx.x & 31);
     const int y = blockIdx.y * 8 + (threadIdx.x >> 5);
@@ -53,6 +54,23 @@ __global__ __launch_bounds__(256) void pyrdown_kernel(const uint8_t* __restrict_
         sum += (j == 0 || j == 4) ? r : (j == 2 ? 6 * r : 4 * r);
     }
     dst[(size_t)y * dw + x] = (uint8_t)((sum + 128) >> 8);
+}
+__global__ __launch_bounds__(256) void pyrdown_kernel(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh)
+{
+    pyrdown_body(src, sw, sh, dst, dw, dh);
+}
+// The batch forms (lvi_tbatch, include/lvi_tbatch.h): the same bodies, the slot in blockIdx.z, one by-value table of per-slot
+// argument blocks per launch (as lvi_scan.hip's B_.a[blockIdx.z]).  A zeroed block is a slot that sits the call out; the grid is
+// sized for the largest slot, and a workgroup beyond its own slot's extent returns at once (uniform per workgroup).
+template <class T> struct TBatch { T a[LVI_TRACKER_MAX_BATCH]; };
+#define LVI_TBATCH_FITS(T) static_assert(sizeof(TBatch<T>) <= 4096, #T ": the per-slot table exceeds the 4 KB kernel-argument limit")
+struct PyrArgs { const uint8_t* src; uint8_t* dst; int sw, sh, dw, dh; };
+LVI_TBATCH_FITS(PyrArgs);
+__global__ __launch_bounds__(256) void pyrdown_batch_kernel(TBatch<PyrArgs> B_)
+{
+    const PyrArgs& a = B_.a[blockIdx.z];
+    if ((int)blockIdx.x * 32 >= a.dw || (int)blockIdx.y * 8 >= a.dh) return;
+    pyrdown_body(a.src, a.sw, a.sh, a.dst, a.dw, a.dh);
 }
 
 // ------------------------------------------------------------------------------------------- LK
@@ -79,7 +97,7 @@ struct ClaheArgs {
     int W, H, tilesX, tilesY, tw, th, clipLimit; float lutScale;
 };
 
-__global__ __launch_bounds__(1024) void clahe_lut_kernel(ClaheArgs a)
+__device__ __forceinline__ void clahe_lut_body(const ClaheArgs& a)
 {
     // 1024 threads per tile, four pixels per load, one histogram per wavefront (a tile of the 1280 x 720 frame is 14 400 pixels: 256
     // threads reading bytes one by one into ONE histogram were 32 us of the node's frame — 64 workgroups, 56 dependent rounds each)
@@ -144,8 +162,16 @@ __global__ __launch_bounds__(1024) void clahe_lut_kernel(ClaheArgs a)
     if (tid >= 256) return;
     a.lut[(size_t)k * 256 + tid] = (uint8_t)min(max(v, 0), 255);
 }
+__global__ __launch_bounds__(1024) void clahe_lut_kernel(ClaheArgs a) { clahe_lut_body(a); }
+LVI_TBATCH_FITS(ClaheArgs);
+__global__ __launch_bounds__(1024) void clahe_lut_batch_kernel(TBatch<ClaheArgs> B_)
+{
+    const ClaheArgs& a = B_.a[blockIdx.z];
+    if ((int)blockIdx.x >= a.tilesX * a.tilesY) return;
+    clahe_lut_body(a);
+}
 
-__global__ __launch_bounds__(256) void clahe_interp_kernel(ClaheArgs a)
+__device__ __forceinline__ void clahe_interp_body(const ClaheArgs& a)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= a.W || y >= a.H) return;
@@ -165,31 +191,58 @@ __global__ __launch_bounds__(256) void clahe_interp_kernel(ClaheArgs a)
     const float res = ((float)p1[ind1] * xa1 + (float)p1[ind2] * xa) * ya1 + ((float)p2[ind1] * xa1 + (float)p2[ind2] * xa) * ya;
     a.dst[(size_t)y * a.W + x] = (uint8_t)min(max(cv_round(res), 0), 255);
 }
+__global__ __launch_bounds__(256) void clahe_interp_kernel(ClaheArgs a) { clahe_interp_body(a); }
+__global__ __launch_bounds__(256) void clahe_interp_batch_kernel(TBatch<ClaheArgs> B_)
+{
+    const ClaheArgs& a = B_.a[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= a.W || (int)blockIdx.y * 4 >= a.H) return;
+    clahe_interp_body(a);
+}
 
 // ---------------------------------------------------------------------------------------------
 // f-3  CataCamera::liftProjective with the 8-step recursive distortion model + (b.x/b.z, b.y/b.z) → Point2f
 // (CataCamera.cc:556-626, 766-783; feature_tracker.cpp:306-309).  All in double, one thread per point.
 // ---------------------------------------------------------------------------------------------
 // (the device function lives in lvi_mei.hpp: the keyframe describer of lvi_kf.hip compiles the same code)
-__global__ __launch_bounds__(64) void mei_undistort_kernel(lvi_mei_params c, const float* __restrict__ xy, int n, float* __restrict__ out, const int* __restrict__ n_dev = nullptr)
+__device__ __forceinline__ void mei_undistort_body(const lvi_mei_params& c, const float* __restrict__ xy, int n, float* __restrict__ out, const int* __restrict__ n_dev)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (n_dev) n = min(n, *n_dev);                  // (the count of a device-side concatenation)
     if (i >= n) return;
     mei_lift_normalized(c, xy[2 * i], xy[2 * i + 1], out[2 * i], out[2 * i + 1]);
 }
+__global__ __launch_bounds__(64) void mei_undistort_kernel(lvi_mei_params c, const float* __restrict__ xy, int n, float* __restrict__ out, const int* __restrict__ n_dev = nullptr)
+{
+    mei_undistort_body(c, xy, n, out, n_dev);
+}
+struct MeiArgs { lvi_mei_params c; const float* xy; float* out; const int* n_dev; int n; };
+LVI_TBATCH_FITS(MeiArgs);
+__global__ __launch_bounds__(64) void mei_undistort_batch_kernel(TBatch<MeiArgs> B_)
+{
+    const MeiArgs& a = B_.a[blockIdx.z];
+    if ((int)blockIdx.x * 64 >= a.n) return;
+    mei_undistort_body(a.c, a.xy, a.n, a.out, a.n_dev);
+}
 
 // setMask (feature_tracker.cpp:36-69): mask = 255, then cv::circle(mask, pt, MIN_DIST, 0, -1) around every kept point.  The
 // filled circle is OpenCV's midpoint raster (FillCircle): row cy +- dy spans cx +- dx and row cy +- dx spans cx +- dy for the
 // (dx, dy) the integer error recurrence visits; hw[j] = the widest of the spans of row offset j.  One thread per (circle, row).
 struct CircleArgs { uint8_t* mask; int w, h; const float* centers; int n; int radius; };
-__global__ __launch_bounds__(256) void mask_fill_kernel(CircleArgs a)
+__device__ __forceinline__ void mask_fill_body(const CircleArgs& a)
 {
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
     if (i + 16 <= (size_t)a.w * a.h) *reinterpret_cast<uint4*>(a.mask + i) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
     else for (size_t k = i; k < (size_t)a.w * a.h; k++) a.mask[k] = 255;
 }
-__global__ __launch_bounds__(64) void mask_circles_kernel(CircleArgs a)
+__global__ __launch_bounds__(256) void mask_fill_kernel(CircleArgs a) { mask_fill_body(a); }
+LVI_TBATCH_FITS(CircleArgs);
+__global__ __launch_bounds__(256) void mask_fill_batch_kernel(TBatch<CircleArgs> B_)
+{
+    const CircleArgs& a = B_.a[blockIdx.z];
+    if (!a.mask || (size_t)blockIdx.x * 256 * 16 >= (size_t)a.w * a.h) return;
+    mask_fill_body(a);
+}
+__device__ __forceinline__ void mask_circles_body(const CircleArgs& a)
 {
     __shared__ int hw[128];
     const int r = a.radius;
@@ -215,11 +268,18 @@ __global__ __launch_bounds__(64) void mask_circles_kernel(CircleArgs a)
         for (int x = x0; x <= x1; x++) a.mask[(size_t)y * a.w + x] = 0;
     }
 }
+__global__ __launch_bounds__(64) void mask_circles_kernel(CircleArgs a) { mask_circles_body(a); }
+__global__ __launch_bounds__(64) void mask_circles_batch_kernel(TBatch<CircleArgs> B_)
+{
+    const CircleArgs& a = B_.a[blockIdx.z];
+    if (!a.mask || (int)blockIdx.x >= a.n) return;
+    mask_circles_body(a);
+}
 
 // undistortedPoints over [the kept points (host) ; the corners goodFeaturesToTrack just found (device)]: cur_pts of the next frame
-__global__ __launch_bounds__(64) void frame_concat_kernel(const float* __restrict__ kept, int n_kept, const float* __restrict__ found, const int* __restrict__ n_found,
-                                                          const int* __restrict__ n_cand, int with_gftt, int cap, float* __restrict__ all_xy, int* __restrict__ d_hdr,
-                                                          int* __restrict__ h_hdr, float* __restrict__ h_new)
+__device__ __forceinline__ void frame_concat_body(const float* __restrict__ kept, int n_kept, const float* __restrict__ found, const int* __restrict__ n_found,
+                                                  const int* __restrict__ n_cand, int with_gftt, int cap, float* __restrict__ all_xy, int* __restrict__ d_hdr,
+                                                  int* __restrict__ h_hdr, float* __restrict__ h_new)
 {
     // kept: the caller's points in pinned host memory (read in place); h_hdr / h_new: the frame's result block in pinned host memory —
     // {n_new (or the pick kernel's negative code), n_cand, n_all}, then the new corners: the frame end is kernels and one wait
@@ -234,7 +294,21 @@ __global__ __launch_bounds__(64) void frame_concat_kernel(const float* __restric
     }
     if (threadIdx.x == 0) { d_hdr[2] = n; h_hdr[0] = nraw; h_hdr[1] = with_gftt ? *n_cand : 0; h_hdr[2] = n; }
 }
-__global__ __launch_bounds__(64) void lk_kernel(LkArgs a)
+__global__ __launch_bounds__(64) void frame_concat_kernel(const float* __restrict__ kept, int n_kept, const float* __restrict__ found, const int* __restrict__ n_found,
+                                                          const int* __restrict__ n_cand, int with_gftt, int cap, float* __restrict__ all_xy, int* __restrict__ d_hdr,
+                                                          int* __restrict__ h_hdr, float* __restrict__ h_new)
+{
+    frame_concat_body(kept, n_kept, found, n_found, n_cand, with_gftt, cap, all_xy, d_hdr, h_hdr, h_new);
+}
+struct ConcatArgs { const float* kept; const float* found; const int* n_found; const int* n_cand; float* all_xy; int* d_hdr; int* h_hdr; float* h_new; int n_kept, with_gftt, cap; };
+LVI_TBATCH_FITS(ConcatArgs);
+__global__ __launch_bounds__(64) void frame_concat_batch_kernel(TBatch<ConcatArgs> B_)
+{
+    const ConcatArgs& a = B_.a[blockIdx.z];
+    if (!a.d_hdr) return;
+    frame_concat_body(a.kept, a.n_kept, a.found, a.n_found, a.n_cand, a.with_gftt, a.cap, a.all_xy, a.d_hdr, a.h_hdr, a.h_new);
+}
+__device__ __forceinline__ void lk_body(const LkArgs& a)
 {
     constexpr int TW = LK_WIN_MAX + 3;             // 24: source tile (window + 1 for bilinear + 1 on each side for Scharr)
     constexpr int DW = LK_WIN_MAX + 1;             // 22: derivative / target tile
@@ -434,6 +508,12 @@ __global__ __launch_bounds__(64) void lk_kernel(LkArgs a)
         if (a.h_next_xy) { a.h_next_xy[2 * f] = outx; a.h_next_xy[2 * f + 1] = outy; a.h_status[f] = st ? 1 : 0; a.h_err[f] = errv; }
     }
 }
+__global__ __launch_bounds__(64) void lk_kernel(LkArgs a) { lk_body(a); }
+LVI_TBATCH_FITS(LkArgs);               // two 8-level Pyr: 360 bytes per slot
+__global__ __launch_bounds__(64) void lk_batch_kernel(TBatch<LkArgs> B_)
+{
+    lk_body(B_.a[blockIdx.z]);          // (a workgroup past its slot's n returns first thing)
+}
 
 // ------------------------------------------------------------------------------------------- GFTT
 struct GfttArgs {
@@ -466,7 +546,7 @@ __device__ __forceinline__ void sobel_at(const uint8_t* img, int w, int h, int x
 // LDS (the first version recomputed them nine times per pixel), then every thread adds its nine in the reference's
 // order (rows, then columns, in double).  The masked maximum goes to one partial per workgroup; gftt_thr folds them
 // (14 400 wavefronts hitting one atomicMax address cost ~0.16 ms: same-address atomics serialise).
-__global__ __launch_bounds__(256) void mineig_kernel(GfttArgs a)
+__device__ __forceinline__ void mineig_body(const GfttArgs& a, int gx)
 {
     constexpr int TW = 34, TH = 10;
     __shared__ float sxx[TH][TW], sxy[TH][TW], syy[TH][TW];
@@ -504,7 +584,15 @@ __global__ __launch_bounds__(256) void mineig_kernel(GfttArgs a)
     for (int s = 32; s > 0; s >>= 1) { const unsigned t = __shfl_xor(o, s, 64); o = t > o ? t : o; }
     if (lane_id() == 0) smax[wave_id()] = o;
     __syncthreads();
-    if (threadIdx.x == 0) a.maxPartial[blockIdx.y * gridDim.x + blockIdx.x] = max(max(smax[0], smax[1]), max(smax[2], smax[3]));
+    if (threadIdx.x == 0) a.maxPartial[blockIdx.y * gx + blockIdx.x] = max(max(smax[0], smax[1]), max(smax[2], smax[3]));
+}
+__global__ __launch_bounds__(256) void mineig_kernel(GfttArgs a) { mineig_body(a, (int)gridDim.x); }
+LVI_TBATCH_FITS(GfttArgs);
+__global__ __launch_bounds__(256) void mineig_batch_kernel(TBatch<GfttArgs> B_)
+{
+    const GfttArgs& a = B_.a[blockIdx.z];
+    if ((int)blockIdx.x * 32 >= a.w || (int)blockIdx.y * 8 >= a.h) return;
+    mineig_body(a, (a.w + 31) / 32);       // the partial maxima keep the slot's own layout
 }
 
 // quality threshold = max over the (masked) min-eigenvalue image x qualityLevel (featureselect.cpp): the fold of mineig's per-workgroup
@@ -547,7 +635,7 @@ __device__ __forceinline__ bool gftt_is_cand(const GfttArgs& a, int x, int y, fl
 }
 
 constexpr int CAND_TILE = 1024;
-__global__ __launch_bounds__(256) void gftt_count_kernel(GfttArgs a, int npartial)
+__device__ __forceinline__ void gftt_count_body(const GfttArgs& a, int npartial)
 {
     __shared__ unsigned smax[4];
     const float thr = gftt_threshold(a, npartial, smax);
@@ -560,9 +648,16 @@ __global__ __launch_bounds__(256) void gftt_count_kernel(GfttArgs a, int npartia
     block_excl_scan<256>(c, ws, &tot);
     if (threadIdx.x == 0) a.blockCnt[blockIdx.x] = tot;
 }
+__global__ __launch_bounds__(256) void gftt_count_kernel(GfttArgs a, int npartial) { gftt_count_body(a, npartial); }
+__global__ __launch_bounds__(256) void gftt_count_batch_kernel(TBatch<GfttArgs> B_)
+{
+    const GfttArgs& a = B_.a[blockIdx.z];
+    if ((int)blockIdx.x * CAND_TILE >= a.w * a.h) return;
+    gftt_count_body(a, ((a.w + 31) / 32) * ((a.h + 7) / 8));
+}
 // ordered compaction; the prefix over the (<= a few thousand) per-tile counts is folded by every workgroup itself (the one-workgroup
 // scan launch in between was 4.8 us of the node's frame)
-__global__ __launch_bounds__(256) void gftt_emit_kernel(GfttArgs a, int nblk)
+__device__ __forceinline__ void gftt_emit_body(const GfttArgs& a, int nblk)
 {
     const float thr = *a.thr;
     __shared__ int ws[8];
@@ -587,6 +682,13 @@ __global__ __launch_bounds__(256) void gftt_emit_kernel(GfttArgs a, int nblk)
         a.valsA[pos] = (unsigned)p;
     }
 }
+__global__ __launch_bounds__(256) void gftt_emit_kernel(GfttArgs a, int nblk) { gftt_emit_body(a, nblk); }
+__global__ __launch_bounds__(256) void gftt_emit_batch_kernel(TBatch<GfttArgs> B_)
+{
+    const GfttArgs& a = B_.a[blockIdx.z];
+    if ((int)blockIdx.x * CAND_TILE >= a.w * a.h) return;
+    gftt_emit_body(a, (a.w * a.h + CAND_TILE - 1) / CAND_TILE);
+}
 
 struct PickArgs {
     const unsigned *keysA;
@@ -610,7 +712,7 @@ struct PickArgs {
 // exactly equal values) or an accepted list beyond the LDS tables reports -2: the host runs the radix form for that frame.
 constexpr int GFTT_BAND = 1024;                   // one candidate per thread: the band is ordered by counting, for every key, the keys below it
 template <bool SORTLDS>
-__global__ __launch_bounds__(SORTLDS ? 1024 : 64) void gftt_pick_kernel(PickArgs a)
+__device__ __forceinline__ void gftt_pick_body(const PickArgs& a)
 {
     constexpr int ACC_MAX = SORTLDS ? 2048 : 4096, GRID_MAX = SORTLDS ? 4096 : 8192, CELL_CAP = 4;
     constexpr int NT = SORTLDS ? 1024 : 64;
@@ -806,6 +908,16 @@ __global__ __launch_bounds__(SORTLDS ? 1024 : 64) void gftt_pick_kernel(PickArgs
     if (l == 0) *a.out_n = SORTLDS ? (s_state == 2 ? -2 : nacc) : (overflow ? -1 : nacc);
     if (SORTLDS && l == 0 && a.dbg) { a.dbg[0] = tq[1] - tq[0]; a.dbg[1] = tq[2]; a.dbg[2] = tq[3]; a.dbg[3] = clock64() - tq[0]; a.dbg[4] = nbands; a.dbg[5] = total; a.dbg[6] = nacc; }
 }
+template <bool SORTLDS>
+__global__ __launch_bounds__(SORTLDS ? 1024 : 64) void gftt_pick_kernel(PickArgs a) { gftt_pick_body<SORTLDS>(a); }
+LVI_TBATCH_FITS(PickArgs);
+// the LDS form for every slot of a batch: one 1024-thread workgroup per slot, each on its own CU (its ~108 KB of LDS leave room for one)
+__global__ __launch_bounds__(1024) void gftt_sortpick_batch_kernel(TBatch<PickArgs> B_)
+{
+    const PickArgs& a = B_.a[blockIdx.z];
+    if (!a.total) return;
+    gftt_pick_body<true>(a);
+}
 
 }  // namespace
 
@@ -887,7 +999,7 @@ void tracker_layout(AR& ar, lvi_tracker& t)
 }
 
 // src (w x h, dense) → dst equalised; both device buffers of the handle
-void run_clahe(lvi_tracker& t, const uint8_t* src, uint8_t* dst, int w, int h, double clip, int tilesX, int tilesY)
+ClaheArgs clahe_args(lvi_tracker& t, const uint8_t* src, uint8_t* dst, int w, int h, double clip, int tilesX, int tilesY)
 {
     int extW = w, extH = h;
     if (w % tilesX != 0 || h % tilesY != 0) { extW = w + (tilesX - (w % tilesX)); extH = h + (tilesY - (h % tilesY)); }   // copyMakeBorder quirk: both sides grow
@@ -898,6 +1010,11 @@ void run_clahe(lvi_tracker& t, const uint8_t* src, uint8_t* dst, int w, int h, d
     a.lutScale = static_cast<float>(255) / area;
     a.clipLimit = 0;
     if (clip > 0.0) a.clipLimit = std::max(static_cast<int>(clip * area / 256), 1);
+    return a;
+}
+void run_clahe(lvi_tracker& t, const uint8_t* src, uint8_t* dst, int w, int h, double clip, int tilesX, int tilesY)
+{
+    const ClaheArgs a = clahe_args(t, src, dst, w, h, clip, tilesX, tilesY);
     LVI_LAUNCH(t.ctx, "clahe_lut", (double)w * h, hipLaunchKernelGGL(clahe_lut_kernel, dim3(tilesX * tilesY), dim3(1024), 0, t.ctx.stream, a));
     LVI_LAUNCH(t.ctx, "clahe_interp", 2.0 * w * h, hipLaunchKernelGGL(clahe_interp_kernel, dim3(div_up(w, 64), div_up(h, 4)), dim3(256), 0, t.ctx.stream, a));
 }
@@ -921,6 +1038,62 @@ void build_pyramid(lvi_tracker& t, int slot)
     }
 }
 
+// the levels build_pyramid fills for a w x h image, without the launches (the batch form launches level by level for all slots)
+void plan_pyramid(Pyr& p, int w, int h, const lvi_tracker_params& P)
+{
+    p.lv[0].w = w; p.lv[0].h = h;
+    p.top = P.lk_max_level;
+    for (int level = 0; level <= P.lk_max_level; level++) {
+        if (level != 0) { p.lv[level].w = (p.lv[level - 1].w + 1) / 2; p.lv[level].h = (p.lv[level - 1].h + 1) / 2; }
+        w = (w + 1) / 2; h = (h + 1) / 2;
+        if (w <= P.lk_win || h <= P.lk_win) { p.top = level; break; }
+    }
+}
+
+int32_t check_tracker_params(const lvi_tracker_params* p)
+{
+    if (p->lk_win < 3 || (p->lk_win & 1) == 0 || p->lk_win > LK_WIN_MAX || p->lk_max_level < 0 || p->lk_max_level >= MAX_LEVELS)
+        return fail(LVI_ERR_INVALID_ARG, "bad LK parameters (odd window <= 21, maxLevel 0..7)");
+    if (p->max_width <= 0 || p->max_height <= 0 || p->max_features <= 0 || p->max_features > 4096) return fail(LVI_ERR_INVALID_ARG, "bad capacities");
+    return LVI_OK;
+}
+
+// the pinned staging buffers of one tracker state, their events recorded on its stream
+void tracker_host_alloc(lvi_tracker* t)
+{
+    for (int s = 0; s < 2; s++) {
+        LVI_HIP(hipHostMalloc((void**)&t->h_frame[s], (size_t)t->P.max_width * t->P.max_height, hipHostMallocDefault));
+        LVI_HIP(hipEventCreateWithFlags(&t->ev_frame[s], hipEventDisableTiming));
+        LVI_HIP(hipEventRecord(t->ev_frame[s], t->ctx.stream));
+        LVI_HIP(hipHostMalloc((void**)&t->h_centers[s], sizeof(float) * 2 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
+        LVI_HIP(hipEventCreateWithFlags(&t->ev_centers[s], hipEventDisableTiming));
+        LVI_HIP(hipEventRecord(t->ev_centers[s], t->ctx.stream));
+        LVI_HIP(hipHostMalloc((void**)&t->h_pts[s], sizeof(float) * 2 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
+        LVI_HIP(hipEventCreateWithFlags(&t->ev_pts[s], hipEventDisableTiming));
+        LVI_HIP(hipEventRecord(t->ev_pts[s], t->ctx.stream));
+        LVI_HIP(hipHostMalloc((void**)&t->h_kept[s], sizeof(float) * 2 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
+        LVI_HIP(hipEventCreateWithFlags(&t->ev_kept[s], hipEventDisableTiming));
+        LVI_HIP(hipEventRecord(t->ev_kept[s], t->ctx.stream));
+    }
+    LVI_HIP(hipHostMalloc((void**)&t->h_frame_out, sizeof(float) * (4 + 4 * (size_t)std::max(t->P.max_features, 64)), hipHostMallocDefault));
+    LVI_HIP(hipHostMalloc((void**)&t->h_lk, sizeof(float) * 4 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
+}
+void tracker_host_free(lvi_tracker* t)
+{
+    for (int s = 0; s < 2; s++) {
+        if (t->h_frame[s]) (void)hipHostFree(t->h_frame[s]);
+        if (t->ev_frame[s]) (void)hipEventDestroy(t->ev_frame[s]);
+        if (t->h_pts[s]) (void)hipHostFree(t->h_pts[s]);
+        if (t->h_centers[s]) (void)hipHostFree(t->h_centers[s]);
+        if (t->ev_centers[s]) (void)hipEventDestroy(t->ev_centers[s]);
+        if (t->ev_pts[s]) (void)hipEventDestroy(t->ev_pts[s]);
+        if (t->h_kept[s]) (void)hipHostFree(t->h_kept[s]);
+        if (t->ev_kept[s]) (void)hipEventDestroy(t->ev_kept[s]);
+    }
+    if (t->h_frame_out) (void)hipHostFree(t->h_frame_out);
+    if (t->h_lk) (void)hipHostFree(t->h_lk);
+}
+
 }  // namespace
 
 extern "C" {
@@ -936,9 +1109,7 @@ void lvi_tracker_params_default(lvi_tracker_params* p)
 int32_t lvi_tracker_create(const lvi_tracker_params* p, int32_t device, lvi_tracker** out)
 {
     if (!p || !out) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    if (p->lk_win < 3 || (p->lk_win & 1) == 0 || p->lk_win > LK_WIN_MAX || p->lk_max_level < 0 || p->lk_max_level >= MAX_LEVELS)
-        return fail(LVI_ERR_INVALID_ARG, "bad LK parameters (odd window <= 21, maxLevel 0..7)");
-    if (p->max_width <= 0 || p->max_height <= 0 || p->max_features <= 0 || p->max_features > 4096) return fail(LVI_ERR_INVALID_ARG, "bad capacities");
+    if (const int32_t bad = check_tracker_params(p)) return bad;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
@@ -952,22 +1123,7 @@ int32_t lvi_tracker_create(const lvi_tracker_params* p, int32_t device, lvi_trac
         t->arena.init(sz.used + (1 << 16));
         tracker_layout(t->arena, *t);
         LVI_HIP(hipMemsetAsync(t->arena.base, 0, t->arena.size, t->ctx.stream));
-        for (int s = 0; s < 2; s++) {
-            LVI_HIP(hipHostMalloc((void**)&t->h_frame[s], (size_t)t->P.max_width * t->P.max_height, hipHostMallocDefault));
-            LVI_HIP(hipEventCreateWithFlags(&t->ev_frame[s], hipEventDisableTiming));
-            LVI_HIP(hipEventRecord(t->ev_frame[s], t->ctx.stream));
-            LVI_HIP(hipHostMalloc((void**)&t->h_centers[s], sizeof(float) * 2 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
-            LVI_HIP(hipEventCreateWithFlags(&t->ev_centers[s], hipEventDisableTiming));
-            LVI_HIP(hipEventRecord(t->ev_centers[s], t->ctx.stream));
-            LVI_HIP(hipHostMalloc((void**)&t->h_pts[s], sizeof(float) * 2 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
-            LVI_HIP(hipEventCreateWithFlags(&t->ev_pts[s], hipEventDisableTiming));
-            LVI_HIP(hipEventRecord(t->ev_pts[s], t->ctx.stream));
-            LVI_HIP(hipHostMalloc((void**)&t->h_kept[s], sizeof(float) * 2 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
-            LVI_HIP(hipEventCreateWithFlags(&t->ev_kept[s], hipEventDisableTiming));
-            LVI_HIP(hipEventRecord(t->ev_kept[s], t->ctx.stream));
-        }
-        LVI_HIP(hipHostMalloc((void**)&t->h_frame_out, sizeof(float) * (4 + 4 * (size_t)std::max(t->P.max_features, 64)), hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&t->h_lk, sizeof(float) * 4 * (size_t)std::max(t->P.max_features, 64), hipHostMallocDefault));
+        tracker_host_alloc(t);
         LVI_HIP(hipStreamSynchronize(t->ctx.stream));
         return LVI_OK;
     });
@@ -983,18 +1139,7 @@ void lvi_tracker_destroy(lvi_tracker* t)
     if (t->ctx.stream) (void)hipStreamSynchronize(t->ctx.stream);
     t->prof.collect();
     t->arena.release();
-    for (int s = 0; s < 2; s++) {
-        if (t->h_frame[s]) (void)hipHostFree(t->h_frame[s]);
-        if (t->ev_frame[s]) (void)hipEventDestroy(t->ev_frame[s]);
-        if (t->h_pts[s]) (void)hipHostFree(t->h_pts[s]);
-        if (t->h_centers[s]) (void)hipHostFree(t->h_centers[s]);
-        if (t->ev_centers[s]) (void)hipEventDestroy(t->ev_centers[s]);
-        if (t->ev_pts[s]) (void)hipEventDestroy(t->ev_pts[s]);
-        if (t->h_kept[s]) (void)hipHostFree(t->h_kept[s]);
-        if (t->ev_kept[s]) (void)hipEventDestroy(t->ev_kept[s]);
-    }
-    if (t->h_frame_out) (void)hipHostFree(t->h_frame_out);
-    if (t->h_lk) (void)hipHostFree(t->h_lk);
+    tracker_host_free(t);
     if (t->ctx.stream) (void)hipStreamDestroy(t->ctx.stream);
     delete t;
 }
@@ -1141,21 +1286,31 @@ int32_t lvi_tracker_set_mask(lvi_tracker* t, const uint8_t* mask, int32_t w, int
 namespace {
 // goodFeaturesToTrack on forw, enqueued only.  lds_form: the candidates are sorted and picked by ONE workgroup in LDS (a frame with
 // more than GFTT_LDS_MAX candidates reports -2 in d_out_n and is redone in the radix form by whoever fetches the result).
+GfttArgs gftt_args(lvi_tracker* t)
+{
+    GfttArgs a{};
+    a.img = t->pyr[t->forw].lv[0].px; a.mask = t->have_mask ? t->d_mask : nullptr; a.w = t->w; a.h = t->h;
+    a.eig = t->d_eig; a.maxord = t->d_maxord; a.maxPartial = t->d_maxPartial; a.thr = t->d_thr; a.blockCnt = t->d_blockCnt; a.total = t->d_total;
+    a.keysA = t->sort.keysA; a.valsA = t->sort.valsA; a.d_n = t->d_n; a.d_nbits = t->d_nbits; a.quality = t->P.gftt_quality;
+    return a;
+}
+PickArgs pick_args(lvi_tracker* t, int32_t max_corners)
+{
+    PickArgs p{};
+    p.keysA = t->sort.keysA; p.valsA = t->sort.valsA; p.valsB = t->sort.valsB; p.d_nbits = t->d_nbits; p.total = t->d_total;
+    p.w = t->w; p.h = t->h; p.max_corners = max_corners; p.cap = t->P.max_features; p.min_dist = t->P.min_dist;
+    p.out_xy = t->d_gftt_xy; p.out_n = t->d_out_n; p.ncand = t->d_ncand; p.dbg = t->d_dbg;
+    return p;
+}
 void enqueue_gftt(lvi_tracker* t, int32_t max_corners, bool lds_form)
 {
     const int w = t->w, h = t->h, npx = w * h;
-    GfttArgs a{};
-    a.img = t->pyr[t->forw].lv[0].px; a.mask = t->have_mask ? t->d_mask : nullptr; a.w = w; a.h = h;
-    a.eig = t->d_eig; a.maxord = t->d_maxord; a.maxPartial = t->d_maxPartial; a.thr = t->d_thr; a.blockCnt = t->d_blockCnt; a.total = t->d_total;
-    a.keysA = t->sort.keysA; a.valsA = t->sort.valsA; a.d_n = t->d_n; a.d_nbits = t->d_nbits; a.quality = t->P.gftt_quality;
+    const GfttArgs a = gftt_args(t);
     const int nblk = div_up(npx, CAND_TILE);
     LVI_LAUNCH(t->ctx, "gftt_mineig", 2.0 * npx + 4.0 * npx, hipLaunchKernelGGL(mineig_kernel, dim3(div_up(w, 32), div_up(h, 8)), dim3(256), 0, t->ctx.stream, a));
     LVI_LAUNCH(t->ctx, "gftt_count", 5.0 * npx, hipLaunchKernelGGL(gftt_count_kernel, dim3(nblk), dim3(256), 0, t->ctx.stream, a, div_up(w, 32) * div_up(h, 8)));
     LVI_LAUNCH(t->ctx, "gftt_emit", 5.0 * npx, hipLaunchKernelGGL(gftt_emit_kernel, dim3(nblk), dim3(256), 0, t->ctx.stream, a, nblk));
-    PickArgs p{};
-    p.keysA = t->sort.keysA; p.valsA = t->sort.valsA; p.valsB = t->sort.valsB; p.d_nbits = t->d_nbits; p.total = t->d_total;
-    p.w = w; p.h = h; p.max_corners = max_corners; p.cap = t->P.max_features; p.min_dist = t->P.min_dist;
-    p.out_xy = t->d_gftt_xy; p.out_n = t->d_out_n; p.ncand = t->d_ncand; p.dbg = t->d_dbg;
+    const PickArgs p = pick_args(t, max_corners);
     if (lds_form) {
         LVI_LAUNCH(t->ctx, "gftt_sortpick", 0, hipLaunchKernelGGL(gftt_pick_kernel<true>, dim3(1), dim3(1024), 0, t->ctx.stream, p));
     } else {
@@ -1341,22 +1496,21 @@ int32_t lvi_tracker_debug_get(lvi_tracker* t, int32_t what, void* dst, int64_t c
     });
 }
 
-int32_t lvi_tracker_prof_enable(lvi_tracker* t, int32_t on)
+}  // extern "C"
+
+namespace {
+int32_t prof_enable_impl(int device, Ctx& c, Profiler& p, int32_t on)
 {
-    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
-    return guarded(t->device, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(t->ctx.stream)); t->prof.collect(); t->prof.on = on != 0; return LVI_OK; });
+    return guarded(device, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(c.stream)); p.collect(); p.on = on != 0; return LVI_OK; });
 }
-int32_t lvi_tracker_prof_reset(lvi_tracker* t)
+int32_t prof_reset_impl(int device, Ctx& c, Profiler& p)
 {
-    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
-    return guarded(t->device, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(t->ctx.stream)); t->prof.reset(); return LVI_OK; });
+    return guarded(device, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(c.stream)); p.reset(); return LVI_OK; });
 }
-int32_t lvi_tracker_prof_read(lvi_tracker* t, lvi_kernel_stat* stats, int32_t capacity, int32_t* n)
+int32_t prof_read_impl(int device, Ctx& c, Profiler& p, lvi_kernel_stat* stats, int32_t capacity, int32_t* n)
 {
-    if (!t || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    return guarded(t->device, [&]() -> int32_t {
-        Profiler& p = t->prof;
-        LVI_HIP(hipStreamSynchronize(t->ctx.stream)); p.collect();
+    return guarded(device, [&]() -> int32_t {
+        LVI_HIP(hipStreamSynchronize(c.stream)); p.collect();
         int k = 0;
         for (size_t i = 0; i < p.names.size(); i++) {
             if (!p.launches[i]) continue;
@@ -1370,6 +1524,449 @@ int32_t lvi_tracker_prof_read(lvi_tracker* t, lvi_kernel_stat* stats, int32_t ca
         *n = std::min(k, capacity);
         return LVI_OK;
     });
+}
+}  // namespace
+
+extern "C" {
+
+int32_t lvi_tracker_prof_enable(lvi_tracker* t, int32_t on)
+{
+    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return prof_enable_impl(t->device, t->ctx, t->prof, on);
+}
+int32_t lvi_tracker_prof_reset(lvi_tracker* t)
+{
+    if (!t) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return prof_reset_impl(t->device, t->ctx, t->prof);
+}
+int32_t lvi_tracker_prof_read(lvi_tracker* t, lvi_kernel_stat* stats, int32_t capacity, int32_t* n)
+{
+    if (!t || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    return prof_read_impl(t->device, t->ctx, t->prof, stats, capacity, n);
+}
+
+}  // extern "C"
+
+// =============================================================================================
+// lvi_tbatch (include/lvi_tbatch.h): up to 8 tracker states in one arena on one stream, every stage one launch for all
+// slots.  A slot IS an lvi_tracker state (same buffers, same pinned double slots, same flags) whose launches go through the
+// handle's stream and profiler; the host side of every call is the single handle's, slot by slot, around one batched launch.
+// =============================================================================================
+struct lvi_tbatch {
+    lvi_tracker_params P;
+    int device = 0, S = 0;
+    Ctx ctx; Profiler prof; Arena arena;
+    lvi_tracker slot[LVI_TRACKER_MAX_BATCH];
+    bool armed[LVI_TRACKER_MAX_BATCH] = {};        // set_points since the slot's last run_lk
+    bool lk_in_flight = false;                     // run_lk enqueued, the stream not waited for yet (get_lk waits once)
+    int32_t redo_mask = 0;                         // LVI_TBDBG_REDO_MASK
+};
+
+namespace {
+
+template <class K, class T>
+void launch_batch(lvi_tbatch* b, const char* name, double bytes, K kernel, dim3 grid, int threads, const TBatch<T>& B)
+{
+    grid.z = (unsigned)b->S;
+    LVI_LAUNCH(b->ctx, name, bytes, hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, b->ctx.stream, B));
+}
+
+// build_pyramid for the slots of `take`: one launch per level; a slot whose pyramid ends early has a zeroed block in the deeper launches
+void build_pyramids(lvi_tbatch* b, const bool* take, bool cur_side)
+{
+    int maxtop = 0;
+    for (int s = 0; s < b->S; s++) {
+        if (!take[s]) continue;
+        lvi_tracker& t = b->slot[s];
+        Pyr& p = t.pyr[cur_side ? t.cur : t.forw];
+        plan_pyramid(p, t.w, t.h, t.P);
+        maxtop = std::max(maxtop, p.top);
+    }
+    for (int level = 1; level <= maxtop; level++) {
+        TBatch<PyrArgs> B{};
+        int gx = 0, gy = 0; double bytes = 0;
+        for (int s = 0; s < b->S; s++) {
+            if (!take[s]) continue;
+            lvi_tracker& t = b->slot[s];
+            const Pyr& p = t.pyr[cur_side ? t.cur : t.forw];
+            if (level > p.top) continue;
+            B.a[s] = PyrArgs{p.lv[level - 1].px, p.lv[level].px, p.lv[level - 1].w, p.lv[level - 1].h, p.lv[level].w, p.lv[level].h};
+            gx = std::max(gx, div_up(p.lv[level].w, 32)); gy = std::max(gy, div_up(p.lv[level].h, 8));
+            bytes += (double)p.lv[level - 1].w * p.lv[level - 1].h + (double)p.lv[level].w * p.lv[level].h;
+        }
+        launch_batch(b, "pyrdown", bytes, pyrdown_batch_kernel, dim3(gx, gy), 256, B);
+    }
+}
+
+int32_t bad_slot(const lvi_tbatch* b, int32_t slot) { return !b || slot < 0 || slot >= b->S; }
+
+}  // namespace
+
+extern "C" {
+
+int32_t lvi_tbatch_abi_version(void) { return LVI_TBATCH_ABI_VERSION; }
+
+int32_t lvi_tbatch_create(const lvi_tracker_params* p, int32_t slots, int32_t device, lvi_tbatch** out)
+{
+    if (!p || !out) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    if (slots < 1 || slots > LVI_TRACKER_MAX_BATCH) return fail(LVI_ERR_INVALID_ARG, "slots must be 1..LVI_TRACKER_MAX_BATCH");
+    if (const int32_t bad = check_tracker_params(p)) return bad;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    lvi_tbatch* b = new lvi_tbatch();
+    b->P = *p; b->device = device; b->S = slots;
+    const char* e = getenv("LVI_GFTT_RADIX");
+    for (int s = 0; s < slots; s++) { b->slot[s].P = *p; b->slot[s].device = device; b->slot[s].gftt_force_radix = e && e[0] == '1'; }
+    int32_t st = guarded(device, [&]() -> int32_t {
+        LVI_HIP(hipStreamCreateWithFlags(&b->ctx.stream, hipStreamNonBlocking));
+        b->ctx.prof = &b->prof;
+        ArenaSizer sz;
+        for (int s = 0; s < slots; s++) tracker_layout(sz, b->slot[s]);
+        b->arena.init(sz.used + (1 << 16));
+        for (int s = 0; s < slots; s++) tracker_layout(b->arena, b->slot[s]);
+        LVI_HIP(hipMemsetAsync(b->arena.base, 0, b->arena.size, b->ctx.stream));
+        for (int s = 0; s < slots; s++) { b->slot[s].ctx = b->ctx; tracker_host_alloc(&b->slot[s]); }
+        LVI_HIP(hipStreamSynchronize(b->ctx.stream));
+        return LVI_OK;
+    });
+    if (st != LVI_OK) { lvi_tbatch_destroy(b); return st; }
+    *out = b;
+    return LVI_OK;
+}
+
+void lvi_tbatch_destroy(lvi_tbatch* b)
+{
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->ctx.stream) (void)hipStreamSynchronize(b->ctx.stream);
+    b->prof.collect();
+    b->arena.release();
+    for (int s = 0; s < b->S; s++) tracker_host_free(&b->slot[s]);
+    if (b->ctx.stream) (void)hipStreamDestroy(b->ctx.stream);
+    delete b;
+}
+
+int32_t lvi_tbatch_sync(lvi_tbatch* b)
+{
+    if (!b) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return guarded(b->device, [&]() -> int32_t { LVI_HIP(hipStreamSynchronize(b->ctx.stream)); b->lk_in_flight = false; return LVI_OK; });
+}
+
+int32_t lvi_tbatch_set_equalize(lvi_tbatch* b, int32_t on, double clip_limit, int32_t tiles_x, int32_t tiles_y)
+{
+    if (!b) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    if (on && (tiles_x < 1 || tiles_y < 1 || tiles_x > CLAHE_MAX_TILES || tiles_y > CLAHE_MAX_TILES)) return fail(LVI_ERR_INVALID_ARG, "bad tile grid");
+    for (int s = 0; s < b->S; s++) { lvi_tracker& t = b->slot[s]; t.equalize = on != 0; t.clahe_clip = clip_limit; t.clahe_tx = tiles_x; t.clahe_ty = tiles_y; }
+    return LVI_OK;
+}
+
+int32_t lvi_tbatch_push_images(lvi_tbatch* b, const uint8_t* const* imgs, int32_t w, int32_t h, int32_t stride)
+{
+    if (!b || !imgs || w <= 0 || h <= 0 || stride < w) return fail(LVI_ERR_INVALID_ARG, "bad image table");
+    if (w > b->P.max_width || h > b->P.max_height) return fail(LVI_ERR_CAPACITY, "image exceeds capacity");
+    bool take[LVI_TRACKER_MAX_BATCH] = {}, first[LVI_TRACKER_MAX_BATCH] = {}, any = false;
+    for (int s = 0; s < b->S; s++) { take[s] = imgs[s] != nullptr; any = any || take[s]; }
+    if (!any) return LVI_OK;
+    return guarded(b->device, [&]() -> int32_t {
+        bool any_first = false;
+        for (int s = 0; s < b->S; s++) {
+            if (!take[s]) continue;
+            lvi_tracker* t = &b->slot[s];
+            if (t->have_forw && (w != t->w || h != t->h)) { t->have_forw = t->have_cur = false; }
+            if (t->have_forw) { std::swap(t->cur, t->forw); t->have_cur = true; }     // cur_img = forw_img (:203), this slot's own rotation
+            first[s] = !t->have_forw; any_first = any_first || first[s];
+            t->w = w; t->h = h;
+            const int fs = (t->frame_slot ^= 1);
+            LVI_HIP(hipEventSynchronize(t->ev_frame[fs]));
+            for (int y = 0; y < h; y++) std::memcpy(t->h_frame[fs] + (size_t)y * w, imgs[s] + (size_t)y * stride, (size_t)w);
+            uint8_t* dst0 = t->equalize ? t->d_stage : t->pyr[t->forw].lv[0].px;
+            LVI_HIP(hipMemcpyAsync(dst0, t->h_frame[fs], (size_t)w * h, hipMemcpyHostToDevice, b->ctx.stream));
+            LVI_HIP(hipEventRecord(t->ev_frame[fs], b->ctx.stream));
+        }
+        if (b->slot[0].equalize) {                                                  // readImage's EQUALIZE branch (:86-90), all slots alike
+            TBatch<ClaheArgs> B{};
+            int ntile = 0; double px = 0;
+            for (int s = 0; s < b->S; s++) {
+                if (!take[s]) continue;
+                lvi_tracker& t = b->slot[s];
+                B.a[s] = clahe_args(t, t.d_stage, t.pyr[t.forw].lv[0].px, w, h, t.clahe_clip, t.clahe_tx, t.clahe_ty);
+                ntile = B.a[s].tilesX * B.a[s].tilesY; px += (double)w * h;
+            }
+            launch_batch(b, "clahe_lut", px, clahe_lut_batch_kernel, dim3(ntile), 1024, B);
+            launch_batch(b, "clahe_interp", 2.0 * px, clahe_interp_batch_kernel, dim3(div_up(w, 64), div_up(h, 4)), 256, B);
+        }
+        build_pyramids(b, take, false);
+        if (any_first) {                                                            // prev = cur = forw = img (:94-97)
+            for (int s = 0; s < b->S; s++) {
+                if (!first[s]) continue;
+                lvi_tracker& t = b->slot[s];
+                LVI_HIP(hipMemcpyAsync(t.pyr[t.cur].lv[0].px, t.pyr[t.forw].lv[0].px, (size_t)w * h, hipMemcpyDeviceToDevice, b->ctx.stream));
+            }
+            build_pyramids(b, first, true);
+        }
+        for (int s = 0; s < b->S; s++) {
+            if (!take[s]) continue;
+            lvi_tracker& t = b->slot[s];
+            if (first[s]) t.have_cur = true;
+            t.have_forw = true; t.have_lk = false; t.have_gftt = false;
+        }
+        return LVI_OK;
+    });
+}
+
+int32_t lvi_tbatch_set_points(lvi_tbatch* b, const float* const* cur_xy, const int32_t* n)
+{
+    if (!b || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    for (int s = 0; s < b->S; s++) {
+        if (n[s] > 0 && (!cur_xy || !cur_xy[s])) return fail(LVI_ERR_INVALID_ARG, "bad points");
+        if (n[s] > b->P.max_features) return fail(LVI_ERR_CAPACITY, "too many points");
+    }
+    return guarded(b->device, [&]() -> int32_t {
+        for (int s = 0; s < b->S; s++) {
+            if (n[s] < 0) continue;
+            lvi_tracker* t = &b->slot[s];
+            if (n[s]) {
+                const int ps = (t->pts_slot ^= 1);
+                LVI_HIP(hipEventSynchronize(t->ev_pts[ps]));
+                std::memcpy(t->h_pts[ps], cur_xy[s], sizeof(float) * 2 * (size_t)n[s]);
+                t->cur_src = t->h_pts[ps]; t->cur_slot = ps;
+            }
+            t->n_pts = n[s]; t->have_lk = false;
+            b->armed[s] = true;
+        }
+        return LVI_OK;
+    });
+}
+
+int32_t lvi_tbatch_run_lk(lvi_tbatch* b)
+{
+    if (!b) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    for (int s = 0; s < b->S; s++)
+        if (b->armed[s] && (!b->slot[s].have_forw || !b->slot[s].have_cur)) return fail(LVI_ERR_STATE, "no image pair");
+    return guarded(b->device, [&]() -> int32_t {
+        TBatch<LkArgs> B{};
+        int nmax = 0; double bytes = 0;
+        for (int s = 0; s < b->S; s++) {
+            if (!b->armed[s]) continue;
+            lvi_tracker* t = &b->slot[s];
+            LkArgs& a = B.a[s];
+            a.prev = t->pyr[t->cur]; a.next = t->pyr[t->forw];
+            const size_t F = (size_t)std::max(t->P.max_features, 64);
+            a.prev_xy = t->cur_src ? t->cur_src : t->d_cur_xy; a.next_xy = t->d_forw_xy; a.status = t->d_status; a.err = t->d_err;
+            a.h_next_xy = t->h_lk; a.h_err = t->h_lk + 2 * F; a.h_status = reinterpret_cast<uint8_t*>(t->h_lk + 3 * F);
+            a.n = t->n_pts; a.win = t->P.lk_win; a.max_level = std::min(a.prev.top, a.next.top);
+            a.max_count = std::min(std::max(t->P.lk_max_iters, 0), 100);
+            const double eps = std::min(std::max(t->P.lk_eps, 0.), 10.);
+            a.epsilon = eps * eps; a.min_eig = t->P.lk_min_eig_threshold;
+            nmax = std::max(nmax, a.n);
+            bytes += (double)a.n * (a.max_level + 1) * (24.0 * 24 + 22.0 * 22 * 4);
+        }
+        if (nmax > 0) {
+            launch_batch(b, "lk_track", bytes, lk_batch_kernel, dim3(nmax), 64, B);
+            for (int s = 0; s < b->S; s++) {
+                lvi_tracker* t = &b->slot[s];
+                if (b->armed[s] && t->n_pts > 0 && t->cur_slot >= 0) LVI_HIP(hipEventRecord(t->ev_pts[t->cur_slot], b->ctx.stream));
+            }
+            b->lk_in_flight = true;
+        }
+        for (int s = 0; s < b->S; s++) if (b->armed[s]) { b->slot[s].have_lk = true; b->armed[s] = false; }
+        return LVI_OK;
+    });
+}
+
+int32_t lvi_tbatch_get_lk(lvi_tbatch* b, int32_t slot, float* forw_xy, uint8_t* status, float* err, int32_t capacity, int32_t* n)
+{
+    if (bad_slot(b, slot) || !n) return fail(LVI_ERR_INVALID_ARG, "bad slot or null argument");
+    lvi_tracker* t = &b->slot[slot];
+    if (!t->have_lk) return fail(LVI_ERR_STATE, "LK not run");
+    *n = t->n_pts;
+    if (capacity < *n) return fail(LVI_ERR_CAPACITY, "capacity too small");
+    return guarded(b->device, [&]() -> int32_t {
+        const int m = *n;
+        const size_t F = (size_t)std::max(t->P.max_features, 64);
+        if (b->lk_in_flight) { LVI_HIP(hipStreamSynchronize(b->ctx.stream)); b->lk_in_flight = false; }     // the one wait for all slots
+        if (m && forw_xy) std::memcpy(forw_xy, t->h_lk, sizeof(float) * 2 * (size_t)m);
+        if (m && err) std::memcpy(err, t->h_lk + 2 * F, sizeof(float) * (size_t)m);
+        if (m && status) std::memcpy(status, t->h_lk + 3 * F, (size_t)m);
+        return LVI_OK;
+    });
+}
+
+int32_t lvi_tbatch_set_mask_circles(lvi_tbatch* b, const float* const* centers_xy, const int32_t* n, int32_t radius)
+{
+    if (!b || !n || radius < 0 || radius > 120) return fail(LVI_ERR_INVALID_ARG, "bad circle table");
+    bool any = false;
+    for (int s = 0; s < b->S; s++) {
+        if (n[s] > 0 && (!centers_xy || !centers_xy[s])) return fail(LVI_ERR_INVALID_ARG, "bad circle list");
+        if (n[s] >= 0 && !b->slot[s].have_forw) return fail(LVI_ERR_STATE, "no image");
+        if (n[s] > b->P.max_features) return fail(LVI_ERR_CAPACITY, "too many circles");
+        any = any || n[s] >= 0;
+    }
+    if (!any) return LVI_OK;
+    return guarded(b->device, [&]() -> int32_t {
+        TBatch<CircleArgs> B{};
+        int cs[LVI_TRACKER_MAX_BATCH]; int nmax = 0, gfill = 0; double px = 0;
+        for (int s = 0; s < b->S; s++) {
+            cs[s] = -1;
+            if (n[s] < 0) continue;
+            lvi_tracker* t = &b->slot[s];
+            B.a[s] = CircleArgs{t->d_mask, t->w, t->h, t->d_centers, n[s], radius};
+            if (n[s]) {
+                cs[s] = (t->centers_slot ^= 1);
+                LVI_HIP(hipEventSynchronize(t->ev_centers[cs[s]]));
+                std::memcpy(t->h_centers[cs[s]], centers_xy[s], sizeof(float) * 2 * (size_t)n[s]);
+                B.a[s].centers = t->h_centers[cs[s]];
+            }
+            nmax = std::max(nmax, n[s]); gfill = std::max(gfill, div_up(div_up(t->w * t->h, 16), 256)); px += (double)t->w * t->h;
+        }
+        launch_batch(b, "mask_fill", px, mask_fill_batch_kernel, dim3(gfill), 256, B);
+        if (nmax) {
+            launch_batch(b, "mask_circles", 0, mask_circles_batch_kernel, dim3(nmax), 64, B);
+            for (int s = 0; s < b->S; s++) if (cs[s] >= 0) LVI_HIP(hipEventRecord(b->slot[s].ev_centers[cs[s]], b->ctx.stream));
+        }
+        for (int s = 0; s < b->S; s++) if (n[s] >= 0) b->slot[s].have_mask = true;
+        return LVI_OK;
+    });
+}
+
+int32_t lvi_tbatch_run_gftt_async(lvi_tbatch* b, const int32_t* max_corners)
+{
+    if (!b || !max_corners) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    bool any = false;
+    for (int s = 0; s < b->S; s++) {
+        if (max_corners[s] >= 0 && !b->slot[s].have_forw) return fail(LVI_ERR_STATE, "no image");
+        any = any || max_corners[s] >= 0;
+    }
+    if (!any) return LVI_OK;
+    return guarded(b->device, [&]() -> int32_t {
+        if (b->slot[0].gftt_force_radix) {                          // LVI_GFTT_RADIX=1: every slot through the radix form, slot by slot
+            for (int s = 0; s < b->S; s++) if (max_corners[s] >= 0) enqueue_gftt(&b->slot[s], max_corners[s], false);
+        } else {
+            TBatch<GfttArgs> G{}; TBatch<PickArgs> K{};
+            int gx = 0, gy = 0, nblk = 0; double npx = 0;
+            for (int s = 0; s < b->S; s++) {
+                if (max_corners[s] < 0) continue;
+                lvi_tracker* t = &b->slot[s];
+                G.a[s] = gftt_args(t); K.a[s] = pick_args(t, max_corners[s]);
+                gx = std::max(gx, div_up(t->w, 32)); gy = std::max(gy, div_up(t->h, 8)); nblk = std::max(nblk, div_up(t->w * t->h, CAND_TILE));
+                npx += (double)t->w * t->h;
+            }
+            launch_batch(b, "gftt_mineig", 6.0 * npx, mineig_batch_kernel, dim3(gx, gy), 256, G);
+            launch_batch(b, "gftt_count", 5.0 * npx, gftt_count_batch_kernel, dim3(nblk), 256, G);
+            launch_batch(b, "gftt_emit", 5.0 * npx, gftt_emit_batch_kernel, dim3(nblk), 256, G);
+            launch_batch(b, "gftt_sortpick", 0, gftt_sortpick_batch_kernel, dim3(1), 1024, K);
+        }
+        for (int s = 0; s < b->S; s++) {
+            if (max_corners[s] < 0) continue;
+            lvi_tracker& t = b->slot[s];
+            t.gftt_pending = true; t.gftt_pending_max = max_corners[s]; t.have_gftt = false;
+        }
+        return LVI_OK;
+    });
+}
+
+int32_t lvi_tbatch_finish_frame(lvi_tbatch* b, const lvi_mei_params* cams, const float* const* kept_xy, const int32_t* n_kept,
+                                float* const* new_xy, int32_t new_capacity, int32_t* n_new, float* const* un_xy)
+{
+    if (!b || !n_kept || !n_new) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
+    bool any = false;
+    for (int s = 0; s < b->S; s++) {
+        if (n_kept[s] > 0 && (!kept_xy || !kept_xy[s])) return fail(LVI_ERR_INVALID_ARG, "bad kept points");
+        if (n_kept[s] > b->P.max_features) return fail(LVI_ERR_CAPACITY, "too many points");
+        any = any || n_kept[s] >= 0;
+    }
+    if (!any) return LVI_OK;
+    return guarded(b->device, [&]() -> int32_t {
+        const int F = b->P.max_features;
+        TBatch<ConcatArgs> C{}; TBatch<MeiArgs> M{};
+        const float* kept_src[LVI_TRACKER_MAX_BATCH]; bool with_gftt[LVI_TRACKER_MAX_BATCH]; int ks[LVI_TRACKER_MAX_BATCH];
+        for (int s = 0; s < b->S; s++) {
+            ks[s] = -1; with_gftt[s] = false; kept_src[s] = nullptr;
+            if (n_kept[s] < 0) continue;
+            lvi_tracker* t = &b->slot[s];
+            with_gftt[s] = t->gftt_pending;
+            kept_src[s] = t->d_un_in;
+            if (n_kept[s]) {
+                ks[s] = (t->kept_slot ^= 1);
+                LVI_HIP(hipEventSynchronize(t->ev_kept[ks[s]]));
+                std::memcpy(t->h_kept[ks[s]], kept_xy[s], sizeof(float) * 2 * (size_t)n_kept[s]);
+                kept_src[s] = t->h_kept[ks[s]];
+            }
+            int* d_hdr = reinterpret_cast<int*>(t->d_frame_out);
+            C.a[s] = ConcatArgs{kept_src[s], t->d_gftt_xy, t->d_out_n, t->d_ncand, t->d_all_xy, d_hdr, reinterpret_cast<int*>(t->h_frame_out), t->h_frame_out + 4,
+                                n_kept[s], with_gftt[s] ? 1 : 0, F};
+            if (cams) M.a[s] = MeiArgs{cams[s], t->d_all_xy, t->h_frame_out + 4 + 2 * (size_t)F, d_hdr + 2, F};
+        }
+        launch_batch(b, "frame_concat", 0, frame_concat_batch_kernel, dim3(1), 64, C);
+        for (int s = 0; s < b->S; s++) if (ks[s] >= 0) LVI_HIP(hipEventRecord(b->slot[s].ev_kept[ks[s]], b->ctx.stream));
+        if (cams) launch_batch(b, "mei_undistort", 16.0 * F, mei_undistort_batch_kernel, dim3(div_up(F, 64)), 64, M);
+        LVI_HIP(hipStreamSynchronize(b->ctx.stream));                   // the ONE wait of the frame end, all slots
+        b->lk_in_flight = false;
+        // a slot beyond the LDS form: redone alone in the radix form on its own state, its two frame-end kernels re-read (the kept
+        // points are still in the pinned slot the first attempt read); the other slots' results stand
+        b->redo_mask = 0;
+        for (int s = 0; s < b->S; s++) {
+            if (n_kept[s] < 0 || !with_gftt[s]) continue;
+            lvi_tracker* t = &b->slot[s];
+            if (reinterpret_cast<const int*>(t->h_frame_out)[0] != -2) continue;
+            b->redo_mask |= 1 << s;
+            enqueue_gftt(t, t->gftt_pending_max, false);
+            int* d_hdr = reinterpret_cast<int*>(t->d_frame_out);
+            LVI_LAUNCH(b->ctx, "frame_concat", 0, hipLaunchKernelGGL(frame_concat_kernel, dim3(1), dim3(64), 0, b->ctx.stream, kept_src[s], n_kept[s], t->d_gftt_xy, t->d_out_n,
+                                                                     t->d_ncand, 1, F, t->d_all_xy, d_hdr, reinterpret_cast<int*>(t->h_frame_out), t->h_frame_out + 4));
+            if (ks[s] >= 0) LVI_HIP(hipEventRecord(t->ev_kept[ks[s]], b->ctx.stream));
+            if (cams) LVI_LAUNCH(b->ctx, "mei_undistort", 16.0 * F, hipLaunchKernelGGL(mei_undistort_kernel, dim3(div_up(F, 64)), dim3(64), 0, b->ctx.stream, cams[s], t->d_all_xy, F,
+                                                                                       t->h_frame_out + 4 + 2 * (size_t)F, (const int*)(d_hdr + 2)));
+        }
+        if (b->redo_mask) LVI_HIP(hipStreamSynchronize(b->ctx.stream));
+        int32_t rc = LVI_OK;
+        for (int s = 0; s < b->S; s++) {
+            if (n_kept[s] < 0) continue;
+            lvi_tracker* t = &b->slot[s];
+            const int* hdr = reinterpret_cast<const int*>(t->h_frame_out);
+            t->gftt_pending = false;
+            const int nn = with_gftt[s] ? hdr[0] : 0;
+            if (nn < 0) { rc = fail(LVI_ERR_CAPACITY, "more corners than the pick kernel's accepted-list capacity"); continue; }
+            if (nn > F || n_kept[s] + nn > F) { rc = fail(LVI_ERR_CAPACITY, "more corners than max_features"); continue; }
+            if (nn > new_capacity) { rc = fail(LVI_ERR_CAPACITY, "capacity too small"); continue; }
+            n_new[s] = nn;
+            if (with_gftt[s]) { t->gftt_n = nn; t->gftt_ncand = hdr[1]; t->have_gftt = true; }
+            if (nn && new_xy && new_xy[s]) std::memcpy(new_xy[s], t->h_frame_out + 4, sizeof(float) * 2 * (size_t)nn);
+            if (cams && un_xy && un_xy[s]) std::memcpy(un_xy[s], t->h_frame_out + 4 + 2 * (size_t)F, sizeof(float) * 2 * (size_t)(n_kept[s] + nn));
+        }
+        return rc;
+    });
+}
+
+int32_t lvi_tbatch_debug_get(lvi_tbatch* b, int32_t slot, int32_t what, void* dst, int64_t cap, int64_t* n_bytes)
+{
+    if (!b) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    if (what == LVI_TBDBG_REDO_MASK) {
+        if (n_bytes) *n_bytes = 4;
+        if (!dst) return LVI_OK;
+        if (cap < 4) return fail(LVI_ERR_CAPACITY, "debug buffer too small");
+        memcpy(dst, &b->redo_mask, 4);
+        return LVI_OK;
+    }
+    if (bad_slot(b, slot)) return fail(LVI_ERR_INVALID_ARG, "slot out of range");
+    return lvi_tracker_debug_get(&b->slot[slot], what, dst, cap, n_bytes);      // (the slot's stream is the handle's)
+}
+
+int32_t lvi_tbatch_prof_enable(lvi_tbatch* b, int32_t on)
+{
+    if (!b) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return prof_enable_impl(b->device, b->ctx, b->prof, on);
+}
+int32_t lvi_tbatch_prof_reset(lvi_tbatch* b)
+{
+    if (!b) return fail(LVI_ERR_INVALID_ARG, "null handle");
+    return prof_reset_impl(b->device, b->ctx, b->prof);
+}
+int32_t lvi_tbatch_prof_read(lvi_tbatch* b, lvi_kernel_stat* stats, int32_t capacity, int32_t* n)
+{
+    if (!b || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    return prof_read_impl(b->device, b->ctx, b->prof, stats, capacity, n);
 }
 
 }  // extern "C"

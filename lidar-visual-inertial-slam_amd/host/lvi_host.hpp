@@ -474,9 +474,12 @@ inline void fillCircleZero(std::vector<uint8_t>& img, int w, int h, int cx, int 
     }
 }
 
-class FeatureTracker {
+// The handle-free half of FeatureTracker: the point lists and everything readImage does with them on the host.  FeatureTracker
+// (one lvi_tracker) and FeatureTrackerRig (host/lvi_tbatch_host.hpp: S cameras over one lvi_tbatch) run this same code around
+// their device calls.
+class FeatureTrackerState {
 public:
-    FeatureTracker(TrackerHandle& t, int row, int col, int max_cnt, int min_dist) : t_(t), ROW(row), COL(col), MAX_CNT(max_cnt), MIN_DIST(min_dist) {}
+    FeatureTrackerState(int row, int col, int max_cnt, int min_dist) : ROW(row), COL(col), MAX_CNT(max_cnt), MIN_DIST(min_dist) {}
 
     std::vector<Point2f> prev_pts, cur_pts, forw_pts, n_pts;
     std::vector<int> ids, track_cnt;
@@ -546,8 +549,6 @@ public:
     {
         for (auto& p : n_pts) { forw_pts.push_back(p); ids.push_back(-1); track_cnt.push_back(1); }
     }
-    // EQUALIZE (feature_tracker.cpp:86-90): CLAHE(3.0, 8x8) on the device, inside push_image
-    void setEqualize(bool on) { check(lvi_tracker_set_equalize(t_.get(), on ? 1 : 0, 3.0, 8, 8), "lvi_tracker_set_equalize"); }
     void setCamera(const lvi_mei_params& cam) { cam_ = cam; have_cam_ = true; }
 
     std::vector<Point2f> cur_un_pts, pts_velocity;
@@ -605,63 +606,48 @@ public:
         reduceVector(ids, status); reduceVector(track_cnt, status);
     }
 
-    // readImage (feature_tracker.cpp:81-207).  `img` is ROW x COL, 8-bit, tightly packed.
-    void readImage(const uint8_t* img, double _cur_time = 0.0)
+    // ---- the host steps of readImage (feature_tracker.cpp:81-207), in the order readImage takes them
+    // after calcOpticalFlowPyrLK: the border test and the five reduceVector (:137-146)
+    void applyLkStatus(std::vector<uint8_t>& status)
     {
-        cur_time = _cur_time;
-        check(lvi_tracker_push_image(t_.get(), img, COL, ROW, COL), "lvi_tracker_push_image");   // forw_img = img (:94-101)
-        forw_pts.clear();
-        if (!cur_pts.empty()) {
-            std::vector<uint8_t> status(cur_pts.size());
-            std::vector<float> err(cur_pts.size());
-            forw_pts.resize(cur_pts.size());
-            check(lvi_tracker_set_points(t_.get(), &cur_pts[0].x, (int32_t)cur_pts.size()), "lvi_tracker_set_points");
-            check(lvi_tracker_run_lk(t_.get()), "lvi_tracker_run_lk");                            // calcOpticalFlowPyrLK (:113)
-            int32_t n = 0;
-            check(lvi_tracker_get_lk(t_.get(), &forw_pts[0].x, status.data(), err.data(), (int32_t)cur_pts.size(), &n), "lvi_tracker_get_lk");
-            for (size_t i = 0; i < forw_pts.size(); i++) if (status[i] && !inBorder(forw_pts[i])) status[i] = 0;   // :137-139
-            reduceVector(prev_pts, status); reduceVector(cur_pts, status); reduceVector(forw_pts, status);
-            reduceVector(ids, status); reduceVector(track_cnt, status);
-        }
-        for (auto& n : track_cnt) n++;                                                            // :150-151
-        bool gftt_asked = false;
-        if (PUB_THIS_FRAME) {
-            rejectWithF();                                                                        // :153
-            setMask();
-            const int n_max_cnt = MAX_CNT - (int)forw_pts.size();
-            if (n_max_cnt > 0) {
-                // the mask is rastered on the device from the kept points; goodFeaturesToTrack (:166) is enqueued behind it
-                check(lvi_tracker_set_mask_circles(t_.get(), forw_pts.empty() ? nullptr : &forw_pts[0].x, (int32_t)forw_pts.size(), MIN_DIST), "lvi_tracker_set_mask_circles");
-                check(lvi_tracker_run_gftt_async(t_.get(), n_max_cnt), "lvi_tracker_run_gftt_async");
-                gftt_asked = true;
-            }
-        }
-        // ONE read ends the frame: the new corners and — with a camera — the undistorted cur_pts of the next frame (= forw_pts + n_pts)
-        {
-            std::vector<Point2f> out((size_t)t_.P.max_features), un((size_t)t_.P.max_features);
-            int32_t n = 0;
-            const bool want_un = have_cam_;
-            if (gftt_asked || (want_un && !forw_pts.empty()))
-                check(lvi_tracker_finish_frame(t_.get(), want_un ? &cam_ : nullptr, forw_pts.empty() ? nullptr : &forw_pts[0].x, (int32_t)forw_pts.size(),
-                                               &out[0].x, (int32_t)out.size(), &n, want_un ? &un[0].x : nullptr), "lvi_tracker_finish_frame");
-            if (PUB_THIS_FRAME) {
-                n_pts.assign(out.begin(), out.begin() + (gftt_asked ? n : 0));
-                addPoints();
-            }
-            un_ready_.assign(un.begin(), un.begin() + (want_un ? forw_pts.size() : 0));
-        }
-        prev_pts = cur_pts;                                                                       // :200-204
-        cur_pts = forw_pts;
-        if (have_cam_) undistortedPoints();                                                       // :205
-        prev_time = cur_time;
+        for (size_t i = 0; i < forw_pts.size(); i++) if (status[i] && !inBorder(forw_pts[i])) status[i] = 0;   // :137-139
+        reduceVector(prev_pts, status); reduceVector(cur_pts, status); reduceVector(forw_pts, status);
+        reduceVector(ids, status); reduceVector(track_cnt, status);
     }
-    void undistortedPoints()                                    // :298-347, liftProjective on the device (f-3)
+    // track_cnt++, then on a PUB frame rejectWithF and setMask (:150-161); returns goodFeaturesToTrack's quota MAX_CNT - forw_pts.size()
+    // (<= 0, or a frame that is not published: nothing to detect)
+    int beginDetection()
+    {
+        for (auto& n : track_cnt) n++;                                                            // :150-151
+        if (!PUB_THIS_FRAME) return 0;
+        rejectWithF();                                                                            // :153
+        setMask();
+        return MAX_CNT - (int)forw_pts.size();
+    }
+    // the frame end's results are in: n_pts + addPoints on a PUB frame (:166-185), the undistorted [forw_pts ; n_pts] kept for
+    // undistortedPoints (`un` may be null: no camera), and the rotation of the point lists (:200-204)
+    void endFrame(const Point2f* out, int n_new, const Point2f* un)
+    {
+        if (PUB_THIS_FRAME) {
+            n_pts.assign(out, out + n_new);
+            addPoints();
+        }
+        un_ready_.assign(un, un + (un ? forw_pts.size() : 0));
+        prev_pts = cur_pts;
+        cur_pts = forw_pts;
+    }
+    // undistortedPoints (:298-347) around the device lift: cur_un_pts from the frame's one read when it is there (false: the caller
+    // lifts cur_pts itself), then the id map and the velocities
+    bool takeReadyUndistorted()
     {
         cur_un_pts.assign(cur_pts.size(), Point2f{0.f, 0.f});
         cur_un_pts_map.clear();
-        if (un_ready_.size() == cur_pts.size()) cur_un_pts = un_ready_;                           // came back with the frame's one read (lvi_tracker_finish_frame)
-        else if (!cur_pts.empty())
-            check(lvi_undistort_points(t_.get(), &cam_, &cur_pts[0].x, (int32_t)cur_pts.size(), &cur_un_pts[0].x), "lvi_undistort_points");
+        if (un_ready_.size() != cur_pts.size()) return false;
+        cur_un_pts = un_ready_;                                                                   // came back with the frame's one read
+        return true;
+    }
+    void velocityMap()
+    {
         for (size_t i = 0; i < cur_pts.size(); i++) cur_un_pts_map.insert({ids[i], cur_un_pts[i]});
         pts_velocity.clear();
         if (!prev_un_pts_map.empty()) {
@@ -687,12 +673,66 @@ public:
         if (i < ids.size()) { if (ids[i] == -1) ids[i] = n_id()++; return true; }
         return false;
     }
-private:
-    TrackerHandle& t_;
+protected:
+    friend class FeatureTrackerRig;
     int ROW, COL, MAX_CNT, MIN_DIST;
     lvi_mei_params cam_{}; bool have_cam_ = false;
     std::vector<int> hw_;                                      // circleHalfWidths(MIN_DIST)
-    std::vector<Point2f> un_ready_;                            // undistorted [forw_pts ; n_pts] of this frame, from lvi_tracker_finish_frame
+    std::vector<Point2f> un_ready_;                            // undistorted [forw_pts ; n_pts] of this frame, from the frame end's one read
+};
+
+class FeatureTracker : public FeatureTrackerState {
+public:
+    FeatureTracker(TrackerHandle& t, int row, int col, int max_cnt, int min_dist) : FeatureTrackerState(row, col, max_cnt, min_dist), t_(t) {}
+
+    // EQUALIZE (feature_tracker.cpp:86-90): CLAHE(3.0, 8x8) on the device, inside push_image
+    void setEqualize(bool on) { check(lvi_tracker_set_equalize(t_.get(), on ? 1 : 0, 3.0, 8, 8), "lvi_tracker_set_equalize"); }
+
+    // readImage (feature_tracker.cpp:81-207).  `img` is ROW x COL, 8-bit, tightly packed.
+    void readImage(const uint8_t* img, double _cur_time = 0.0)
+    {
+        cur_time = _cur_time;
+        check(lvi_tracker_push_image(t_.get(), img, COL, ROW, COL), "lvi_tracker_push_image");   // forw_img = img (:94-101)
+        forw_pts.clear();
+        if (!cur_pts.empty()) {
+            std::vector<uint8_t> status(cur_pts.size());
+            std::vector<float> err(cur_pts.size());
+            forw_pts.resize(cur_pts.size());
+            check(lvi_tracker_set_points(t_.get(), &cur_pts[0].x, (int32_t)cur_pts.size()), "lvi_tracker_set_points");
+            check(lvi_tracker_run_lk(t_.get()), "lvi_tracker_run_lk");                            // calcOpticalFlowPyrLK (:113)
+            int32_t n = 0;
+            check(lvi_tracker_get_lk(t_.get(), &forw_pts[0].x, status.data(), err.data(), (int32_t)cur_pts.size(), &n), "lvi_tracker_get_lk");
+            applyLkStatus(status);
+        }
+        bool gftt_asked = false;
+        const int n_max_cnt = beginDetection();
+        if (n_max_cnt > 0) {
+            // the mask is rastered on the device from the kept points; goodFeaturesToTrack (:166) is enqueued behind it
+            check(lvi_tracker_set_mask_circles(t_.get(), forw_pts.empty() ? nullptr : &forw_pts[0].x, (int32_t)forw_pts.size(), MIN_DIST), "lvi_tracker_set_mask_circles");
+            check(lvi_tracker_run_gftt_async(t_.get(), n_max_cnt), "lvi_tracker_run_gftt_async");
+            gftt_asked = true;
+        }
+        // ONE read ends the frame: the new corners and — with a camera — the undistorted cur_pts of the next frame (= forw_pts + n_pts)
+        {
+            std::vector<Point2f> out((size_t)t_.P.max_features), un((size_t)t_.P.max_features);
+            int32_t n = 0;
+            const bool want_un = have_cam_;
+            if (gftt_asked || (want_un && !forw_pts.empty()))
+                check(lvi_tracker_finish_frame(t_.get(), want_un ? &cam_ : nullptr, forw_pts.empty() ? nullptr : &forw_pts[0].x, (int32_t)forw_pts.size(),
+                                               &out[0].x, (int32_t)out.size(), &n, want_un ? &un[0].x : nullptr), "lvi_tracker_finish_frame");
+            endFrame(out.data(), gftt_asked ? n : 0, want_un ? un.data() : nullptr);
+        }
+        if (have_cam_) undistortedPoints();                                                       // :205
+        prev_time = cur_time;
+    }
+    void undistortedPoints()                                    // :298-347, liftProjective on the device (f-3)
+    {
+        if (!takeReadyUndistorted() && !cur_pts.empty())
+            check(lvi_undistort_points(t_.get(), &cam_, &cur_pts[0].x, (int32_t)cur_pts.size(), &cur_un_pts[0].x), "lvi_undistort_points");
+        velocityMap();
+    }
+private:
+    TrackerHandle& t_;
 };
 
 // ---------------------------------------------------------------------------------------------- feature_tracker_node

@@ -45,6 +45,8 @@ KF_SOURCES = ("lvi_kf_capi.cpp",)
 BOW_SOURCES = ("lvi_bow_capi.cpp",)
 # the loop confirmation's (include/lvi_pnp.h, the same restriction; it hooks into the loop detector, so BOW_SOURCES go with it)
 PNP_SOURCES = ("lvi_pnp_capi.cpp",)
+# the camera rig's (include/lvi_tbatch.h, the same restriction; its cameras may take the device RANSAC, so FMAT_SOURCES go with it)
+TBATCH_SOURCES = ("lvi_tbatch_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -58,7 +60,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
                  os.path.join(HOST_DIR, "lvi_loop_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_loop.h"),
                  os.path.join(HOST_DIR, "lvi_kf_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_kf.h"),
                  os.path.join(HOST_DIR, "lvi_bow_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_bow.h"),
-                 os.path.join(HOST_DIR, "lvi_bow_capi_detail.hpp"), os.path.join(HOST_DIR, "lvi_pnp_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pnp.h")]
+                 os.path.join(HOST_DIR, "lvi_bow_capi_detail.hpp"), os.path.join(HOST_DIR, "lvi_pnp_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pnp.h"),
+                 os.path.join(HOST_DIR, "lvi_tbatch_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_tbatch.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -174,6 +177,17 @@ class HostLibrary:
             d.lvh_pnp_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
             d.lvh_bow_use_pnp.argtypes = [C.c_void_p, C.c_void_p]
             d.lvh_bow_pnp_connection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.has_rig = hasattr(d, "lvh_rig_create")      # the HIP host library only
+        if self.has_rig:
+            d.lvh_rig_last_error.restype = C.c_char_p
+            d.lvh_rig_create.restype = C.c_void_p
+            d.lvh_rig_create.argtypes = [C.POINTER(A.TrackerParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(A.MeiParams), C.c_int32]
+            d.lvh_rig_destroy.argtypes = [C.c_void_p]
+            d.lvh_rig_use_device_fundamental.argtypes = [C.c_void_p, C.c_int32]
+            d.lvh_rig_read_images.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+            d.lvh_rig_update_ids.argtypes = [C.c_void_p]
+            d.lvh_rig_reset_ids.restype = None
+            d.lvh_rig_camera.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         self.has_fmat = hasattr(d, "lvh_trk_use_device_fundamental")      # the HIP host library only
         if self.has_fmat:
             d.lvh_fmat_last_error.restype = C.c_char_p
@@ -723,3 +737,68 @@ class HostPnPRansac:
         if code < 0:
             raise A.LviError(code, "lvh_pnp_status", self.hl.dll.lvh_pnp_last_error().decode(errors="replace"))
         return st[:len(p2)].copy()
+
+
+class TrackerRig:
+    """FeatureTrackerRig of host/lvi_tbatch_host.hpp: FeatureTracker::readImage for S cameras over one batch tracker handle
+    (include/lvi_tbatch.h), and the node's updateID loop (feature_tracker_node.cpp:136-166).  The reference compiles
+    NUM_OF_CAM = 1: a capability of the library, not a restated behaviour.  ``batched=False`` is the yardstick: one
+    FeatureTracker over one lvi_tracker per camera, called one after another.  HIP host library only."""
+
+    def __init__(self, hostlib, tracker_params, slots, row, col, equalize=False, cams=None, device=0, batched=True):
+        if not hostlib.has_rig:
+            raise RuntimeError("this host library has no camera rig (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        self.slots = int(slots)
+        tab = None
+        if cams is not None:
+            if len(cams) != self.slots:
+                raise ValueError("one camera model per slot")
+            tab = (A.MeiParams * self.slots)(*[A.MeiParams(*[float(c[k]) for k in ("xi", "k1", "k2", "p1", "p2", "gamma1", "gamma2", "u0", "v0")]) for c in cams])
+        self._r = hostlib.dll.lvh_rig_create(C.byref(tracker_params), self.slots, int(device), int(row), int(col), 1 if equalize else 0, tab, 1 if batched else 0)
+        if not self._r:
+            raise A.LviError(-3, "lvh_rig_create", hostlib.dll.lvh_rig_last_error().decode(errors="replace"))
+        self.cap = int(tracker_params.max_features)
+
+    def close(self):
+        if self._r:
+            self.hl.dll.lvh_rig_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_rig_last_error().decode(errors="replace"))
+
+    def use_device_fundamental(self, device=0):
+        """every camera's rejectWithF runs the device RANSAC (include/lvi_fmat.h) through a handle of its own"""
+        self._check(self.hl.dll.lvh_rig_use_device_fundamental(self._r, int(device)), "lvh_rig_use_device_fundamental")
+
+    def reset_ids(self):
+        """FeatureTracker::n_id := 0 (one counter per process)"""
+        self.hl.dll.lvh_rig_reset_ids()
+
+    def read_images(self, imgs, times, pub_this_frame):
+        """imgs: one row x col uint8 image per camera (None: no image for that camera this frame)"""
+        arrs = [None if x is None else np.ascontiguousarray(x, np.uint8) for x in imgs]
+        ptrs = (C.c_void_p * self.slots)(*[A._ptr(a) if a is not None else None for a in arrs])
+        t = (C.c_double * self.slots)(*[float(v) for v in times])
+        pub = (C.c_int32 * self.slots)(*[1 if v else 0 for v in pub_this_frame])
+        self._check(self.hl.dll.lvh_rig_read_images(self._r, ptrs, t, pub), "lvh_rig_read_images")
+
+    def update_ids(self):
+        self._check(self.hl.dll.lvh_rig_update_ids(self._r), "lvh_rig_update_ids")
+
+    def camera(self, cam):
+        """dict(cur_pts, cur_un_pts, pts_velocity [n,2] f32; ids, track_cnt [n] i32) of one camera after the last frame"""
+        n = C.c_int32(0)
+        rows = np.zeros((self.cap, 6), np.float32)
+        ic = np.zeros((self.cap, 2), np.int32)
+        self._check(self.hl.dll.lvh_rig_camera(self._r, int(cam), A._ptr(rows), A._ptr(ic), self.cap, C.byref(n)), "lvh_rig_camera")
+        m = n.value
+        return dict(cur_pts=rows[:m, 0:2].copy(), cur_un_pts=rows[:m, 2:4].copy(), pts_velocity=rows[:m, 4:6].copy(), ids=ic[:m, 0].copy(), track_cnt=ic[:m, 1].copy())
