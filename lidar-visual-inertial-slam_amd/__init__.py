@@ -8,7 +8,7 @@ import it through ``__graft_entry__.import_package()`` (module name
 """
 import os
 
-from . import _abi, bow, config, depth, fmat, gmap, host_api, kf, loop, pnp, replay, synth, tbatch  # noqa: F401
+from . import _abi, bow, config, depth, fmat, gmap, host_api, kf, loop, pgo, pnp, replay, synth, tbatch  # noqa: F401
 from ._abi import Library, LviError, PT_DTYPE, LIVOX_DTYPE  # noqa: F401
 from .lidar import LidarHotpath, default_params  # noqa: F401
 from .tracker import TrackerHotpath, default_tracker_params  # noqa: F401
@@ -19,6 +19,7 @@ from .loop import LoopIcp  # noqa: F401
 from .kf import KeyframeDescriber  # noqa: F401
 from .bow import BowDatabase  # noqa: F401
 from .pnp import PnPRansac  # noqa: F401
+from .pgo import PoseGraph  # noqa: F401
 from .tbatch import TrackerBatch  # noqa: F401
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -185,8 +185,9 @@ private:
 // becomes a keyframe: updateInitialGuess (:806-877), extractNearby (:894-929), extractCloud's
 // key selection (:931-957), saveFrame (:1387-1412), the key-pose push of saveKeyFramesAndFactor (:1575-1599).
 // Key POSES are a few thousand points: host work.  Key CLOUDS never leave the device (lvi_keyframe_*, lvi_map_*).
-// iSAM2 / loop closure / GPS are out of scope: with only the prior and odometry factors the newest
-// estimate of iSAM2 is the scan-matching result, which is what is pushed here ("odometry chain").
+// With only the prior and odometry factors the newest estimate of iSAM2 is the scan-matching result, which is what is
+// pushed here ("odometry chain").  Loop closures are applied when a pose graph is installed (usePoseGraph; PoseGraphHook
+// below); GPS factors are out of scope.
 struct Affine3f { float m[3][4]; };            // Eigen::Affine3f: linear part | translation
 inline Affine3f getTransformation(float x, float y, float z, float roll, float pitch, float yaw)      // pcl::getTransformation
 {
@@ -270,9 +271,34 @@ struct MapCallerParams {                       // params_lidar.yaml:17,60-66 (ut
     bool   incrementalMap = true;              // lvi_map_update (keyframes entering / leaving the local map) instead of lvi_map_assemble; same bits
 };
 
+// The factor graph of saveKeyFramesAndFactor / correctPoses as the node calls it (addOdomFactor :1414-1428, addLoopFactor
+// :1509-1527, isam->update and calculateEstimate :1546-1566).  The library behind lvi_hotpath.h has none; the one over
+// include/lvi_pgo.h is lvi_host::PoseGraphBackend (host/lvi_pgo_host.hpp, HIP library only), installed with usePoseGraph.
+// Poses are (roll, pitch, yaw, x, y, z).
+class PoseGraphHook {
+public:
+    virtual ~PoseGraphHook() = default;
+    virtual int size() const = 0;                                            // keys in the graph
+    virtual void addOdomFactor(const float* poseFrom, const float poseTo[6]) = 0;      // poseFrom == nullptr: the prior
+    virtual int addLoopFactor() = 0;                                         // drains the queued constraints; how many were added
+    virtual void update() = 0;
+    virtual void estimate(int first, int count, float* rpyxyz) = 0;          // isamCurrentEstimate.at<Pose3>(first ...)
+};
+
 class MapOptimizationNode {
 public:
     MapOptimizationNode(LidarHandle& h, const MapCallerParams& p = MapCallerParams()) : P(p), h_(h) { for (float& v : transformTobeMapped) v = 0.f; }
+    // With a pose graph the node applies loop closures: saveKeyFramesAndFactor adds the prior or the odometry edge, drains
+    // the loop constraints the caller pushed into the graph, solves when one was added, and correctPoses rewrites every key
+    // pose (and the device store's).  Install it before the first key; nullptr removes it.  Without it every answer of the
+    // node is what it was: the odometry chain.
+    void usePoseGraph(PoseGraphHook* pg)
+    {
+        if (pg && pg->size() != (int)cloudKeyPoses3D.size()) throw Error(LVI_ERR_STATE, "usePoseGraph: the graph and the key poses differ in length");
+        pg_ = pg;
+    }
+    bool aLoopIsClosed = false;
+    int posesCorrected = 0;                    // how often correctPoses rewrote the key poses
     MapCallerParams P;
     float transformTobeMapped[6];
     std::vector<lvi_pt> cloudKeyPoses3D;       // x, y, z, intensity = index
@@ -299,6 +325,7 @@ public:
                                            cloudInfo.cloud_surface.data(), (int32_t)cloudInfo.cloud_surface.size(), &imu, transformTobeMapped, &last),
                            "lvi_scan_to_map");
         saveKeyFramesAndFactor();
+        correctPoses();
         return true;
     }
     // the same for a scan whose features already sit on the device (replay harness: lvi_scan_upload* / organize / extract ran)
@@ -318,6 +345,7 @@ public:
         extractSurroundingKeyFrames();
         lastStatus = check(lvi_scan_match(h_.get(), &imu, transformTobeMapped, &last), "lvi_scan_match");
         saveKeyFramesAndFactor();
+        correctPoses();
         return true;
     }
 
@@ -378,14 +406,18 @@ public:
 
     // a keyframe from an earlier session (map loaded at start-up): its DS clouds go into the device store, its pose into
     // cloudKeyPoses3D / 6D, exactly what saveKeyFramesAndFactor leaves behind for a scan it kept
-    int seedKeyFrame(const lvi_pt* cornerDS, int32_t nc, const lvi_pt* surfDS, int32_t ns, const float pose[6], double time)
+    int seedKeyFrame(const lvi_pt* cornerDS, int32_t nc, const lvi_pt* surfDS, int32_t ns, const float pose_in[6], double time)
     {
+        float pose[6];
+        for (int k = 0; k < 6; k++) pose[k] = pose_in[k];
+        addFactors(pose);
         int32_t idx = -1;
         check(lvi_keyframe_add(h_.get(), cornerDS, nc, surfDS, ns, pose, &idx), "lvi_keyframe_add");
         if (idx != (int32_t)cloudKeyPoses3D.size()) throw Error(LVI_ERR_STATE, "keyframe store out of step with the key poses");
         cloudKeyPoses3D.push_back(lvi_pt{pose[3], pose[4], pose[5], (float)idx});
         cloudKeyPoses6D.push_back(PointTypePose{pose[3], pose[4], pose[5], (float)idx, pose[0], pose[1], pose[2], time});
         for (int k = 0; k < 6; k++) transformTobeMapped[k] = pose[k];
+        correctPoses();
         return idx;
     }
 
@@ -405,10 +437,11 @@ public:
         return true;
     }
 
-    void saveKeyFramesAndFactor()                                                         // :1529-1603 without the factor graph
+    void saveKeyFramesAndFactor()                                                         // :1529-1603; the factor graph only with usePoseGraph
     {
         lastSavedKeyFrame = false;
         if (!saveFrame()) return;
+        addFactors(transformTobeMapped);                                                  // :1537-1573
         lvi_pt thisPose3D{transformTobeMapped[3], transformTobeMapped[4], transformTobeMapped[5], (float)cloudKeyPoses3D.size()};
         PointTypePose thisPose6D{thisPose3D.x, thisPose3D.y, thisPose3D.z, thisPose3D.intensity,
                                  transformTobeMapped[0], transformTobeMapped[1], transformTobeMapped[2], timeLaserInfoCur};
@@ -418,8 +451,48 @@ public:
         cloudKeyPoses3D.push_back(thisPose3D); cloudKeyPoses6D.push_back(thisPose6D);
         lastSavedKeyFrame = true;
     }
+    // correctPoses (:1615-1646): after a loop was applied every key pose is the graph's estimate, in cloudKeyPoses3D / 6D and
+    // in the device store (the local map's cache of a key whose pose changed is rebuilt by lvi_map_update, as :1621 clears
+    // laserCloudMapContainer)
+    void correctPoses()
+    {
+        if (!pg_ || cloudKeyPoses3D.empty() || !aLoopIsClosed) return;
+        const int n = (int)cloudKeyPoses3D.size();
+        std::vector<float> est(6 * (size_t)n);
+        pg_->estimate(0, n, est.data());
+        for (int i = 0; i < n; i++) {
+            const float* e = &est[6 * (size_t)i];
+            cloudKeyPoses3D[i].x = e[3]; cloudKeyPoses3D[i].y = e[4]; cloudKeyPoses3D[i].z = e[5];
+            PointTypePose& p = cloudKeyPoses6D[i];
+            p.x = e[3]; p.y = e[4]; p.z = e[5]; p.roll = e[0]; p.pitch = e[1]; p.yaw = e[2];
+            check(lvi_keyframe_set_pose(h_.get(), i, e), "lvi_keyframe_set_pose");
+        }
+        aLoopIsClosed = false;
+        posesCorrected++;
+    }
     double laserTime() const { return timeLaserInfoCur; }                                  // stamp of the last scan taken (the loop thread's time rule)
 private:
+    // addOdomFactor, addLoopFactor, the updates and the newest estimate (:1537-1573) for the key about to be pushed with `pose`
+    // (in: the scan-matching result; out: the graph's estimate of it).  The graph is solved only when a loop was added: a new
+    // key hangs on one factor, which its initial estimate satisfies, so the minimiser of the other keys does not move.
+    void addFactors(float pose[6])
+    {
+        if (!pg_) return;
+        if (pg_->size() != (int)cloudKeyPoses3D.size()) throw Error(LVI_ERR_STATE, "pose graph out of step with the key poses");
+        if (cloudKeyPoses3D.empty()) {
+            pg_->addOdomFactor(nullptr, pose);
+        } else {
+            const PointTypePose& b = cloudKeyPoses6D.back();                               // pclPointTogtsamPose3(cloudKeyPoses6D->points.back())
+            const float from[6] = {b.roll, b.pitch, b.yaw, b.x, b.y, b.z};
+            pg_->addOdomFactor(from, pose);
+        }
+        if (pg_->addLoopFactor() > 0) {
+            aLoopIsClosed = true;
+            pg_->update();
+            pg_->estimate((int)cloudKeyPoses3D.size(), 1, pose);
+        }
+    }
+    PoseGraphHook* pg_ = nullptr;
     void applyIncrement(const Affine3f& transIncre)
     {
         const Affine3f transTobe = getTransformation(transformTobeMapped[3], transformTobeMapped[4], transformTobeMapped[5],

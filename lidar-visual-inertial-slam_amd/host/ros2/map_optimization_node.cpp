@@ -8,10 +8,12 @@
 // overwritten; the reference's `rm -r` of the directory is not reproduced.
 // The loop-closure thread (:523-535) runs performLoopClosure through lvi_host::LoopCloser (include/lvi_loop.h): the key
 // search on the host, the two submaps and the ICP on the MI355X; it publishes the two clouds and visualizeLoopClosure's
-// markers and leaves the constraints in takeLoopConstraints() for a GTSAM back end.
-// Outside the hot path and therefore NOT reproduced here: the GTSAM / iSAM2 factor graph, GPS and the
-// APPLICATION of loop factors (addLoopFactor, correctPoses) — the key pose pushed is the scan-matching result ("odometry
-// chain"), which does not consume the constraint queue.
+// markers and leaves the constraints in takeLoopConstraints().
+// With the parameter use_device_pose_graph (default false) the node applies them: addOdomFactor, addLoopFactor, the
+// updates and correctPoses (:1414-1428, 1509-1527, 1546-1599, 1615-1646) run through lvi_host::PoseGraphBackend
+// (include/lvi_pgo.h: the minimiser of the graph's cost on the MI355X, not iSAM2's iterate), and the path is rebuilt after
+// a correction (:1641-1645).  Without it the key pose pushed is the scan-matching result ("odometry chain"), which does not
+// consume the constraint queue.  GPS factors are not reproduced.
 // Builds only where rclcpp, tf2_ros, pcl_conversions and the lidar_odometry messages / services exist.
 #include <cstdlib>
 #include <deque>
@@ -36,6 +38,7 @@
 #include "../lvi_gmap_host.hpp"
 #include "../lvi_host.hpp"
 #include "../lvi_loop_host.hpp"
+#include "../lvi_pgo_host.hpp"
 #include "lidar_odometry/msg/cloud_info.hpp"
 #include "lidar_odometry/srv/save_map.hpp"
 #include "utility.h"   // the reference's ParamServer, publishCloud, qos, stamp2Sec (and pcl/io/pcd_io.h)
@@ -72,7 +75,9 @@ class mapOptimization : public ParamServer {
     std::mutex mtxLoopInfo;       // loopInfoVec (:539)
     std::mutex loopQueueMtx;      // the constraint queue
     std::unique_ptr<lvi_host::LoopCloser> loop;
-    std::deque<lvi_host::LoopConstraint> loopConstraints;      // loopIndexQueue / loopPoseQueue / loopNoiseQueue for a GTSAM back end
+    std::deque<lvi_host::LoopConstraint> loopConstraints;      // loopIndexQueue / loopPoseQueue / loopNoiseQueue
+    std::unique_ptr<lvi_host::PoseGraphBackend> poseGraph;     // use_device_pose_graph
+    int posesCorrectedSeen = 0;
     rclcpp::Time timeLaserInfoStamp;
     nav_msgs::msg::Path globalPath;
     // incremental odometry (publishOdometry :1693-1741)
@@ -110,6 +115,10 @@ public:
         lpp.mappingSurfLeafSize = mappingSurfLeafSize;
         loop = std::make_unique<lvi_host::LoopCloser>(*mo, handle->get(), lpp);
         if (loopClosureEnableFlag) loop->reserve(1 << 20, 1 << 24);                                                    // the arena, once: one key / 2 n + 1 keys
+        if (declare_parameter<bool>("use_device_pose_graph", false)) {
+            poseGraph = std::make_unique<lvi_host::PoseGraphBackend>(0, p.max_keyframes, LVI_PGO_MAX_LOOPS);
+            mo->usePoseGraph(poseGraph.get());
+        }
         pubHistoryKeyFrames = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/icp_loop_closure_history_cloud", 1);   // :239
         pubIcpKeyFrames = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/icp_loop_closure_history_cloud", 1);       // :240 (the same topic, as written)
         pubLoopConstraintEdge = create_publisher<visualization_msgs::msg::MarkerArray>("/lio_sam/mapping/loop_closure_constraints", 1);
@@ -308,9 +317,29 @@ public:
         timeLaserInfoStamp = msgIn->header.stamp;
         const float* T = mo->transformTobeMapped;
         incrementalOdometryAffineFront = lvi_host::getTransformation(T[3], T[4], T[5], T[0], T[1], T[2]);          // updateInitialGuess :809
-        if (!mo->laserCloudInfoHandler(ci)) return;                                      // mappingProcessInterval gate; else: guess, map, match, keyframe
+        if (poseGraph) {                                                                 // addLoopFactor's queues (:1511): what the loop thread found
+            std::deque<lvi_host::LoopConstraint> found = takeLoopConstraints();
+            poseGraph->takeLoops(found);
+        }
+        if (!mo->laserCloudInfoHandler(ci)) return;                                      // mappingProcessInterval gate; else: guess, map, match, keyframe, correctPoses
+        if (mo->posesCorrected != posesCorrectedSeen) {                                   // :1641-1645: the path follows the corrected key poses
+            posesCorrectedSeen = mo->posesCorrected;
+            globalPath.poses.clear();                                                     // the key just saved is appended by publishFrames
+            const size_t keep = mo->cloudKeyPoses6D.size() - (mo->lastSavedKeyFrame ? 1 : 0);
+            for (size_t i = 0; i < keep; i++) globalPath.poses.push_back(pathPose(mo->cloudKeyPoses6D[i]));
+        }
         publishOdometry(msgIn->header.stamp, ci);
         publishFrames(msgIn->header.stamp);
+    }
+
+    geometry_msgs::msg::PoseStamped pathPose(const lvi_host::PointTypePose& p) const              // updatePath :1650-1664
+    {
+        geometry_msgs::msg::PoseStamped ps;
+        ps.header.stamp = rclcpp::Time((int64_t)(p.time * 1e9)); ps.header.frame_id = odometryFrame;
+        ps.pose.position.x = p.x; ps.pose.position.y = p.y; ps.pose.position.z = p.z;
+        tf2::Quaternion q; q.setRPY(p.roll, p.pitch, p.yaw);
+        ps.pose.orientation.x = q.x(); ps.pose.orientation.y = q.y(); ps.pose.orientation.z = q.z(); ps.pose.orientation.w = q.w();
+        return ps;
     }
 
     void publishOdometry(const builtin_interfaces::msg::Time& stamp, const lvi_host::CloudInfo& ci)               // :1666-1746
@@ -367,13 +396,7 @@ public:
             }
         }
         if (mo->lastSavedKeyFrame && pubPath->get_subscription_count() != 0) {            // updatePath :1650-1664
-            const lvi_host::PointTypePose& p = mo->cloudKeyPoses6D.back();
-            geometry_msgs::msg::PoseStamped ps;
-            ps.header.stamp = rclcpp::Time((int64_t)(p.time * 1e9)); ps.header.frame_id = odometryFrame;
-            ps.pose.position.x = p.x; ps.pose.position.y = p.y; ps.pose.position.z = p.z;
-            tf2::Quaternion q; q.setRPY(p.roll, p.pitch, p.yaw);
-            ps.pose.orientation.x = q.x(); ps.pose.orientation.y = q.y(); ps.pose.orientation.z = q.z(); ps.pose.orientation.w = q.w();
-            globalPath.poses.push_back(ps);
+            globalPath.poses.push_back(pathPose(mo->cloudKeyPoses6D.back()));
             globalPath.header.stamp = stamp; globalPath.header.frame_id = odometryFrame;
             pubPath->publish(globalPath);
         }

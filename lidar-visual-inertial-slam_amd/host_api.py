@@ -45,6 +45,8 @@ KF_SOURCES = ("lvi_kf_capi.cpp",)
 BOW_SOURCES = ("lvi_bow_capi.cpp",)
 # the loop confirmation's (include/lvi_pnp.h, the same restriction; it hooks into the loop detector, so BOW_SOURCES go with it)
 PNP_SOURCES = ("lvi_pnp_capi.cpp",)
+# the pose-graph back end's (include/lvi_pgo.h, the same restriction; it reads the loop closer's constraints, so LOOP_SOURCES go with it)
+PGO_SOURCES = ("lvi_pgo_capi.cpp",)
 # the camera rig's (include/lvi_tbatch.h, the same restriction; its cameras may take the device RANSAC, so FMAT_SOURCES go with it)
 TBATCH_SOURCES = ("lvi_tbatch_capi.cpp",)
 
@@ -61,7 +63,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
                  os.path.join(HOST_DIR, "lvi_kf_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_kf.h"),
                  os.path.join(HOST_DIR, "lvi_bow_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_bow.h"),
                  os.path.join(HOST_DIR, "lvi_bow_capi_detail.hpp"), os.path.join(HOST_DIR, "lvi_pnp_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pnp.h"),
-                 os.path.join(HOST_DIR, "lvi_tbatch_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_tbatch.h")]
+                 os.path.join(HOST_DIR, "lvi_tbatch_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_tbatch.h"),
+                 os.path.join(HOST_DIR, "lvi_pgo_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pgo.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -177,6 +180,19 @@ class HostLibrary:
             d.lvh_pnp_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
             d.lvh_bow_use_pnp.argtypes = [C.c_void_p, C.c_void_p]
             d.lvh_bow_pnp_connection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.has_pgo = hasattr(d, "lvh_pgo_create")      # the HIP host library only
+        if self.has_pgo:
+            from .pgo import PgoInfo
+            d.lvh_pgo_last_error.restype = C.c_char_p
+            d.lvh_pgo_create.restype = C.c_void_p
+            d.lvh_pgo_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double]
+            d.lvh_pgo_destroy.argtypes = [C.c_void_p]
+            d.lvh_pgo_handle.restype = C.c_void_p
+            d.lvh_pgo_handle.argtypes = [C.c_void_p]
+            d.lvh_seq_use_pose_graph.argtypes = [C.c_void_p, C.c_void_p]
+            d.lvh_pgo_push_loop.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_float]
+            d.lvh_pgo_last.argtypes = [C.c_void_p, C.POINTER(PgoInfo), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+            d.lvh_seq_poses_corrected.argtypes = [C.c_void_p]
         self.has_rig = hasattr(d, "lvh_rig_create")      # the HIP host library only
         if self.has_rig:
             d.lvh_rig_last_error.restype = C.c_char_p
@@ -265,6 +281,23 @@ class SequentialMapper:
         c, s = A.as_pts(corner), A.as_pts(surf)
         pose_c = (C.c_float * 6)(*[float(v) for v in pose])
         return self.hl.check(self.hl.dll.lvh_seq_seed_keyframe(self._s, A._ptr(c), len(c), A._ptr(s), len(s), pose_c, float(time)), "lvh_seq_seed_keyframe")
+
+    def usePoseGraph(self, backend):
+        """MapOptimizationNode::usePoseGraph: the node applies loop closures through this PoseGraphBackend (prior / odometry
+        edge per key, the pushed loop constraints, a solve when one was added, correctPoses); None removes the hook.  Install
+        it before the first key.  keyposes() then returns the corrected key poses."""
+        if not self.hl.has_pgo:
+            raise RuntimeError("this host library has no pose-graph back end (only the one linked against liblvi_hip.so has)")
+        code = self.hl.dll.lvh_seq_use_pose_graph(self._s, backend._p if backend is not None else None)
+        if code < 0:
+            raise A.LviError(code, "lvh_seq_use_pose_graph", self.hl.dll.lvh_pgo_last_error().decode(errors="replace"))
+        self._pg = backend                                               # keeps it alive while installed
+
+    def poses_corrected(self):
+        """how often correctPoses rewrote the key poses"""
+        if not self.hl.has_pgo:
+            return 0
+        return int(self.hl.dll.lvh_seq_poses_corrected(self._s))
 
     def keys(self):
         n = C.c_int32(0)
@@ -737,6 +770,55 @@ class HostPnPRansac:
         if code < 0:
             raise A.LviError(code, "lvh_pnp_status", self.hl.dll.lvh_pnp_last_error().decode(errors="replace"))
         return st[:len(p2)].copy()
+
+
+class PoseGraphBackend:
+    """lvi_host::PoseGraphBackend (host/lvi_pgo_host.hpp): mapOptimization's factor graph without GPS over
+    include/lvi_pgo.h.  HIP host library only.  Install it with SequentialMapper.usePoseGraph and feed it what
+    LoopCloser.pop() returns.  `graph` is a pgo.PoseGraph view of the handle the C++ side owns."""
+
+    def __init__(self, hostlib, abi_lib, device=0, max_poses=4096, max_loops=64, full_logmap=-1, max_iters=0, conv_eps=0.0):
+        from .pgo import PgoParams, PoseGraph, bind as pgo_bind
+        if not hostlib.has_pgo:
+            raise RuntimeError("this host library has no pose-graph back end (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        self._p = hostlib.dll.lvh_pgo_create(int(device), int(max_poses), int(max_loops), int(full_logmap), int(max_iters), float(conv_eps))
+        if not self._p:
+            raise A.LviError(-1, "lvh_pgo_create", hostlib.dll.lvh_pgo_last_error().decode(errors="replace"))
+        self.graph = PoseGraph.__new__(PoseGraph)                         # never destroyed from here
+        self.graph.lib = pgo_bind(abi_lib)
+        self.graph.max_poses, self.graph.max_loops = int(max_poses), int(max_loops)
+        self.graph._h = C.c_void_p(hostlib.dll.lvh_pgo_handle(self._p))
+        self.graph.params = PgoParams()
+        self.graph.close = lambda: None
+
+    def close(self):
+        if self._p:
+            self.hl.dll.lvh_pgo_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push_loop(self, constraint):
+        """a dict of LoopCloser.pop(): key_cur, key_pre, between [4, 4], noise; returns the queue's length"""
+        b = np.ascontiguousarray(constraint["between"], np.float64).reshape(16)
+        n = self.hl.dll.lvh_pgo_push_loop(self._p, int(constraint["key_cur"]), int(constraint["key_pre"]), b.ctypes.data_as(C.POINTER(C.c_double)),
+                                          float(constraint["noise"]))
+        if n < 0:
+            raise A.LviError(n, "lvh_pgo_push_loop", self.hl.dll.lvh_pgo_last_error().decode(errors="replace"))
+        return n
+
+    def last(self):
+        """dict(updates, loops_added, loops_queued, status, info of the last update, pose_to of the last addOdomFactor)"""
+        from .pgo import PgoInfo
+        info, pose, cnt = PgoInfo(), (C.c_float * 6)(), (C.c_int32 * 4)()
+        self.hl.dll.lvh_pgo_last(self._p, C.byref(info), pose, cnt)
+        return dict(updates=cnt[0], loops_added=cnt[1], loops_queued=cnt[2], status=cnt[3], iterations=info.iterations, converged=bool(info.converged),
+                    chi2_before=info.chi2_before, chi2_after=info.chi2_after, max_step=info.max_step, pose_to=np.array(pose[:], np.float32))
 
 
 class TrackerRig:
