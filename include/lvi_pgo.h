@@ -2,7 +2,8 @@
  *
  * Replaces addOdomFactor (mapOptimization.cpp:1414-1428), addLoopFactor (:1509-1527), the isam->update calls and the
  * estimate read-back of saveKeyFramesAndFactor (:1546-1599) and the pose source of correctPoses (:1615-1646).  GPS
- * factors (addGPSFactor, :1430-1507) are not restated.  GTSAM is not vendored: the conventions are restated from memory
+ * factors (addGPSFactor, :1430-1507) and the covariance that gates them (:1591) operate on this handle through
+ * lvi_pgo_gps.h, a separate header with its own version.  GTSAM is not vendored: the conventions are restated from memory
  *  — tangent order rotation then translation, Rot3::RzRyRx(roll, pitch, yaw), right perturbations, factor
  * error = Local(measured, h(x)) whitened by 1 / sqrt(variance).  Parity is with the MINIMISER of that cost
  * (tests/pgo_ref.py), not with iSAM2's iterate after its 2 (or 7) updates.
@@ -50,7 +51,8 @@ typedef struct lvi_pgo_info {
 int32_t lvi_pgo_abi_version(void);
 void lvi_pgo_params_default(lvi_pgo_params *p);      /* full_logmap 1, max_iters 10, conv_eps 1e-10 */
 
-/* max_poses 1..LVI_PGO_MAX_POSES, max_loops 0..LVI_PGO_MAX_LOOPS.  Memory grows with max_poses * (6 max_loops + 1). */
+/* max_poses 1..LVI_PGO_MAX_POSES, max_loops 0..LVI_PGO_MAX_LOOPS.  Memory grows with max_poses * (6 max_loops + 6):
+ * the right-hand sides of a step (6 max_loops + 1) or of lvi_pgo_gps_marginal_covariance (6 max_loops + 6). */
 int32_t lvi_pgo_create(int32_t device, int32_t max_poses, int32_t max_loops, lvi_pgo **out);
 void lvi_pgo_destroy(lvi_pgo *g);
 int32_t lvi_pgo_clear(lvi_pgo *g);                   /* no poses, no loops; the parameters stay */

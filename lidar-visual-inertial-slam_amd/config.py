@@ -48,6 +48,24 @@ def load_loop_yaml(path):
     return out
 
 
+GPS_KEYS = dict(useGpsElevation=("use_gps_elevation", False), gpsCovThreshold=("gps_cov_threshold", 2.0), poseCovThreshold=("pose_cov_threshold", 25.0))
+
+
+def load_gps_yaml(path):
+    """→ the GPS settings of params_lidar.yaml (utility.h:178-183): dict(use_gps_elevation, gps_cov_threshold,
+    pose_cov_threshold, gps_topic), the keyword arguments of host_api.SequentialMapper.useGps plus the topic.  The shipped
+    file sets none of the three, so an absent key takes the default utility.h declares"""
+    node = yaml.safe_load(open(path))
+    for k in ("/**", "ros__parameters"):
+        node = node[k]
+    out = {name: node.get(k, default) for k, (name, default) in GPS_KEYS.items()}
+    out["use_gps_elevation"] = bool(out["use_gps_elevation"])
+    for k in ("gps_cov_threshold", "pose_cov_threshold"):
+        out[k] = float(out[k])
+    out["gps_topic"] = str(node.get("gpsTopic", "lio_sam/odometry/gps"))                # utility.h:164
+    return out
+
+
 def _opencv_yaml(path):
     txt = open(path).read()
     txt = re.sub(r"^%YAML[:\s]*1\.0\s*$", "", txt, flags=re.M)          # FileStorage header is not YAML 1.1 directive syntax

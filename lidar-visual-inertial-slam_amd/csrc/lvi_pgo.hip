@@ -20,13 +20,26 @@
 // A step is active when it is the first or the step before it was taken and was not below conv_eps; every kernel of a step
 // reads that from step[] and returns when the step is not active, so the whole solve is enqueued at once and waited for
 // once.  No workgroup waits for another: what one launch writes, only later launches read.
+//
+// GPS factors (include/lvi_pgo_gps.h).  A GPS factor is not invariant under a common left transform, so with
+// G >= 1 of them the shortcut for key 0 no longer holds and the step is the full system's: key 0 is a live key of the chain
+// (its block Bp'Bp + A1'A1), nothing is substituted, and every GPS factor adds J'J to its key's diagonal block and J'r to the
+// gradient.  The chain stays block tridiagonal, so the same reduce / backsub / loops / update launches run with N live keys.
+// The factors are held sorted by key (goff[i] .. goff[i + 1] are key i's), so a key's workgroup sums its own in a fixed order.
+// With G == 0 every kernel takes exactly the branches it took before GPS factors existed.
+//
+// lvi_pgo_gps_marginal_covariance is one pass of the same launches at the current poses with R = 6 unit right-hand sides at
+// the key instead of -g (M = 6 L + 6), then pgo_cov: the (key, key) block of T^-1 - T^-1 V' S^-1 V T^-1.  Without GPS factors
+// that is the block of the anchored system, and the prior's part Ad (Bp' W Bp)^-1 Ad' is added in closed form.
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <vector>
 
 #include "lvi_dev.hpp"
 #include "lvi_pgo_math.hpp"
 #include "../../include/lvi_pgo.h"
+#include "../../include/lvi_pgo_gps.h"
 
 using namespace lvi;
 using namespace lvi_pgo_math;
@@ -43,18 +56,39 @@ struct Dev {
     double *D, *Lo, *Up, *Bm, *S, *w;
     double* delta0; double* step; lvi_pgo_info* info;
     int N, L, M, full, max_iters; double eps;
+    // GPS factors, sorted by key: the key, the measurement [3], 1 / sqrt(variance) [3]; goff [N + 1]; the whitened Jacobian [18] and residual [3]
+    const int* gkey; const int* goff; const double* gz; const double* gsw;
+    double *JG, *rg, *cov;
+    int G, R, ckey;                  // R right-hand sides ahead of the columns of V': 1 (-g) for a step, 6 (unit vectors at key ckey) for the covariance
 };
 
 __device__ __forceinline__ bool active(const Dev& d, int it) { return it == 0 || d.step[it - 1] >= d.eps; }
 
 __constant__ double PRIOR_SW[6] = {10., 10., 0.31830988618379067154, 1e-4, 1e-4, 1e-4};       // 1 / sqrt(1e-2, 1e-2, pi^2, 1e8 x3)
 __constant__ double ODOM_SW[6] = {1e3, 1e3, 1e3, 1e2, 1e2, 1e2};                               // 1 / sqrt(1e-6 x3, 1e-4 x3)
+__constant__ double PRIOR_VAR[6] = {1e-2, 1e-2, 9.8696044010893586188, 1e8, 1e8, 1e8};         // mapOptimization.cpp:1418-1420
 
 __global__ __launch_bounds__(NB) void pgo_linearise(Dev d, int it, int eval_only)
 {
     if (!eval_only && !active(d, it)) return;
     const int e = blockIdx.x * NB + threadIdx.x;
-    if (e >= d.N + d.L) return;
+    if (e >= d.N + d.L + d.G) return;
+    if (e >= d.N + d.L) {
+        const int g = e - d.N - d.L;
+        double r3[3], J[18];
+        gps_error(d.X[d.gkey[g]], d.gz + 3 * (size_t)g, r3, J);
+        double s2 = 0.;
+        for (int i = 0; i < 3; i++) {
+            const double sw = d.gsw[3 * (size_t)g + i], rw = sw * r3[i];
+            s2 += rw * rw;
+            if (!eval_only) {
+                d.rg[3 * (size_t)g + i] = rw;
+                for (int j = 0; j < 6; j++) d.JG[18 * (size_t)g + 6 * i + j] = sw * J[6 * i + j];
+            }
+        }
+        d.e2[e] = s2;
+        return;
+    }
     double r[6], A[36], B[36], sw[6];
     double *oA, *oB, *orr;
     if (e == 0) {
@@ -110,7 +144,9 @@ __device__ __forceinline__ double ptv(const double* P, const double* v, int a)
 __global__ __launch_bounds__(NB) void pgo_assemble(Dev d, int it)
 {
     if (!active(d, it)) return;
-    const int i = blockIdx.x, N = d.N, M = d.M;
+    const int i = blockIdx.x, N = d.N, M = d.M, R = d.R;
+    const bool fs = d.G > 0;                                      // the full system: key 0 is live
+    const int g0 = fs ? d.goff[i] : 0, g1 = fs ? d.goff[i + 1] : 0;
     double* Di = d.D + 36 * (size_t)i;
     double* Loi = d.Lo + 36 * (size_t)i;
     double* Upi = d.Up + 36 * (size_t)i;
@@ -120,13 +156,15 @@ __global__ __launch_bounds__(NB) void pgo_assemble(Dev d, int it)
         if (t < 108) {
             const int which = t / 36, a = (t % 36) / 6, b = t % 6;
             double v = 0.;
-            if (i == 0) {
+            if (i == 0 && !fs) {
                 v = which == 0 && a == b ? 1. : 0.;
             } else if (which == 0) {
                 v = ptq(d.JBc + 36 * (size_t)i, d.JBc + 36 * (size_t)i, a, b);
                 if (i + 1 < N) v += ptq(d.JAc + 36 * (size_t)(i + 1), d.JAc + 36 * (size_t)(i + 1), a, b);
+                for (int g = g0; g < g1; g++)
+                    for (int k = 0; k < 3; k++) v += d.JG[18 * (size_t)g + 6 * k + a] * d.JG[18 * (size_t)g + 6 * k + b];
             } else if (which == 1) {
-                if (i >= 2) v = ptq(d.JBc + 36 * (size_t)i, d.JAc + 36 * (size_t)i, a, b);            // row i, column i - 1
+                if (i >= (fs ? 1 : 2)) v = ptq(d.JBc + 36 * (size_t)i, d.JAc + 36 * (size_t)i, a, b);            // row i, column i - 1
             } else {
                 if (i + 1 < N) v = ptq(d.JAc + 36 * (size_t)(i + 1), d.JBc + 36 * (size_t)(i + 1), a, b);   // row i, column i + 1
             }
@@ -135,27 +173,31 @@ __global__ __launch_bounds__(NB) void pgo_assemble(Dev d, int it)
         }
         const int q = t - 108, a = q / M, col = q % M;            // row a of the key's block, right-hand side col
         double v = 0.;
-        if (i > 0) {
-            if (col == 0) {
-                // -g_i, with delta_0 substituted into the edges that touch key 0
+        if (i > 0 || fs) {
+            if (col < R && R == 6) {
+                v = i == d.ckey && col == a ? 1. : 0.;            // the covariance's unit right-hand sides
+            } else if (col == 0) {
+                // -g_i, with delta_0 substituted into the edges that touch key 0 (not in the full system)
                 double rr[6];
                 for (int k = 0; k < 6; k++) rr[k] = d.rc[6 * (size_t)i + k];
-                if (i == 1) for (int k = 0; k < 6; k++) for (int j = 0; j < 6; j++) rr[k] += d.JAc[36 + 6 * k + j] * d.delta0[j];
+                if (i == 1 && !fs) for (int k = 0; k < 6; k++) for (int j = 0; j < 6; j++) rr[k] += d.JAc[36 + 6 * k + j] * d.delta0[j];
                 v = ptv(d.JBc + 36 * (size_t)i, rr, a);
                 if (i + 1 < N) v += ptv(d.JAc + 36 * (size_t)(i + 1), d.rc + 6 * (size_t)(i + 1), a);
                 for (int l = 0; l < d.L; l++) {
                     const int2 ft = d.lidx[l];
                     if (ft.x != i && ft.y != i) continue;
-                    const double* Jo = ft.x == 0 ? d.JAl + 36 * (size_t)l : ft.y == 0 ? d.JBl + 36 * (size_t)l : nullptr;
+                    const double* Jo = fs ? nullptr : ft.x == 0 ? d.JAl + 36 * (size_t)l : ft.y == 0 ? d.JBl + 36 * (size_t)l : nullptr;
                     for (int k = 0; k < 6; k++) {
                         rr[k] = d.rl[6 * (size_t)l + k];
                         if (Jo) for (int j = 0; j < 6; j++) rr[k] += Jo[6 * k + j] * d.delta0[j];
                     }
                     v += ptv((ft.x == i ? d.JAl : d.JBl) + 36 * (size_t)l, rr, a);
                 }
+                for (int g = g0; g < g1; g++)
+                    for (int k = 0; k < 3; k++) v += d.JG[18 * (size_t)g + 6 * k + a] * d.rg[3 * (size_t)g + k];
                 v = -v;
             } else {
-                const int l = (col - 1) / 6, k = (col - 1) % 6;       // row k of loop l's Jacobian = column of V'
+                const int l = (col - R) / 6, k = (col - R) % 6;       // row k of loop l's Jacobian = column of V'
                 const int2 ft = d.lidx[l];
                 if (ft.x == i) v = d.JAl[36 * (size_t)l + 6 * k + a];
                 else if (ft.y == i) v = d.JBl[36 * (size_t)l + 6 * k + a];
@@ -259,23 +301,23 @@ __global__ __launch_bounds__(NB) void pgo_backsub(Dev d, int it, int with_root, 
     }
 }
 
-// one workgroup: S = I + V Y[:, 1:], w = V Y[:, 0]; Cholesky of S in place; w <- S^-1 w
+// one workgroup: S = I + V Y[:, R:], w = V Y[:, :R] (6 L x R, row-major); Cholesky of S in place; w <- S^-1 w
 __global__ __launch_bounds__(LOOPS_THREADS) void pgo_loops(Dev d, int it)
 {
     if (!active(d, it)) return;
-    const int n = 6 * d.L, M = d.M, T = LOOPS_THREADS, tid = threadIdx.x;
+    const int n = 6 * d.L, M = d.M, R = d.R, T = LOOPS_THREADS, tid = threadIdx.x;
     if (n == 0) return;
     double* S = d.S;
     double* w = d.w;
-    for (int e = tid; e < n * (n + 1); e += T) {
-        const int p = e / (n + 1), qq = e % (n + 1);              // qq == n: the right-hand side
-        const int l = p / 6, k = p % 6, col = qq == n ? 0 : 1 + qq;
+    for (int e = tid; e < n * (n + R); e += T) {
+        const int p = e / (n + R), qq = e % (n + R);              // qq >= n: a right-hand side
+        const int l = p / 6, k = p % 6, col = qq >= n ? qq - n : R + qq;
         const int2 ft = d.lidx[l];
         const double *Ya = d.Bm + 6 * (size_t)M * ft.x, *Yb = d.Bm + 6 * (size_t)M * ft.y;
         const double *Ja = d.JAl + 36 * (size_t)l + 6 * k, *Jb = d.JBl + 36 * (size_t)l + 6 * k;
         double v = 0.;
         for (int r = 0; r < 6; r++) v += Ja[r] * Ya[(size_t)r * M + col] + Jb[r] * Yb[(size_t)r * M + col];
-        if (qq == n) w[p] = v;
+        if (qq >= n) w[(size_t)p * R + (qq - n)] = v;
         else S[(size_t)p * n + qq] = v + (p == qq ? 1. : 0.);
     }
     __syncthreads();
@@ -293,19 +335,72 @@ __global__ __launch_bounds__(LOOPS_THREADS) void pgo_loops(Dev d, int it)
         __syncthreads();
     }
     for (int j = 0; j < n; j++) {                                 // L y = w
-        if (tid == 0) w[j] /= S[(size_t)j * n + j];
+        if (tid < R) w[(size_t)j * R + tid] /= S[(size_t)j * n + j];
         __syncthreads();
-        const double yj = w[j];
-        for (int p = j + 1 + tid; p < n; p += T) w[p] -= S[(size_t)p * n + j] * yj;
+        for (int e = tid; e < (n - j - 1) * R; e += T) {
+            const int p = j + 1 + e / R, c = e % R;
+            w[(size_t)p * R + c] -= S[(size_t)p * n + j] * w[(size_t)j * R + c];
+        }
         __syncthreads();
     }
     for (int j = n - 1; j >= 0; j--) {                            // L' z = y
-        if (tid == 0) w[j] /= S[(size_t)j * n + j];
+        if (tid < R) w[(size_t)j * R + tid] /= S[(size_t)j * n + j];
         __syncthreads();
-        const double zj = w[j];
-        for (int p = tid; p < j; p += T) w[p] -= S[(size_t)j * n + p] * zj;
+        for (int e = tid; e < j * R; e += T) {
+            const int p = e / R, c = e % R;
+            w[(size_t)p * R + c] -= S[(size_t)j * n + p] * w[(size_t)j * R + c];
+        }
         __syncthreads();
     }
+}
+
+// one workgroup, after a pass with R = 6: cov = the (ckey, ckey) block of T^-1 - T^-1 V' S^-1 V T^-1 = Y[:, :6] - Y[:, 6:] w at
+// the key's rows.  Without GPS factors T is the anchored system (key 0's block the identity, its right-hand sides zero), the
+// block is Sigma_rel, and the gauge part is added in closed form: A Sigma_0 A', A = Ad(X_k^-1 X_0), Sigma_0 = (Bp' W Bp)^-1 =
+// Bp^-1 diag(variances) Bp^-T from the unwhitened prior Jacobian, so 1e-8 never meets 1e6 in one matrix.
+__global__ __launch_bounds__(NB) void pgo_cov(Dev d)
+{
+    __shared__ double sA[36], sS0[36];
+    const int tid = threadIdx.x, M = d.M, n = 6 * d.L, k = d.ckey;
+    const bool fs = d.G > 0;
+    if (!fs && tid == 0) {
+        double r[6], B[36], Bi[36];
+        prior_error(d.X[0], d.Zc[0], d.full, r, B);
+        for (int c = 0; c < 6; c++) {                             // column c of Bp^-1
+            double Bc[36], x[6];
+            for (int q = 0; q < 36; q++) Bc[q] = B[q];
+            for (int q = 0; q < 6; q++) x[q] = q == c ? 1. : 0.;
+            solve6(Bc, x);
+            for (int q = 0; q < 6; q++) Bi[6 * q + c] = x[q];
+        }
+        for (int a = 0; a < 6; a++)
+            for (int b = 0; b < 6; b++) {
+                double s = 0.;
+                for (int m = 0; m < 6; m++) s += Bi[6 * a + m] * PRIOR_VAR[m] * Bi[6 * b + m];
+                sS0[6 * a + b] = s;
+            }
+        Pose Xi, Rel;
+        pose_inv(d.X[k], &Xi);
+        pose_mul(Xi, d.X[0], &Rel);
+        pose_adjoint(Rel, sA);
+    }
+    __syncthreads();
+    if (tid >= 36) return;
+    const int r = tid / 6, c = tid % 6;
+    const double* Y = d.Bm + 6 * (size_t)M * k;
+    double s = 0.;
+    for (int q = 0; q < n; q++) s += Y[(size_t)r * M + 6 + q] * d.w[(size_t)q * 6 + c];
+    double v = Y[(size_t)r * M + c] - s;
+    if (!fs) {
+        double g = 0.;
+        for (int a = 0; a < 6; a++) {
+            double t = 0.;
+            for (int b = 0; b < 6; b++) t += sS0[6 * a + b] * sA[6 * c + b];
+            g += sA[6 * r + a] * t;
+        }
+        v += g;
+    }
+    d.cov[tid] = v;
 }
 
 __global__ __launch_bounds__(NB) void pgo_update(Dev d, int it)
@@ -316,7 +411,7 @@ __global__ __launch_bounds__(NB) void pgo_update(Dev d, int it)
     bool bad = false;
     if (i < d.N) {
         double delta[6];
-        if (i == 0) {
+        if (i == 0 && d.G == 0) {
             for (int r = 0; r < 6; r++) delta[r] = d.delta0[r];
         } else {
             const double* Y = d.Bm + 6 * (size_t)M * i;
@@ -349,7 +444,7 @@ __global__ __launch_bounds__(NB) void pgo_update(Dev d, int it)
 __global__ __launch_bounds__(LOOPS_THREADS) void pgo_finish(Dev d, int which)
 {
     __shared__ double sh[LOOPS_THREADS];
-    const int tid = threadIdx.x, E = d.N + d.L;
+    const int tid = threadIdx.x, E = d.N + d.L + d.G;
     double s = 0.;
     for (int e = tid; e < E; e += LOOPS_THREADS) s += d.e2[e];
     sh[tid] = s;
@@ -388,25 +483,33 @@ struct lvi_pgo {
     Pose *h_X = nullptr, *h_Zc = nullptr, *h_Zl = nullptr, *h_out = nullptr;
     int2* h_lidx = nullptr; double* h_lsw = nullptr; lvi_pgo_info* h_info = nullptr;
     Pose* d_Zc = nullptr; Pose* d_Zl = nullptr; int2* d_lidx = nullptr; double* d_lsw = nullptr;
+    // GPS factors in the order they were added; the device holds them sorted by key (staged and sent by flush when they or N changed)
+    std::vector<int> g_key; std::vector<double> g_z, g_sw;
+    int g_up_G = 0, g_up_N = 0;
+    int *h_gkey = nullptr, *h_goff = nullptr; double *h_gz = nullptr, *h_gsw = nullptr, *h_cov = nullptr;
+    int *d_gkey = nullptr, *d_goff = nullptr; double *d_gz = nullptr, *d_gsw = nullptr;
 };
 
 namespace {
 
 template <class A> void carve(A& a, lvi_pgo* h)
 {
-    const size_t N = (size_t)h->Ncap, L = (size_t)std::max(h->Lcap, 1), M = 6 * (size_t)h->Lcap + 1, n6 = 6 * L;
+    const size_t N = (size_t)h->Ncap, L = (size_t)std::max(h->Lcap, 1), M = 6 * (size_t)h->Lcap + 6, n6 = 6 * L;
     Dev& d = h->d;
     d.X = a.template alloc<Pose>(N);
     h->d_Zc = a.template alloc<Pose>(N); h->d_Zl = a.template alloc<Pose>(L);
     h->d_lidx = a.template alloc<int2>(L); h->d_lsw = a.template alloc<double>(L);
     d.JAc = a.template alloc<double>(36 * N); d.JBc = a.template alloc<double>(36 * N); d.rc = a.template alloc<double>(6 * N);
     d.JAl = a.template alloc<double>(36 * L); d.JBl = a.template alloc<double>(36 * L); d.rl = a.template alloc<double>(6 * L);
-    d.e2 = a.template alloc<double>(N + L);
+    d.e2 = a.template alloc<double>(N + L + N);
     d.D = a.template alloc<double>(36 * N); d.Lo = a.template alloc<double>(36 * N); d.Up = a.template alloc<double>(36 * N);
     d.Bm = a.template alloc<double>(6 * N * M);
-    d.S = a.template alloc<double>(n6 * n6); d.w = a.template alloc<double>(n6);
+    d.S = a.template alloc<double>(n6 * n6); d.w = a.template alloc<double>(n6 * 6);
     d.delta0 = a.template alloc<double>(6); d.step = a.template alloc<double>(LVI_PGO_MAX_ITERS);
     d.info = a.template alloc<lvi_pgo_info>(1);
+    h->d_gkey = a.template alloc<int>(N); h->d_goff = a.template alloc<int>(N + 1);
+    h->d_gz = a.template alloc<double>(3 * N); h->d_gsw = a.template alloc<double>(3 * N);
+    d.JG = a.template alloc<double>(18 * N); d.rg = a.template alloc<double>(3 * N); d.cov = a.template alloc<double>(36);
 }
 
 // what add_pose / add_loop staged since the last flush goes to the device (stream order: ahead of whatever reads it)
@@ -425,6 +528,66 @@ void flush(lvi_pgo* h)
         LVI_HIP(hipMemcpyAsync(h->d_lsw + h->l_up, h->h_lsw + h->l_up, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
         h->l_up = h->L;
     }
+    const int G = (int)h->g_key.size();
+    if (G > 0 && (h->g_up_G != G || h->g_up_N != h->N)) {
+        // a stable counting sort by key: goff[i] .. goff[i + 1] are key i's factors, in the order they were added
+        int* off = h->h_goff;
+        for (int i = 0; i <= h->N; i++) off[i] = 0;
+        for (int g = 0; g < G; g++) off[h->g_key[g] + 1]++;
+        for (int i = 0; i < h->N; i++) off[i + 1] += off[i];
+        std::vector<int> next(off, off + h->N);
+        for (int g = 0; g < G; g++) {
+            const int at = next[h->g_key[g]]++;
+            h->h_gkey[at] = h->g_key[g];
+            for (int k = 0; k < 3; k++) { h->h_gz[3 * (size_t)at + k] = h->g_z[3 * (size_t)g + k]; h->h_gsw[3 * (size_t)at + k] = h->g_sw[3 * (size_t)g + k]; }
+        }
+        LVI_HIP(hipMemcpyAsync(h->d_gkey, h->h_gkey, sizeof(int) * (size_t)G, hipMemcpyHostToDevice, h->stream));
+        LVI_HIP(hipMemcpyAsync(h->d_goff, h->h_goff, sizeof(int) * (size_t)(h->N + 1), hipMemcpyHostToDevice, h->stream));
+        LVI_HIP(hipMemcpyAsync(h->d_gz, h->h_gz, sizeof(double) * 3 * (size_t)G, hipMemcpyHostToDevice, h->stream));
+        LVI_HIP(hipMemcpyAsync(h->d_gsw, h->h_gsw, sizeof(double) * 3 * (size_t)G, hipMemcpyHostToDevice, h->stream));
+        h->g_up_G = G; h->g_up_N = h->N;
+    }
+}
+
+// the device view of the graph as it stands, with R right-hand sides
+Dev view(lvi_pgo* h, int R)
+{
+    Dev d = h->d;
+    d.Zc = h->d_Zc; d.Zl = h->d_Zl; d.lidx = h->d_lidx; d.lsw = h->d_lsw;
+    d.gkey = h->d_gkey; d.goff = h->d_goff; d.gz = h->d_gz; d.gsw = h->d_gsw;
+    d.N = h->N; d.L = h->L; d.G = (int)h->g_key.size(); d.R = R; d.M = 6 * h->L + R; d.ckey = 0;
+    d.full = h->P.full_logmap; d.max_iters = h->P.max_iters; d.eps = h->P.conv_eps;
+    return d;
+}
+
+// the launches of one linear solve Y = T^-1 B and the loop system, step `it` (linearise is the caller's)
+struct Schedule { int n_wide = 0, s_tail = 1, n_tail = 0; };
+Schedule schedule(int N)
+{
+    // single-level launches while more than TAIL_KEYS keys survive a level, then one workgroup
+    Schedule c;
+    for (int st = 1; st < N; st *= 2) {
+        const int count = (N + 2 * st - 1) / (2 * st);
+        if (count > TAIL_KEYS && c.n_tail == 0) c.n_wide++;
+        else { if (c.n_tail == 0) c.s_tail = st; c.n_tail++; }
+    }
+    return c;
+}
+void enqueue_linear_solve(const Dev& d, const Schedule& c, int it, hipStream_t s)
+{
+    const int N = d.N, n_wide = c.n_wide, s_tail = c.s_tail, n_tail = c.n_tail;
+    hipLaunchKernelGGL(pgo_assemble, dim3(N), dim3(NB), 0, s, d, it);
+    int st = 1;
+    for (int k = 0; k < n_wide; k++, st *= 2)
+        hipLaunchKernelGGL(pgo_reduce, dim3((N + 2 * st - 1) / (2 * st)), dim3(NB), 0, s, d, it, st, 1);
+    if (n_tail > 0) hipLaunchKernelGGL(pgo_reduce, dim3(1), dim3(NB), 0, s, d, it, s_tail, n_tail);
+    // downwards: the root and the tail levels in one workgroup, then the wide levels
+    const int s_top = n_tail > 0 ? s_tail << (n_tail - 1) : 0;
+    hipLaunchKernelGGL(pgo_backsub, dim3(1), dim3(NB), 0, s, d, it, 1, s_top, n_tail);
+    st = n_wide > 0 ? 1 << (n_wide - 1) : 0;
+    for (int k = 0; k < n_wide; k++, st /= 2)
+        hipLaunchKernelGGL(pgo_backsub, dim3(((N - 1) / st + 1) / 2), dim3(NB), 0, s, d, it, 0, st, 1);
+    if (d.L > 0) hipLaunchKernelGGL(pgo_loops, dim3(1), dim3(LOOPS_THREADS), 0, s, d, it);
 }
 
 bool params_ok(const lvi_pgo_params& p)
@@ -470,6 +633,11 @@ int32_t lvi_pgo_create(int32_t device, int32_t max_poses, int32_t max_loops, lvi
         LVI_HIP(hipHostMalloc((void**)&h->h_lidx, sizeof(int2) * L, hipHostMallocDefault));
         LVI_HIP(hipHostMalloc((void**)&h->h_lsw, sizeof(double) * L, hipHostMallocDefault));
         LVI_HIP(hipHostMalloc((void**)&h->h_info, align256(sizeof(lvi_pgo_info)), hipHostMallocDefault));
+        LVI_HIP(hipHostMalloc((void**)&h->h_gkey, sizeof(int) * N, hipHostMallocDefault));
+        LVI_HIP(hipHostMalloc((void**)&h->h_goff, sizeof(int) * (N + 1), hipHostMallocDefault));
+        LVI_HIP(hipHostMalloc((void**)&h->h_gz, sizeof(double) * 3 * N, hipHostMallocDefault));
+        LVI_HIP(hipHostMalloc((void**)&h->h_gsw, sizeof(double) * 3 * N, hipHostMallocDefault));
+        LVI_HIP(hipHostMalloc((void**)&h->h_cov, align256(sizeof(double) * 36), hipHostMallocDefault));
         return LVI_OK;
     });
     if (st != LVI_OK) { lvi_pgo_destroy(h); return st; }
@@ -483,7 +651,8 @@ void lvi_pgo_destroy(lvi_pgo* h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->arena.release();
-    for (void* p : {(void*)h->h_X, (void*)h->h_Zc, (void*)h->h_out, (void*)h->h_Zl, (void*)h->h_lidx, (void*)h->h_lsw, (void*)h->h_info})
+    for (void* p : {(void*)h->h_X, (void*)h->h_Zc, (void*)h->h_out, (void*)h->h_Zl, (void*)h->h_lidx, (void*)h->h_lsw, (void*)h->h_info,
+                    (void*)h->h_gkey, (void*)h->h_goff, (void*)h->h_gz, (void*)h->h_gsw, (void*)h->h_cov})
         if (p) (void)hipHostFree(p);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -495,6 +664,8 @@ int32_t lvi_pgo_clear(lvi_pgo* h)
     return guarded(h->device, [&]() -> int32_t {
         LVI_HIP(hipStreamSynchronize(h->stream));
         h->N = h->L = h->n_up = h->l_up = 0;
+        h->g_key.clear(); h->g_z.clear(); h->g_sw.clear();
+        h->g_up_G = h->g_up_N = 0;
         return LVI_OK;
     });
 }
@@ -557,34 +728,15 @@ int32_t lvi_pgo_solve(lvi_pgo* h, lvi_pgo_info* info_out)
     if (h->N == 0) return fail(LVI_ERR_STATE, "no poses");
     return guarded(h->device, [&]() -> int32_t {
         flush(h);
-        Dev d = h->d;
-        d.Zc = h->d_Zc; d.Zl = h->d_Zl; d.lidx = h->d_lidx; d.lsw = h->d_lsw;
-        d.N = h->N; d.L = h->L; d.M = 6 * h->L + 1; d.full = h->P.full_logmap; d.max_iters = h->P.max_iters; d.eps = h->P.conv_eps;
-        const int N = d.N, E = d.N + d.L;
+        const Dev d = view(h, 1);
+        const int N = d.N, E = d.N + d.L + d.G;
         hipStream_t s = h->stream;
         LVI_HIP(hipMemsetAsync(d.step, 0, sizeof(double) * LVI_PGO_MAX_ITERS, s));
-        // the reduction's schedule: single-level launches while more than TAIL_KEYS keys survive a level, then one workgroup
-        int n_wide = 0, s_tail = 1, n_tail = 0;
-        for (int st = 1; st < N; st *= 2) {
-            const int count = (N + 2 * st - 1) / (2 * st);
-            if (count > TAIL_KEYS && n_tail == 0) n_wide++;
-            else { if (n_tail == 0) s_tail = st; n_tail++; }
-        }
+        const Schedule c = schedule(N);
         for (int it = 0; it < d.max_iters; it++) {
             hipLaunchKernelGGL(pgo_linearise, dim3(div_up(E, NB)), dim3(NB), 0, s, d, it, 0);
             if (it == 0) hipLaunchKernelGGL(pgo_finish, dim3(1), dim3(LOOPS_THREADS), 0, s, d, 0);
-            hipLaunchKernelGGL(pgo_assemble, dim3(N), dim3(NB), 0, s, d, it);
-            int st = 1;
-            for (int k = 0; k < n_wide; k++, st *= 2)
-                hipLaunchKernelGGL(pgo_reduce, dim3((N + 2 * st - 1) / (2 * st)), dim3(NB), 0, s, d, it, st, 1);
-            if (n_tail > 0) hipLaunchKernelGGL(pgo_reduce, dim3(1), dim3(NB), 0, s, d, it, s_tail, n_tail);
-            // downwards: the root and the tail levels in one workgroup, then the wide levels
-            const int s_top = n_tail > 0 ? s_tail << (n_tail - 1) : 0;
-            hipLaunchKernelGGL(pgo_backsub, dim3(1), dim3(NB), 0, s, d, it, 1, s_top, n_tail);
-            st = n_wide > 0 ? 1 << (n_wide - 1) : 0;
-            for (int k = 0; k < n_wide; k++, st /= 2)
-                hipLaunchKernelGGL(pgo_backsub, dim3(((N - 1) / st + 1) / 2), dim3(NB), 0, s, d, it, 0, st, 1);
-            if (d.L > 0) hipLaunchKernelGGL(pgo_loops, dim3(1), dim3(LOOPS_THREADS), 0, s, d, it);
+            enqueue_linear_solve(d, c, it, s);
             hipLaunchKernelGGL(pgo_update, dim3(div_up(N, NB)), dim3(NB), 0, s, d, it);
             LVI_HIP(hipGetLastError());
         }
@@ -611,6 +763,52 @@ int32_t lvi_pgo_get_poses(lvi_pgo* h, int32_t first, int32_t count, double* T, f
             if (T) pose_to_matrix(h->h_out[i], T + 16 * (size_t)i);
             if (rpyxyz) pose_to_rpyxyz(h->h_out[i], rpyxyz + 6 * (size_t)i);
         }
+        return LVI_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------------------------- include/lvi_pgo_gps.h
+int32_t lvi_pgo_gps_abi_version(void) { return LVI_PGO_GPS_ABI_VERSION; }
+
+int32_t lvi_pgo_gps_add(lvi_pgo* h, int32_t key, const float xyz[3], const float variance[3])
+{
+    if (!h || !xyz || !variance) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    if (key < 0 || key >= h->N) return fail(LVI_ERR_INVALID_ARG, "the GPS factor's key must lie inside the keys added");
+    for (int k = 0; k < 3; k++) {
+        if (!std::isfinite(xyz[k])) return fail(LVI_ERR_INVALID_ARG, "a GPS coordinate is not finite");
+        if (!(variance[k] > 0.f) || !std::isfinite(variance[k])) return fail(LVI_ERR_INVALID_ARG, "variance must be positive and finite");
+    }
+    if ((int)h->g_key.size() >= h->Ncap) return fail(LVI_ERR_CAPACITY, "more GPS factors than max_poses");
+    h->g_key.push_back(key);
+    for (int k = 0; k < 3; k++) { h->g_z.push_back((double)xyz[k]); h->g_sw.push_back(1. / std::sqrt((double)variance[k])); }
+    return LVI_OK;
+}
+
+int32_t lvi_pgo_gps_count(lvi_pgo* h, int32_t* n_gps)
+{
+    if (!h) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    if (n_gps) *n_gps = (int32_t)h->g_key.size();
+    return LVI_OK;
+}
+
+int32_t lvi_pgo_gps_marginal_covariance(lvi_pgo* h, int32_t key, double cov[36])
+{
+    if (!h || !cov) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    if (h->N == 0) return fail(LVI_ERR_STATE, "no poses");
+    if (key < 0 || key >= h->N) return fail(LVI_ERR_INVALID_ARG, "key outside the keys added");
+    return guarded(h->device, [&]() -> int32_t {
+        flush(h);
+        Dev d = view(h, 6);
+        d.ckey = key;
+        hipStream_t s = h->stream;
+        // step 0 is always active, and neither step[] nor a pose is written: the pass ends at the loop system
+        hipLaunchKernelGGL(pgo_linearise, dim3(div_up(d.N + d.L + d.G, NB)), dim3(NB), 0, s, d, 0, 0);
+        enqueue_linear_solve(d, schedule(d.N), 0, s);
+        hipLaunchKernelGGL(pgo_cov, dim3(1), dim3(NB), 0, s, d);
+        LVI_HIP(hipGetLastError());
+        LVI_HIP(hipMemcpyAsync(h->h_cov, d.cov, sizeof(double) * 36, hipMemcpyDeviceToHost, s));
+        LVI_HIP(hipStreamSynchronize(s));                            // the call's one wait
+        std::memcpy(cov, h->h_cov, sizeof(double) * 36);
         return LVI_OK;
     });
 }

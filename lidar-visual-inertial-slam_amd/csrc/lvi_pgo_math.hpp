@@ -238,6 +238,15 @@ LVI_PGO_HD void between_error(const Pose& Xi, const Pose& Xj, const Pose& Z, int
     mat6_mul(B, Ad, A);
     for (int i = 0; i < 36; i++) A[i] = -A[i];
 }
+// GPSFactor(key, z) (include/lvi_pgo_gps.h): r = X.translation() - z; J = d r / d delta_X = [0 | R], 3x6 row-major, in both
+// charts (the translation of X * Retract(delta) is t + R v + O(|delta|^2) whichever chart Retract is)
+LVI_PGO_HD void gps_error(const Pose& X, const double z[3], double r[3], double J[18])
+{
+    for (int i = 0; i < 3; i++) {
+        r[i] = X.t[i] - z[i];
+        for (int j = 0; j < 3; j++) { J[6 * i + j] = 0.; J[6 * i + 3 + j] = X.R[3 * i + j]; }
+    }
+}
 // X <- X * Retract(delta)
 LVI_PGO_HD void pose_retract(Pose* X, const double delta[6], int full)
 {

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/lvi_hotpath.h"
+#include "lvi_gps_gate.hpp"
 
 namespace lvi_host {
 
@@ -187,7 +188,8 @@ private:
 // Key POSES are a few thousand points: host work.  Key CLOUDS never leave the device (lvi_keyframe_*, lvi_map_*).
 // With only the prior and odometry factors the newest estimate of iSAM2 is the scan-matching result, which is what is
 // pushed here ("odometry chain").  Loop closures are applied when a pose graph is installed (usePoseGraph; PoseGraphHook
-// below); GPS factors are out of scope.
+// below), and GPS factors (addGPSFactor, :1430-1507) when useGps is called on top of it: the decisions are GpsGate's
+// (lvi_gps_gate.hpp), the factor and the covariance that gates it the graph's (include/lvi_pgo_gps.h).
 struct Affine3f { float m[3][4]; };            // Eigen::Affine3f: linear part | translation
 inline Affine3f getTransformation(float x, float y, float z, float roll, float pitch, float yaw)      // pcl::getTransformation
 {
@@ -283,6 +285,10 @@ public:
     virtual int addLoopFactor() = 0;                                         // drains the queued constraints; how many were added
     virtual void update() = 0;
     virtual void estimate(int first, int count, float* rpyxyz) = 0;          // isamCurrentEstimate.at<Pose3>(first ...)
+    // GPSFactor(key, xyz, Variances(variance)) (:1497-1499) and isam->marginalCovariance(key) (:1591; row-major 6x6, false when
+    // the graph has none).  Not pure: a hook written before GPS factors existed stays a hook, and does nothing with them.
+    virtual void addGpsFactor(int key, const float xyz[3], const float variance[3]) { (void)key; (void)xyz; (void)variance; }
+    virtual bool marginalCovariance(int key, double cov[36]) { (void)key; (void)cov; return false; }
 };
 
 class MapOptimizationNode {
@@ -297,6 +303,18 @@ public:
         if (pg && pg->size() != (int)cloudKeyPoses3D.size()) throw Error(LVI_ERR_STATE, "usePoseGraph: the graph and the key poses differ in length");
         pg_ = pg;
     }
+    // GPS (gpsHandler :334-337, addGPSFactor :1430-1507, poseCovariance :1591): with a pose graph installed, saveKeyFramesAndFactor
+    // asks the gate between the odometry and the loop factors, solves when a loop OR a GPS factor was added, and then stores the
+    // newest key's marginal covariance, which gates the next key's fix.  Without useGps every answer of the node is what it was.
+    void useGps(const GpsSettings& s) { gpsGate.S = s; gpsInUse_ = true; }
+    void gpsHandler(double stamp, const double xyz[3], const double cov_xyz[3])
+    {
+        gpsGate.gpsHandler(GpsMessage{stamp, xyz[0], xyz[1], xyz[2], cov_xyz[0], cov_xyz[1], cov_xyz[2]});
+    }
+    bool gpsInUse() const { return gpsInUse_; }
+    GpsGate gpsGate;
+    double poseCovariance[36] = {};            // row-major, tangent order rotation then translation (:1591)
+    int gpsFactorsAdded = 0;
     bool aLoopIsClosed = false;
     int posesCorrected = 0;                    // how often correctPoses rewrote the key poses
     MapCallerParams P;
@@ -410,7 +428,7 @@ public:
     {
         float pose[6];
         for (int k = 0; k < 6; k++) pose[k] = pose_in[k];
-        addFactors(pose);
+        addFactors(pose, time);
         int32_t idx = -1;
         check(lvi_keyframe_add(h_.get(), cornerDS, nc, surfDS, ns, pose, &idx), "lvi_keyframe_add");
         if (idx != (int32_t)cloudKeyPoses3D.size()) throw Error(LVI_ERR_STATE, "keyframe store out of step with the key poses");
@@ -441,7 +459,7 @@ public:
     {
         lastSavedKeyFrame = false;
         if (!saveFrame()) return;
-        addFactors(transformTobeMapped);                                                  // :1537-1573
+        addFactors(transformTobeMapped, timeLaserInfoCur);                                // :1537-1573
         lvi_pt thisPose3D{transformTobeMapped[3], transformTobeMapped[4], transformTobeMapped[5], (float)cloudKeyPoses3D.size()};
         PointTypePose thisPose6D{thisPose3D.x, thisPose3D.y, thisPose3D.z, thisPose3D.intensity,
                                  transformTobeMapped[0], transformTobeMapped[1], transformTobeMapped[2], timeLaserInfoCur};
@@ -472,10 +490,11 @@ public:
     }
     double laserTime() const { return timeLaserInfoCur; }                                  // stamp of the last scan taken (the loop thread's time rule)
 private:
-    // addOdomFactor, addLoopFactor, the updates and the newest estimate (:1537-1573) for the key about to be pushed with `pose`
-    // (in: the scan-matching result; out: the graph's estimate of it).  The graph is solved only when a loop was added: a new
-    // key hangs on one factor, which its initial estimate satisfies, so the minimiser of the other keys does not move.
-    void addFactors(float pose[6])
+    // addOdomFactor, addGPSFactor, addLoopFactor, the updates and the newest estimate (:1537-1573) for the key about to be pushed
+    // with `pose` (in: the scan-matching result; out: the graph's estimate of it) at the scan's stamp.  The graph is solved only
+    // when a loop or a GPS factor was added: a new key hangs on one factor, which its initial estimate satisfies, so the
+    // minimiser of the other keys does not move.
+    void addFactors(float pose[6], double stamp)
     {
         if (!pg_) return;
         if (pg_->size() != (int)cloudKeyPoses3D.size()) throw Error(LVI_ERR_STATE, "pose graph out of step with the key poses");
@@ -486,13 +505,28 @@ private:
             const float from[6] = {b.roll, b.pitch, b.yaw, b.x, b.y, b.z};
             pg_->addOdomFactor(from, pose);
         }
-        if (pg_->addLoopFactor() > 0) {
+        const int key = (int)cloudKeyPoses3D.size();
+        bool gpsAdded = false;
+        if (gpsInUse_) {                                                                  // addGPSFactor (:1430-1507): the key poses before the new key is pushed
+            GpsFactor f;
+            const lvi_pt *fr = cloudKeyPoses3D.empty() ? nullptr : &cloudKeyPoses3D.front(), *bk = cloudKeyPoses3D.empty() ? nullptr : &cloudKeyPoses3D.back();
+            const float front[3] = {fr ? fr->x : 0.f, fr ? fr->y : 0.f, fr ? fr->z : 0.f}, back[3] = {bk ? bk->x : 0.f, bk ? bk->y : 0.f, bk ? bk->z : 0.f};
+            if (gpsGate.addGPSFactor(stamp, fr ? front : nullptr, bk ? back : nullptr, poseCovariance[6 * 3 + 3], poseCovariance[6 * 4 + 4], pose[5], &f)) {
+                pg_->addGpsFactor(key, f.xyz, f.variance);
+                gpsFactorsAdded++;
+                gpsAdded = true;
+            }
+        }
+        if (pg_->addLoopFactor() > 0 || gpsAdded) {
             aLoopIsClosed = true;
             pg_->update();
-            pg_->estimate((int)cloudKeyPoses3D.size(), 1, pose);
+            pg_->estimate(key, 1, pose);
         }
+        if (gpsInUse_ && !pg_->marginalCovariance(key, poseCovariance))                   // :1591
+            throw Error(LVI_ERR_STATE, "useGps: the pose graph has no marginal covariance");
     }
     PoseGraphHook* pg_ = nullptr;
+    bool gpsInUse_ = false;
     void applyIncrement(const Affine3f& transIncre)
     {
         const Affine3f transTobe = getTransformation(transformTobeMapped[3], transformTobeMapped[4], transformTobeMapped[5],

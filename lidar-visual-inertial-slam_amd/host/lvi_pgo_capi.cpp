@@ -74,6 +74,37 @@ int32_t lvh_pgo_last(void* p, lvi_pgo_info* info, float pose_to[6], int32_t coun
     return LVI_OK;
 }
 
+// MapOptimizationNode::useGps with the settings of utility.h:178-183
+int32_t lvh_seq_use_gps(lvh_seq* s, int32_t use_gps_elevation, float gps_cov_threshold, float pose_cov_threshold)
+{
+    if (!s) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    return guarded([&]() -> int32_t {
+        GpsSettings g;
+        g.useGpsElevation = use_gps_elevation != 0; g.gpsCovThreshold = gps_cov_threshold; g.poseCovThreshold = pose_cov_threshold;
+        static_cast<MapOptimizationNode*>(lvh_seq_node(s))->useGps(g);
+        return LVI_OK;
+    });
+}
+
+// gpsHandler (:334-337): the stamp, pose.pose.position and pose.covariance[0], [7], [14] of one message; returns the queue's length
+int32_t lvh_seq_gps_push(lvh_seq* s, double stamp, const double xyz[3], const double cov_xyz[3])
+{
+    if (!s || !xyz || !cov_xyz) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    MapOptimizationNode* n = static_cast<MapOptimizationNode*>(lvh_seq_node(s));
+    n->gpsHandler(stamp, xyz, cov_xyz);
+    return (int32_t)n->gpsGate.gpsQueue.size();
+}
+
+// poseCovariance (:1591; row-major 6x6, may be NULL) and counters [3]: GPS factors added, messages still queued, GPS in use
+int32_t lvh_seq_gps_last(lvh_seq* s, double cov[36], int32_t counters[3])
+{
+    if (!s) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    const MapOptimizationNode* n = static_cast<MapOptimizationNode*>(lvh_seq_node(s));
+    if (cov) std::memcpy(cov, n->poseCovariance, sizeof(n->poseCovariance));
+    if (counters) { counters[0] = n->gpsFactorsAdded; counters[1] = (int32_t)n->gpsGate.gpsQueue.size(); counters[2] = n->gpsInUse() ? 1 : 0; }
+    return LVI_OK;
+}
+
 // MapOptimizationNode::posesCorrected / aLoopIsClosed
 int32_t lvh_seq_poses_corrected(lvh_seq* s)
 {

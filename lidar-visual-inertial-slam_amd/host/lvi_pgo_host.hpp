@@ -7,13 +7,15 @@
 //   estimate        :1567-1599, :1627-1640          isamCurrentEstimate.at<Pose3>(i) as (roll, pitch, yaw, x, y, z) floats
 //
 // The caller moves what LoopCloser::loopQueue holds into pushLoop / takeLoops (under its queue lock), as the reference's
-// loop thread fills the three queues.  GPS factors are not restated.  Only liblvi_hip.so exports this ABI, so only code
+// loop thread fills the three queues.  GPS: addGpsFactor (the GPSFactor of :1497-1499) and marginalCovariance (:1591) over
+// include/lvi_pgo_gps.h; the decisions of addGPSFactor are the node's GpsGate (lvi_gps_gate.hpp).  Only liblvi_hip.so exports this ABI, so only code
 // linked against it may include this header.  Parity is with the minimiser of the graph's cost, not with
 // iSAM2's iterate.
 #pragma once
 #include <deque>
 
 #include "../../include/lvi_pgo.h"
+#include "../../include/lvi_pgo_gps.h"
 #include "lvi_loop_host.hpp"
 
 namespace lvi_host {
@@ -33,7 +35,7 @@ public:
     std::deque<LoopConstraint> loopQueue;        // pushed by the caller, drained by addLoopFactor
     lvi_pgo_info lastInfo{};                     // of the last update
     int32_t lastStatus = LVI_OK;                 // LVI_OK or LVI_PGO_NOT_CONVERGED
-    int updates = 0, loopsAdded = 0;
+    int updates = 0, loopsAdded = 0, gpsAdded = 0;
     float lastPoseTo[6] = {};                    // poseTo of the last addOdomFactor
 
     void pushLoop(const LoopConstraint& c) { loopQueue.push_back(c); }
@@ -67,6 +69,16 @@ public:
     {
         lastStatus = check(lvi_pgo_solve(g_, &lastInfo), "lvi_pgo_solve");
         updates++;
+    }
+    void addGpsFactor(int key, const float xyz[3], const float variance[3]) override
+    {
+        check(lvi_pgo_gps_add(g_, key, xyz, variance), "lvi_pgo_gps_add");
+        gpsAdded++;
+    }
+    bool marginalCovariance(int key, double cov[36]) override
+    {
+        check(lvi_pgo_gps_marginal_covariance(g_, key, cov), "lvi_pgo_gps_marginal_covariance");
+        return true;
     }
     void estimate(int first, int count, float* rpyxyz) override { check(lvi_pgo_get_poses(g_, first, count, nullptr, rpyxyz), "lvi_pgo_get_poses"); }
 

@@ -13,7 +13,9 @@
 // updates and correctPoses (:1414-1428, 1509-1527, 1546-1599, 1615-1646) run through lvi_host::PoseGraphBackend
 // (include/lvi_pgo.h: the minimiser of the graph's cost on the MI355X, not iSAM2's iterate), and the path is rebuilt after
 // a correction (:1641-1645).  Without it the key pose pushed is the scan-matching result ("odometry chain"), which does not
-// consume the constraint queue.  GPS factors are not reproduced.
+// consume the constraint queue.  With the pose graph the node also subscribes to gpsTopic (:172-174): gpsHandler (:334-337)
+// forwards each message to lvi_host::MapOptimizationNode::gpsHandler, whose GpsGate (host/lvi_gps_gate.hpp) restates
+// addGPSFactor (:1430-1507) over include/lvi_pgo_gps.h with useGpsElevation, gpsCovThreshold and poseCovThreshold.
 // Builds only where rclcpp, tf2_ros, pcl_conversions and the lidar_odometry messages / services exist.
 #include <cstdlib>
 #include <deque>
@@ -64,6 +66,7 @@ class mapOptimization : public ParamServer {
     rclcpp::Publisher<visualization_msgs::msg::MarkerArray>::SharedPtr pubLoopConstraintEdge;
     rclcpp::Subscription<std_msgs::msg::Float64MultiArray>::SharedPtr subLoop;
     rclcpp::Subscription<lidar_odometry::msg::CloudInfo>::SharedPtr subCloud;
+    rclcpp::Subscription<nav_msgs::msg::Odometry>::SharedPtr subGPS;
     rclcpp::Service<lidar_odometry::srv::SaveMap>::SharedPtr srvSaveMap;
     std::unique_ptr<tf2_ros::TransformBroadcaster> br;
     std::mutex mtx;               // the node's state and every call on the handle but lvi_gmap_result / lvi_gmap_fetch / lvi_loop_result / lvi_loop_fetch
@@ -118,6 +121,16 @@ public:
         if (declare_parameter<bool>("use_device_pose_graph", false)) {
             poseGraph = std::make_unique<lvi_host::PoseGraphBackend>(0, p.max_keyframes, LVI_PGO_MAX_LOOPS);
             mo->usePoseGraph(poseGraph.get());
+            lvi_host::GpsSettings gs;
+            gs.useGpsElevation = useGpsElevation; gs.gpsCovThreshold = gpsCovThreshold; gs.poseCovThreshold = poseCovThreshold;
+            mo->useGps(gs);
+            subGPS = create_subscription<nav_msgs::msg::Odometry>(                                                       // :172-174
+                gpsTopic, 200, [this](const nav_msgs::msg::Odometry::SharedPtr m) {
+                    const double xyz[3] = {m->pose.pose.position.x, m->pose.pose.position.y, m->pose.pose.position.z};
+                    const double cov[3] = {m->pose.covariance[0], m->pose.covariance[7], m->pose.covariance[14]};
+                    std::lock_guard<std::mutex> lock(mtx);
+                    mo->gpsHandler(stamp2Sec(m->header.stamp), xyz, cov);                                                // :334-337
+                });
         }
         pubHistoryKeyFrames = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/icp_loop_closure_history_cloud", 1);   // :239
         pubIcpKeyFrames = create_publisher<sensor_msgs::msg::PointCloud2>("lio_sam/mapping/icp_loop_closure_history_cloud", 1);       // :240 (the same topic, as written)

@@ -193,6 +193,9 @@ class HostLibrary:
             d.lvh_pgo_push_loop.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_float]
             d.lvh_pgo_last.argtypes = [C.c_void_p, C.POINTER(PgoInfo), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
             d.lvh_seq_poses_corrected.argtypes = [C.c_void_p]
+            d.lvh_seq_use_gps.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float]
+            d.lvh_seq_gps_push.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+            d.lvh_seq_gps_last.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         self.has_rig = hasattr(d, "lvh_rig_create")      # the HIP host library only
         if self.has_rig:
             d.lvh_rig_last_error.restype = C.c_char_p
@@ -292,6 +295,28 @@ class SequentialMapper:
         if code < 0:
             raise A.LviError(code, "lvh_seq_use_pose_graph", self.hl.dll.lvh_pgo_last_error().decode(errors="replace"))
         self._pg = backend                                               # keeps it alive while installed
+
+    def useGps(self, use_gps_elevation=False, gps_cov_threshold=2.0, pose_cov_threshold=25.0):
+        """MapOptimizationNode::useGps (addGPSFactor, mapOptimization.cpp:1430-1507, with the settings of utility.h:178-183; the
+        keyword arguments are config.load_gps_yaml's): on top of usePoseGraph, a key may take one GPS factor from the messages
+        pushed with gpsHandler, and the newest key's marginal covariance is stored after every key"""
+        if not self.hl.has_pgo:
+            raise RuntimeError("this host library has no pose-graph back end (only the one linked against liblvi_hip.so has)")
+        code = self.hl.dll.lvh_seq_use_gps(self._s, int(bool(use_gps_elevation)), float(gps_cov_threshold), float(pose_cov_threshold))
+        if code < 0:
+            raise A.LviError(code, "lvh_seq_use_gps", self.hl.dll.lvh_pgo_last_error().decode(errors="replace"))
+
+    def gpsHandler(self, stamp, xyz, cov_xyz):
+        """gpsHandler (:334-337): one odometry message's stamp, position and covariance[0], [7], [14] -> the queue's length"""
+        z = (C.c_double * 3)(*[float(v) for v in xyz])
+        c = (C.c_double * 3)(*[float(v) for v in cov_xyz])
+        return int(self.hl.dll.lvh_seq_gps_push(self._s, float(stamp), z, c))
+
+    def gps_last(self):
+        """dict(pose_covariance [6, 6] (:1591), factors_added, queued, in_use)"""
+        cov, cnt = np.zeros(36, np.float64), (C.c_int32 * 3)()
+        self.hl.dll.lvh_seq_gps_last(self._s, cov.ctypes.data_as(C.POINTER(C.c_double)), cnt)
+        return dict(pose_covariance=cov.reshape(6, 6), factors_added=cnt[0], queued=cnt[1], in_use=bool(cnt[2]))
 
     def poses_corrected(self):
         """how often correctPoses rewrote the key poses"""
@@ -773,8 +798,8 @@ class HostPnPRansac:
 
 
 class PoseGraphBackend:
-    """lvi_host::PoseGraphBackend (host/lvi_pgo_host.hpp): mapOptimization's factor graph without GPS over
-    include/lvi_pgo.h.  HIP host library only.  Install it with SequentialMapper.usePoseGraph and feed it what
+    """lvi_host::PoseGraphBackend (host/lvi_pgo_host.hpp): mapOptimization's factor graph over include/lvi_pgo.h and
+    include/lvi_pgo_gps.h (graph.add_gps, graph.gps_count, graph.marginal_covariance).  HIP host library only.  Install it with SequentialMapper.usePoseGraph and feed it what
     LoopCloser.pop() returns.  `graph` is a pgo.PoseGraph view of the handle the C++ side owns."""
 
     def __init__(self, hostlib, abi_lib, device=0, max_poses=4096, max_loops=64, full_logmap=-1, max_iters=0, conv_eps=0.0):
@@ -811,6 +836,18 @@ class PoseGraphBackend:
         if n < 0:
             raise A.LviError(n, "lvh_pgo_push_loop", self.hl.dll.lvh_pgo_last_error().decode(errors="replace"))
         return n
+
+    def add_gps(self, key, xyz, variance):
+        """GPSFactor(key, xyz, Variances(variance)) on the graph the C++ side owns (include/lvi_pgo_gps.h); the node's GpsGate adds
+        its own through MapOptimizationNode::useGps"""
+        self.graph.add_gps(key, xyz, variance)
+
+    def gps_count(self):
+        return self.graph.gps_count()
+
+    def marginal_covariance(self, key):
+        """isam->marginalCovariance(key) (mapOptimization.cpp:1591) -> [6, 6] float64"""
+        return self.graph.marginal_covariance(key)
 
     def last(self):
         """dict(updates, loops_added, loops_queued, status, info of the last update, pose_to of the last addOdomFactor)"""

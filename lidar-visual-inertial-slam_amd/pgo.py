@@ -1,6 +1,7 @@
-"""Python handle over include/lvi_pgo.h: mapOptimization's factor graph without GPS (addOdomFactor, addLoopFactor,
-isam->update and the estimate read-back; mapOptimization.cpp:1414-1428, 1509-1527, 1546-1599) on the GPU, as the
-minimiser of the same cost — a restatement of GTSAM's conventions, DESIGN §18.
+"""Python handle over include/lvi_pgo.h and include/lvi_pgo_gps.h: mapOptimization's factor graph (addOdomFactor,
+addGPSFactor's factor, addLoopFactor, isam->update, the estimate read-back and the marginal covariance that gates GPS;
+mapOptimization.cpp:1414-1428, 1430-1507, 1509-1527, 1546-1599) on the GPU, as the minimiser of the same cost — a
+restatement of GTSAM's conventions, DESIGN §18 and §19.
 
 A separate ABI from include/lvi_hotpath.h: only the product library exports it, so its signature table lives here and
 is bound against ``liblvi_hip.so`` alone."""
@@ -41,9 +42,19 @@ PGO_SIGNATURES = {
 }
 
 
+# the same for include/lvi_pgo_gps.h, a separate header with its own version
+PGO_GPS_SIGNATURES = {
+    "lvi_pgo_gps_abi_version": (_i32, []),
+    "lvi_pgo_gps_add": (_i32, [_vp, _i32, _P(_f32), _P(_f32)]),
+    "lvi_pgo_gps_count": (_i32, [_vp, _P(_i32)]),
+    "lvi_pgo_gps_marginal_covariance": (_i32, [_vp, _i32, _P(C.c_double)]),
+}
+
+
 def bind(lib):
     """set the pgo signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
-    return lib.bind(PGO_SIGNATURES)
+    lib.bind(PGO_SIGNATURES)
+    return lib.bind(PGO_GPS_SIGNATURES)
 
 
 def _pose6(p):
@@ -103,6 +114,23 @@ class PoseGraph:
     def add_loop(self, frm, to, between, variance):
         b = np.ascontiguousarray(between, np.float64).reshape(16)
         self.lib.check(self.lib.dll.lvi_pgo_add_loop(self._h, int(frm), int(to), b.ctypes.data_as(_P(C.c_double)), float(variance)), "lvi_pgo_add_loop")
+
+    def add_gps(self, key, xyz, variance):
+        """GPSFactor(key, xyz, Variances(variance)) (mapOptimization.cpp:1497-1499); the variances are taken as they are"""
+        z = (C.c_float * 3)(*[float(v) for v in np.asarray(xyz, np.float32).reshape(3)])
+        v = (C.c_float * 3)(*[float(x) for x in np.asarray(variance, np.float32).reshape(3)])
+        self.lib.check(self.lib.dll.lvi_pgo_gps_add(self._h, int(key), z, v), "lvi_pgo_gps_add")
+
+    def gps_count(self):
+        n = C.c_int32(0)
+        self.lib.check(self.lib.dll.lvi_pgo_gps_count(self._h, C.byref(n)), "lvi_pgo_gps_count")
+        return n.value
+
+    def marginal_covariance(self, key):
+        """isam->marginalCovariance(key) (:1591) at the current poses -> [6, 6] float64, tangent order rotation, translation"""
+        c = np.zeros(36, np.float64)
+        self.lib.check(self.lib.dll.lvi_pgo_gps_marginal_covariance(self._h, int(key), c.ctypes.data_as(_P(C.c_double))), "lvi_pgo_gps_marginal_covariance")
+        return c.reshape(6, 6)
 
     def solve(self):
         """-> dict(status, iterations, converged, chi2_before, chi2_after, max_step); status NOT_CONVERGED is soft"""

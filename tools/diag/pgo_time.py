@@ -3,7 +3,10 @@ circuit: wall clock around lvi_pgo_solve (the whole Gauss-Newton run: every laun
 steps behind the converged one return at once; one wait), with the graph rebuilt before every call so that each solve
 starts from the odometry chain.  Beside it, on the CPU, the linear systems of the same Gauss-Newton run (the reference's
 anchored normal equations, tests/pgo_ref.py) solved by scipy's sparse SuperLU without pivoting — the factor-and-solve
-time alone, without the Python linearisation.  Prints one JSON line.  Kernel times come from a separate rocprofv3 run:
+time alone, without the Python linearisation.  Two more measurements on the same circuit (include/lvi_pgo_gps.h): the wall
+clock of one lvi_pgo_gps_marginal_covariance call at the newest key of the solved graph (what the node pays per keyframe
+when GPS is in use), without GPS factors and with them, and one GPS-mode solve with a fix every --gps-every keys (the full
+system: key 0 live).  Prints one JSON line.  Kernel times come from a separate rocprofv3 run:
 
     timeout -k 10 300 python tools/diag/pgo_time.py
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d pgo_prof -o pgo -- python tools/diag/pgo_time.py --calls 20 --no-cpu
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--keys", type=int, default=1024)
     ap.add_argument("--loops", type=int, default=16)
+    ap.add_argument("--gps-every", type=int, default=64)
     ap.add_argument("--no-cpu", action="store_true")
     a = ap.parse_args()
     try:
@@ -57,8 +61,33 @@ def main():
         t2 = time.perf_counter()
         if k >= 3:
             build.append((t1 - t0) * 1e6); wall.append((t2 - t1) * 1e6)
+    # the covariance call at the newest key of the solved graph, without GPS factors (the gauge split)
+    cov = []
+    for k in range(a.calls + 3):
+        t0 = time.perf_counter()
+        g.marginal_covariance(n - 1)
+        if k >= 3:
+            cov.append((time.perf_counter() - t0) * 1e6)
+    # GPS mode: a fix every gps_every keys (ground truth + N(0, 0.3 m), variances 1, 2, 1), the solve and the covariance call
+    g.set_params(max_iters=30)
+    fixes = [(k, (sc["gt"][k][:3, 3] + rs.normal(0, 0.3, 3)).astype(np.float32)) for k in range(0, n, a.gps_every)]
+    gwall, gcov, ginfo = [], [], None
+    for k in range(a.calls + 3):
+        g.clear()
+        R.build(sc, g)
+        for key, z in fixes:
+            g.add_gps(key, z, [1.0, 2.0, 1.0])
+        t1 = time.perf_counter()
+        ginfo = g.solve()
+        t2 = time.perf_counter()
+        g.marginal_covariance(n - 1)
+        t3 = time.perf_counter()
+        if k >= 3:
+            gwall.append((t2 - t1) * 1e6); gcov.append((t3 - t2) * 1e6)
     g.close()
-    out = dict(keys=n, loops=nl, solve_wall_us=_stats(wall), graph_build_python_us=_stats(build), iterations=info["iterations"], converged=info["converged"],
+    gps = dict(fixes=len(fixes), max_iters=30, solve_wall_us=_stats(gwall), iterations=ginfo["iterations"], converged=ginfo["converged"],
+               chi2_before=ginfo["chi2_before"], chi2_after=ginfo["chi2_after"], covariance_wall_us=_stats(gcov))
+    out = dict(keys=n, loops=nl, covariance_wall_us=_stats(cov), gps=gps, solve_wall_us=_stats(wall), graph_build_python_us=_stats(build), iterations=info["iterations"], converged=info["converged"],
                max_iters=10, chi2_before=info["chi2_before"], chi2_after=info["chi2_after"])
     if not a.no_cpu:
         ref = R.build(sc, R.Graph(1))
