@@ -1116,7 +1116,10 @@ def test_corner_eigenvalue_ratio_gate(pkg, oracle, hip):
     (mapOptimization.cpp:1052).  Clusters built so that the ratio is KNOWN (five points on a cross: variance a^2 2/5 along x,
     b^2 2/5 along y → ratio (a/b)^2) sweep the gate from 2 to 4.5; away from the threshold the decision is the analytic one in
     both libraries, and the two libraries agree everywhere (Jacobi in f32 on both sides; cv::eigen itself is not available:
-    parity unpinned)"""
+    parity unpinned).
+    These clusters are AXIS-ALIGNED: the covariance is diagonal, `eig3_sym` leaves before its first rotation, and what is tested
+    at the gate is the ordering of three diagonal entries.  The crosses in rotated planes (full covariances, 5 / 60 / 250 m from
+    the origin, both exact eigenvalue ties) are tests/test_gpu_fit.py::test_flags_on_hand_built_scenes, against float64"""
     P = dict(N_SCAN=4, Horizon_SCAN=2048, max_raw_points=8192, max_map_points=65536, mappingCornerLeafSize=0.05)
     o = pkg.LidarHotpath(oracle, **P); g = pkg.LidarHotpath(hip, **P)
     ratios = np.concatenate([np.linspace(2.0, 2.9, 10), [2.97, 2.99, 2.999, 3.001, 3.01, 3.03], np.linspace(3.1, 4.5, 10)])
