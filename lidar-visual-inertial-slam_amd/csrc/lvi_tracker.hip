@@ -55,20 +55,20 @@ __device__ __forceinline__ void pyrdown_body(const uint8_t* __restrict__ src, in
     }
     dst[(size_t)y * dw + x] = (uint8_t)((sum + 128) >> 8);
 }
-__global__ __launch_bounds__(256) void pyrdown_kernel(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh)
-{
-    pyrdown_body(src, sw, sh, dst, dw, dh);
-}
-// The batch forms (lvi_tbatch, include/lvi_tbatch.h): the same bodies, the slot in blockIdx.z, one by-value table of per-slot
-// argument blocks per launch (as lvi_scan.hip's B_.a[blockIdx.z]).  A zeroed block is a slot that sits the call out; the grid is
-// sized for the largest slot, and a workgroup beyond its own slot's extent returns at once (uniform per workgroup).
-template <class T> struct TBatch { T a[LVI_TRACKER_MAX_BATCH]; };
+// Every tracker kernel has ONE entry: the slot in blockIdx.z, one by-value table of per-slot argument blocks per launch (as
+// lvi_scan.hip's B_.a[blockIdx.z]).  A zeroed block is a slot that sits the call out; the grid is sized for the largest slot, and a
+// workgroup beyond its own slot's extent returns at once (uniform per workgroup).  A set of one slot (a single handle) launches the
+// entry's instantiation for a table of ONE block, grid.z = 1: the eight-block table cost lk_track, gftt_sortpick and gftt_mineig
+// 0.2 - 0.7 us each against arguments passed directly, the one-block table is those arguments.
+template <class T, int N = LVI_TRACKER_MAX_BATCH> struct TBatch { T a[N]; };
+template <class T, int N> __device__ __forceinline__ const T& slot_args(const TBatch<T, N>& B) { return B.a[N == 1 ? 0 : blockIdx.z]; }
 #define LVI_TBATCH_FITS(T) static_assert(sizeof(TBatch<T>) <= 4096, #T ": the per-slot table exceeds the 4 KB kernel-argument limit")
 struct PyrArgs { const uint8_t* src; uint8_t* dst; int sw, sh, dw, dh; };
 LVI_TBATCH_FITS(PyrArgs);
-__global__ __launch_bounds__(256) void pyrdown_batch_kernel(TBatch<PyrArgs> B_)
+template <int N>
+__global__ __launch_bounds__(256) void pyrdown_kernel(TBatch<PyrArgs, N> B_)
 {
-    const PyrArgs& a = B_.a[blockIdx.z];
+    const PyrArgs& a = slot_args(B_);
     if ((int)blockIdx.x * 32 >= a.dw || (int)blockIdx.y * 8 >= a.dh) return;
     pyrdown_body(a.src, a.sw, a.sh, a.dst, a.dw, a.dh);
 }
@@ -97,8 +97,12 @@ struct ClaheArgs {
     int W, H, tilesX, tilesY, tw, th, clipLimit; float lutScale;
 };
 
-__device__ __forceinline__ void clahe_lut_body(const ClaheArgs& a)
+LVI_TBATCH_FITS(ClaheArgs);
+template <int N>
+__global__ __launch_bounds__(1024) void clahe_lut_kernel(TBatch<ClaheArgs, N> B_)
 {
+    const ClaheArgs& a = slot_args(B_);
+    if ((int)blockIdx.x >= a.tilesX * a.tilesY) return;
     // 1024 threads per tile, four pixels per load, one histogram per wavefront (a tile of the 1280 x 720 frame is 14 400 pixels: 256
     // threads reading bytes one by one into ONE histogram were 32 us of the node's frame — 64 workgroups, 56 dependent rounds each)
     __shared__ int whist[16][256];
@@ -162,17 +166,12 @@ __device__ __forceinline__ void clahe_lut_body(const ClaheArgs& a)
     if (tid >= 256) return;
     a.lut[(size_t)k * 256 + tid] = (uint8_t)min(max(v, 0), 255);
 }
-__global__ __launch_bounds__(1024) void clahe_lut_kernel(ClaheArgs a) { clahe_lut_body(a); }
-LVI_TBATCH_FITS(ClaheArgs);
-__global__ __launch_bounds__(1024) void clahe_lut_batch_kernel(TBatch<ClaheArgs> B_)
-{
-    const ClaheArgs& a = B_.a[blockIdx.z];
-    if ((int)blockIdx.x >= a.tilesX * a.tilesY) return;
-    clahe_lut_body(a);
-}
 
-__device__ __forceinline__ void clahe_interp_body(const ClaheArgs& a)
+template <int N>
+__global__ __launch_bounds__(256) void clahe_interp_kernel(TBatch<ClaheArgs, N> B_)
 {
+    const ClaheArgs& a = slot_args(B_);
+    if ((int)blockIdx.x * 64 >= a.W || (int)blockIdx.y * 4 >= a.H) return;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= a.W || y >= a.H) return;
     const float inv_tw = 1.0f / a.tw, inv_th = 1.0f / a.th;
@@ -191,13 +190,6 @@ __device__ __forceinline__ void clahe_interp_body(const ClaheArgs& a)
     const float res = ((float)p1[ind1] * xa1 + (float)p1[ind2] * xa) * ya1 + ((float)p2[ind1] * xa1 + (float)p2[ind2] * xa) * ya;
     a.dst[(size_t)y * a.W + x] = (uint8_t)min(max(cv_round(res), 0), 255);
 }
-__global__ __launch_bounds__(256) void clahe_interp_kernel(ClaheArgs a) { clahe_interp_body(a); }
-__global__ __launch_bounds__(256) void clahe_interp_batch_kernel(TBatch<ClaheArgs> B_)
-{
-    const ClaheArgs& a = B_.a[blockIdx.z];
-    if ((int)blockIdx.x * 64 >= a.W || (int)blockIdx.y * 4 >= a.H) return;
-    clahe_interp_body(a);
-}
 
 // ---------------------------------------------------------------------------------------------
 // f-3  CataCamera::liftProjective with the 8-step recursive distortion model + (b.x/b.z, b.y/b.z) → Point2f
@@ -211,15 +203,12 @@ __device__ __forceinline__ void mei_undistort_body(const lvi_mei_params& c, cons
     if (i >= n) return;
     mei_lift_normalized(c, xy[2 * i], xy[2 * i + 1], out[2 * i], out[2 * i + 1]);
 }
-__global__ __launch_bounds__(64) void mei_undistort_kernel(lvi_mei_params c, const float* __restrict__ xy, int n, float* __restrict__ out, const int* __restrict__ n_dev = nullptr)
-{
-    mei_undistort_body(c, xy, n, out, n_dev);
-}
 struct MeiArgs { lvi_mei_params c; const float* xy; float* out; const int* n_dev; int n; };
 LVI_TBATCH_FITS(MeiArgs);
-__global__ __launch_bounds__(64) void mei_undistort_batch_kernel(TBatch<MeiArgs> B_)
+template <int N>
+__global__ __launch_bounds__(64) void mei_undistort_kernel(TBatch<MeiArgs, N> B_)
 {
-    const MeiArgs& a = B_.a[blockIdx.z];
+    const MeiArgs& a = slot_args(B_);
     if ((int)blockIdx.x * 64 >= a.n) return;
     mei_undistort_body(a.c, a.xy, a.n, a.out, a.n_dev);
 }
@@ -228,22 +217,21 @@ __global__ __launch_bounds__(64) void mei_undistort_batch_kernel(TBatch<MeiArgs>
 // filled circle is OpenCV's midpoint raster (FillCircle): row cy +- dy spans cx +- dx and row cy +- dx spans cx +- dy for the
 // (dx, dy) the integer error recurrence visits; hw[j] = the widest of the spans of row offset j.  One thread per (circle, row).
 struct CircleArgs { uint8_t* mask; int w, h; const float* centers; int n; int radius; };
-__device__ __forceinline__ void mask_fill_body(const CircleArgs& a)
+LVI_TBATCH_FITS(CircleArgs);
+template <int N>
+__global__ __launch_bounds__(256) void mask_fill_kernel(TBatch<CircleArgs, N> B_)
 {
+    const CircleArgs& a = slot_args(B_);
+    if (!a.mask || (size_t)blockIdx.x * 256 * 16 >= (size_t)a.w * a.h) return;
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
     if (i + 16 <= (size_t)a.w * a.h) *reinterpret_cast<uint4*>(a.mask + i) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
     else for (size_t k = i; k < (size_t)a.w * a.h; k++) a.mask[k] = 255;
 }
-__global__ __launch_bounds__(256) void mask_fill_kernel(CircleArgs a) { mask_fill_body(a); }
-LVI_TBATCH_FITS(CircleArgs);
-__global__ __launch_bounds__(256) void mask_fill_batch_kernel(TBatch<CircleArgs> B_)
+template <int N>
+__global__ __launch_bounds__(64) void mask_circles_kernel(TBatch<CircleArgs, N> B_)
 {
-    const CircleArgs& a = B_.a[blockIdx.z];
-    if (!a.mask || (size_t)blockIdx.x * 256 * 16 >= (size_t)a.w * a.h) return;
-    mask_fill_body(a);
-}
-__device__ __forceinline__ void mask_circles_body(const CircleArgs& a)
-{
+    const CircleArgs& a = slot_args(B_);
+    if (!a.mask || (int)blockIdx.x >= a.n) return;
     __shared__ int hw[128];
     const int r = a.radius;
     if (threadIdx.x == 0) {
@@ -268,13 +256,6 @@ __device__ __forceinline__ void mask_circles_body(const CircleArgs& a)
         for (int x = x0; x <= x1; x++) a.mask[(size_t)y * a.w + x] = 0;
     }
 }
-__global__ __launch_bounds__(64) void mask_circles_kernel(CircleArgs a) { mask_circles_body(a); }
-__global__ __launch_bounds__(64) void mask_circles_batch_kernel(TBatch<CircleArgs> B_)
-{
-    const CircleArgs& a = B_.a[blockIdx.z];
-    if (!a.mask || (int)blockIdx.x >= a.n) return;
-    mask_circles_body(a);
-}
 
 // undistortedPoints over [the kept points (host) ; the corners goodFeaturesToTrack just found (device)]: cur_pts of the next frame
 __device__ __forceinline__ void frame_concat_body(const float* __restrict__ kept, int n_kept, const float* __restrict__ found, const int* __restrict__ n_found,
@@ -294,22 +275,20 @@ __device__ __forceinline__ void frame_concat_body(const float* __restrict__ kept
     }
     if (threadIdx.x == 0) { d_hdr[2] = n; h_hdr[0] = nraw; h_hdr[1] = with_gftt ? *n_cand : 0; h_hdr[2] = n; }
 }
-__global__ __launch_bounds__(64) void frame_concat_kernel(const float* __restrict__ kept, int n_kept, const float* __restrict__ found, const int* __restrict__ n_found,
-                                                          const int* __restrict__ n_cand, int with_gftt, int cap, float* __restrict__ all_xy, int* __restrict__ d_hdr,
-                                                          int* __restrict__ h_hdr, float* __restrict__ h_new)
-{
-    frame_concat_body(kept, n_kept, found, n_found, n_cand, with_gftt, cap, all_xy, d_hdr, h_hdr, h_new);
-}
 struct ConcatArgs { const float* kept; const float* found; const int* n_found; const int* n_cand; float* all_xy; int* d_hdr; int* h_hdr; float* h_new; int n_kept, with_gftt, cap; };
 LVI_TBATCH_FITS(ConcatArgs);
-__global__ __launch_bounds__(64) void frame_concat_batch_kernel(TBatch<ConcatArgs> B_)
+template <int N>
+__global__ __launch_bounds__(64) void frame_concat_kernel(TBatch<ConcatArgs, N> B_)
 {
-    const ConcatArgs& a = B_.a[blockIdx.z];
+    const ConcatArgs& a = slot_args(B_);
     if (!a.d_hdr) return;
     frame_concat_body(a.kept, a.n_kept, a.found, a.n_found, a.n_cand, a.with_gftt, a.cap, a.all_xy, a.d_hdr, a.h_hdr, a.h_new);
 }
-__device__ __forceinline__ void lk_body(const LkArgs& a)
+LVI_TBATCH_FITS(LkArgs);               // two 8-level Pyr: 360 bytes per slot
+template <int N>
+__global__ __launch_bounds__(64) void lk_kernel(TBatch<LkArgs, N> B_)
 {
+    const LkArgs& a = slot_args(B_);     // (a workgroup past its slot's n returns below, first thing)
     constexpr int TW = LK_WIN_MAX + 3;             // 24: source tile (window + 1 for bilinear + 1 on each side for Scharr)
     constexpr int DW = LK_WIN_MAX + 1;             // 22: derivative / target tile
     constexpr int NPX = (LK_WIN_MAX * LK_WIN_MAX + 63) / 64;   // 7 window pixels per lane
@@ -508,18 +487,13 @@ __device__ __forceinline__ void lk_body(const LkArgs& a)
         if (a.h_next_xy) { a.h_next_xy[2 * f] = outx; a.h_next_xy[2 * f + 1] = outy; a.h_status[f] = st ? 1 : 0; a.h_err[f] = errv; }
     }
 }
-__global__ __launch_bounds__(64) void lk_kernel(LkArgs a) { lk_body(a); }
-LVI_TBATCH_FITS(LkArgs);               // two 8-level Pyr: 360 bytes per slot
-__global__ __launch_bounds__(64) void lk_batch_kernel(TBatch<LkArgs> B_)
-{
-    lk_body(B_.a[blockIdx.z]);          // (a workgroup past its slot's n returns first thing)
-}
 
 // ------------------------------------------------------------------------------------------- GFTT
 struct GfttArgs {
     const uint8_t* img; const uint8_t* mask; int w, h;
     float* eig; unsigned* maxord; float* thr;
-    unsigned* maxPartial;            // [workgroups of mineig_kernel]
+    unsigned* maxPartial;            // [npartial] one per workgroup of mineig_kernel, rows of gx (the slot's own layout, not the grid's)
+    int gx, npartial, nblk;          // the sizes derived from w, h (gftt_args): mineig's workgroups per row and in all, tiles of CAND_TILE pixels
     int* blockCnt; int* total;
     unsigned *keysA, *valsA;
     int *d_n, *d_nbits;
@@ -546,8 +520,12 @@ __device__ __forceinline__ void sobel_at(const uint8_t* img, int w, int h, int x
 // LDS (the first version recomputed them nine times per pixel), then every thread adds its nine in the reference's
 // order (rows, then columns, in double).  The masked maximum goes to one partial per workgroup; gftt_thr folds them
 // (14 400 wavefronts hitting one atomicMax address cost ~0.16 ms: same-address atomics serialise).
-__device__ __forceinline__ void mineig_body(const GfttArgs& a, int gx)
+LVI_TBATCH_FITS(GfttArgs);
+template <int N>
+__global__ __launch_bounds__(256) void mineig_kernel(TBatch<GfttArgs, N> B_)
 {
+    const GfttArgs& a = slot_args(B_);
+    if ((int)blockIdx.x * 32 >= a.w || (int)blockIdx.y * 8 >= a.h) return;
     constexpr int TW = 34, TH = 10;
     __shared__ float sxx[TH][TW], sxy[TH][TW], syy[TH][TW];
     __shared__ unsigned smax[4];
@@ -584,24 +562,16 @@ __device__ __forceinline__ void mineig_body(const GfttArgs& a, int gx)
     for (int s = 32; s > 0; s >>= 1) { const unsigned t = __shfl_xor(o, s, 64); o = t > o ? t : o; }
     if (lane_id() == 0) smax[wave_id()] = o;
     __syncthreads();
-    if (threadIdx.x == 0) a.maxPartial[blockIdx.y * gx + blockIdx.x] = max(max(smax[0], smax[1]), max(smax[2], smax[3]));
-}
-__global__ __launch_bounds__(256) void mineig_kernel(GfttArgs a) { mineig_body(a, (int)gridDim.x); }
-LVI_TBATCH_FITS(GfttArgs);
-__global__ __launch_bounds__(256) void mineig_batch_kernel(TBatch<GfttArgs> B_)
-{
-    const GfttArgs& a = B_.a[blockIdx.z];
-    if ((int)blockIdx.x * 32 >= a.w || (int)blockIdx.y * 8 >= a.h) return;
-    mineig_body(a, (a.w + 31) / 32);       // the partial maxima keep the slot's own layout
+    if (threadIdx.x == 0) a.maxPartial[blockIdx.y * a.gx + blockIdx.x] = max(max(smax[0], smax[1]), max(smax[2], smax[3]));
 }
 
 // quality threshold = max over the (masked) min-eigenvalue image x qualityLevel (featureselect.cpp): the fold of mineig's per-workgroup
 // maxima.  Every workgroup of gftt_count folds the few thousand partial maxima itself (a separate one-workgroup launch was 4.6 us of
 // the node's frame); its first workgroup leaves the result for gftt_emit and the debug views.
-__device__ __forceinline__ float gftt_threshold(const GfttArgs& a, int npartial, unsigned* smax)
+__device__ __forceinline__ float gftt_threshold(const GfttArgs& a, unsigned* smax)
 {
     unsigned o = 0u;
-    for (int i = threadIdx.x; i < npartial; i += 256) o = max(o, a.maxPartial[i]);
+    for (int i = threadIdx.x; i < a.npartial; i += 256) o = max(o, a.maxPartial[i]);
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) { const unsigned t = __shfl_xor(o, s, 64); o = t > o ? t : o; }
     if (lane_id() == 0) smax[wave_id()] = o;
@@ -635,10 +605,13 @@ __device__ __forceinline__ bool gftt_is_cand(const GfttArgs& a, int x, int y, fl
 }
 
 constexpr int CAND_TILE = 1024;
-__device__ __forceinline__ void gftt_count_body(const GfttArgs& a, int npartial)
+template <int N>
+__global__ __launch_bounds__(256) void gftt_count_kernel(TBatch<GfttArgs, N> B_)
 {
+    const GfttArgs& a = slot_args(B_);
+    if ((int)blockIdx.x >= a.nblk) return;
     __shared__ unsigned smax[4];
-    const float thr = gftt_threshold(a, npartial, smax);
+    const float thr = gftt_threshold(a, smax);
     const int base = blockIdx.x * CAND_TILE;
     int c = 0;
 #pragma unroll
@@ -648,21 +621,17 @@ __device__ __forceinline__ void gftt_count_body(const GfttArgs& a, int npartial)
     block_excl_scan<256>(c, ws, &tot);
     if (threadIdx.x == 0) a.blockCnt[blockIdx.x] = tot;
 }
-__global__ __launch_bounds__(256) void gftt_count_kernel(GfttArgs a, int npartial) { gftt_count_body(a, npartial); }
-__global__ __launch_bounds__(256) void gftt_count_batch_kernel(TBatch<GfttArgs> B_)
-{
-    const GfttArgs& a = B_.a[blockIdx.z];
-    if ((int)blockIdx.x * CAND_TILE >= a.w * a.h) return;
-    gftt_count_body(a, ((a.w + 31) / 32) * ((a.h + 7) / 8));
-}
 // ordered compaction; the prefix over the (<= a few thousand) per-tile counts is folded by every workgroup itself (the one-workgroup
 // scan launch in between was 4.8 us of the node's frame)
-__device__ __forceinline__ void gftt_emit_body(const GfttArgs& a, int nblk)
+template <int N>
+__global__ __launch_bounds__(256) void gftt_emit_kernel(TBatch<GfttArgs, N> B_)
 {
+    const GfttArgs& a = slot_args(B_);
+    if ((int)blockIdx.x >= a.nblk) return;
     const float thr = *a.thr;
     __shared__ int ws[8];
     int bef = 0, all = 0;
-    for (int i = threadIdx.x; i < nblk; i += 256) { const int v = a.blockCnt[i]; all += v; bef += i < (int)blockIdx.x ? v : 0; }
+    for (int i = threadIdx.x; i < a.nblk; i += 256) { const int v = a.blockCnt[i]; all += v; bef += i < (int)blockIdx.x ? v : 0; }
     int total, before;
     (void)block_excl_scan<256>(all, ws, &total);
     (void)block_excl_scan<256>(bef, ws, &before);
@@ -681,13 +650,6 @@ __device__ __forceinline__ void gftt_emit_body(const GfttArgs& a, int nblk)
         a.keysA[pos] = ~__float_as_uint(a.eig[p]);          // eig > 0 here: ascending ~bits = descending value
         a.valsA[pos] = (unsigned)p;
     }
-}
-__global__ __launch_bounds__(256) void gftt_emit_kernel(GfttArgs a, int nblk) { gftt_emit_body(a, nblk); }
-__global__ __launch_bounds__(256) void gftt_emit_batch_kernel(TBatch<GfttArgs> B_)
-{
-    const GfttArgs& a = B_.a[blockIdx.z];
-    if ((int)blockIdx.x * CAND_TILE >= a.w * a.h) return;
-    gftt_emit_body(a, (a.w * a.h + CAND_TILE - 1) / CAND_TILE);
 }
 
 struct PickArgs {
@@ -908,14 +870,15 @@ __device__ __forceinline__ void gftt_pick_body(const PickArgs& a)
     if (l == 0) *a.out_n = SORTLDS ? (s_state == 2 ? -2 : nacc) : (overflow ? -1 : nacc);
     if (SORTLDS && l == 0 && a.dbg) { a.dbg[0] = tq[1] - tq[0]; a.dbg[1] = tq[2]; a.dbg[2] = tq[3]; a.dbg[3] = clock64() - tq[0]; a.dbg[4] = nbands; a.dbg[5] = total; a.dbg[6] = nacc; }
 }
-template <bool SORTLDS>
-__global__ __launch_bounds__(SORTLDS ? 1024 : 64) void gftt_pick_kernel(PickArgs a) { gftt_pick_body<SORTLDS>(a); }
+// the radix form: one slot per launch by design (the sort in front of it is per slot)
+__global__ __launch_bounds__(64) void gftt_pick_kernel(PickArgs a) { gftt_pick_body<false>(a); }
 LVI_TBATCH_FITS(PickArgs);
-// the LDS form for every slot of a batch: one 1024-thread workgroup per slot, each on its own CU (its ~108 KB of LDS leave room for one)
-__global__ __launch_bounds__(1024) void gftt_sortpick_batch_kernel(TBatch<PickArgs> B_)
+// the LDS form: one 1024-thread workgroup per slot, each on its own CU (its ~108 KB of LDS leave room for one)
+template <int N>
+__global__ __launch_bounds__(1024) void gftt_sortpick_kernel(TBatch<PickArgs, N> B_)
 {
-    const PickArgs& a = B_.a[blockIdx.z];
-    if (!a.total) return;
+    const PickArgs& a = slot_args(B_);
+    if (N > 1 && !a.total) return;     // (a set of one launches this kernel only for its slot)
     gftt_pick_body<true>(a);
 }
 
@@ -998,6 +961,39 @@ void tracker_layout(AR& ar, lvi_tracker& t)
     t.d_dbg = ar.template alloc<long long>(8);
 }
 
+// A set of tracker states that every stage serves with ONE launch (the image side's counterpart of lvi_lidar.hpp's Slots): the
+// slots of an lvi_tbatch, or a single handle as a set of one.  c: the stream and the profiler the set's launches go through.
+struct TSlots {
+    const Ctx& c; lvi_tracker* t; int n;             // t[0 .. n), n = 1 .. LVI_TRACKER_MAX_BATCH
+    lvi_tracker& operator[](int s) const { return t[s]; }
+    TSlots one(int s) const { return TSlots{c, t + s, 1}; }
+    template <class T>
+    void launch(const char* name, double bytes, void (*k1)(TBatch<T, 1>), void (*kn)(TBatch<T>), dim3 grid, int threads, const TBatch<T>& B) const
+    {
+        grid.z = (unsigned)n;
+        if (n == 1) {
+            const TBatch<T, 1> B1{{B.a[0]}};
+            LVI_LAUNCH(c, name, bytes, hipLaunchKernelGGL(k1, grid, dim3(threads), 0, c.stream, B1));
+        } else {
+            LVI_LAUNCH(c, name, bytes, hipLaunchKernelGGL(kn, grid, dim3(threads), 0, c.stream, B));
+        }
+    }
+};
+// one launch of a kernel entry for the set S: its one-block instantiation for a set of one slot
+#define LVI_TLAUNCH(S, name, bytes, kernel, grid, threads, B) (S).launch(name, bytes, kernel<1>, kernel<LVI_TRACKER_MAX_BATCH>, grid, threads, B)
+const bool TAKE_ALL[LVI_TRACKER_MAX_BATCH] = {true, true, true, true, true, true, true, true};
+static_assert(LVI_TRACKER_MAX_BATCH == 8, "TAKE_ALL names every slot");
+
+// the pinned double slots: the other buffer of the pair, free once the command that read it two uses ago is through.  The caller
+// fills it and records ev[slot] behind the command that reads it.
+template <class T>
+T* pinned_next(T* const (&h)[2], const hipEvent_t (&ev)[2], int& slot)
+{
+    slot ^= 1;
+    LVI_HIP(hipEventSynchronize(ev[slot]));
+    return h[slot];
+}
+
 // src (w x h, dense) → dst equalised; both device buffers of the handle
 ClaheArgs clahe_args(lvi_tracker& t, const uint8_t* src, uint8_t* dst, int w, int h, double clip, int tilesX, int tilesY)
 {
@@ -1012,33 +1008,14 @@ ClaheArgs clahe_args(lvi_tracker& t, const uint8_t* src, uint8_t* dst, int w, in
     if (clip > 0.0) a.clipLimit = std::max(static_cast<int>(clip * area / 256), 1);
     return a;
 }
-void run_clahe(lvi_tracker& t, const uint8_t* src, uint8_t* dst, int w, int h, double clip, int tilesX, int tilesY)
+// the filled blocks of B are w x h images with one tile grid
+void run_clahe(const TSlots& S, const TBatch<ClaheArgs>& B, int ntile, int w, int h, double px)
 {
-    const ClaheArgs a = clahe_args(t, src, dst, w, h, clip, tilesX, tilesY);
-    LVI_LAUNCH(t.ctx, "clahe_lut", (double)w * h, hipLaunchKernelGGL(clahe_lut_kernel, dim3(tilesX * tilesY), dim3(1024), 0, t.ctx.stream, a));
-    LVI_LAUNCH(t.ctx, "clahe_interp", 2.0 * w * h, hipLaunchKernelGGL(clahe_interp_kernel, dim3(div_up(w, 64), div_up(h, 4)), dim3(256), 0, t.ctx.stream, a));
+    LVI_TLAUNCH(S, "clahe_lut", px, clahe_lut_kernel, dim3(ntile), 1024, B);
+    LVI_TLAUNCH(S, "clahe_interp", 2.0 * px, clahe_interp_kernel, dim3(div_up(w, 64), div_up(h, 4)), 256, B);
 }
 
-void build_pyramid(lvi_tracker& t, int slot)
-{
-    Pyr& p = t.pyr[slot];
-    int w = t.w, h = t.h;
-    p.lv[0].w = w; p.lv[0].h = h;
-    p.top = t.P.lk_max_level;
-    for (int level = 0; level <= t.P.lk_max_level; level++) {
-        if (level != 0) {
-            const int dw = (p.lv[level - 1].w + 1) / 2, dh = (p.lv[level - 1].h + 1) / 2;
-            p.lv[level].w = dw; p.lv[level].h = dh;
-            LVI_LAUNCH(t.ctx, "pyrdown", (double)p.lv[level - 1].w * p.lv[level - 1].h + (double)dw * dh,
-                       hipLaunchKernelGGL(pyrdown_kernel, dim3(div_up(dw, 32), div_up(dh, 8)), dim3(256), 0, t.ctx.stream,
-                                          p.lv[level - 1].px, p.lv[level - 1].w, p.lv[level - 1].h, p.lv[level].px, dw, dh));
-        }
-        w = (w + 1) / 2; h = (h + 1) / 2;
-        if (w <= t.P.lk_win || h <= t.P.lk_win) { p.top = level; break; }      // buildOpticalFlowPyramid's early return
-    }
-}
-
-// the levels build_pyramid fills for a w x h image, without the launches (the batch form launches level by level for all slots)
+// the levels of the pyramid of a w x h image (buildOpticalFlowPyramid's early return included), without the launches
 void plan_pyramid(Pyr& p, int w, int h, const lvi_tracker_params& P)
 {
     p.lv[0].w = w; p.lv[0].h = h;
@@ -1047,6 +1024,33 @@ void plan_pyramid(Pyr& p, int w, int h, const lvi_tracker_params& P)
         if (level != 0) { p.lv[level].w = (p.lv[level - 1].w + 1) / 2; p.lv[level].h = (p.lv[level - 1].h + 1) / 2; }
         w = (w + 1) / 2; h = (h + 1) / 2;
         if (w <= P.lk_win || h <= P.lk_win) { p.top = level; break; }
+    }
+}
+// the pyramids of the slots of `take` over their level-0 images: one launch per level; a slot whose pyramid ends early has a zeroed
+// block in the deeper launches
+void build_pyramids(const TSlots& S, const bool* take, bool cur_side)
+{
+    int maxtop = 0;
+    for (int s = 0; s < S.n; s++) {
+        if (!take[s]) continue;
+        lvi_tracker& t = S[s];
+        Pyr& p = t.pyr[cur_side ? t.cur : t.forw];
+        plan_pyramid(p, t.w, t.h, t.P);
+        maxtop = std::max(maxtop, p.top);
+    }
+    for (int level = 1; level <= maxtop; level++) {
+        TBatch<PyrArgs> B{};
+        int gx = 0, gy = 0; double bytes = 0;
+        for (int s = 0; s < S.n; s++) {
+            if (!take[s]) continue;
+            lvi_tracker& t = S[s];
+            const Pyr& p = t.pyr[cur_side ? t.cur : t.forw];
+            if (level > p.top) continue;
+            B.a[s] = PyrArgs{p.lv[level - 1].px, p.lv[level].px, p.lv[level - 1].w, p.lv[level - 1].h, p.lv[level].w, p.lv[level].h};
+            gx = std::max(gx, div_up(p.lv[level].w, 32)); gy = std::max(gy, div_up(p.lv[level].h, 8));
+            bytes += (double)p.lv[level - 1].w * p.lv[level - 1].h + (double)p.lv[level].w * p.lv[level].h;
+        }
+        LVI_TLAUNCH(S, "pyrdown", bytes, pyrdown_kernel, dim3(gx, gy), 256, B);
     }
 }
 
@@ -1093,6 +1097,263 @@ void tracker_host_free(lvi_tracker* t)
     if (t->h_frame_out) (void)hipHostFree(t->h_frame_out);
     if (t->h_lk) (void)hipHostFree(t->h_lk);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The stages.  Each is written once, for a set of slots; the entry points below check their arguments and hand over a set of one
+// (lvi_tracker_*) or of S (lvi_tbatch_*) slots.  A slot that sits a call out is skipped by its mask or its negative count.
+// ---------------------------------------------------------------------------------------------
+// one image per slot of `take`: staging copy, optional CLAHE, the forw pyramid; a slot's first image (or a new size) is its cur image too
+void stage_push(const TSlots& S, const uint8_t* const* imgs, const bool* take, int w, int h, int stride)
+{
+    bool first[LVI_TRACKER_MAX_BATCH] = {}, any_first = false;
+    for (int s = 0; s < S.n; s++) {
+        if (!take[s]) continue;
+        lvi_tracker& t = S[s];
+        if (t.have_forw && (w != t.w || h != t.h)) { t.have_forw = t.have_cur = false; }
+        if (t.have_forw) { std::swap(t.cur, t.forw); t.have_cur = true; }     // cur_img = forw_img (:203), this slot's own rotation
+        first[s] = !t.have_forw; any_first = any_first || first[s];
+        t.w = w; t.h = h;
+        uint8_t* stage = pinned_next(t.h_frame, t.ev_frame, t.frame_slot);    // (waits for the copy that used this buffer two frames ago)
+        for (int y = 0; y < h; y++) std::memcpy(stage + (size_t)y * w, imgs[s] + (size_t)y * stride, (size_t)w);
+        uint8_t* dst0 = t.equalize ? t.d_stage : t.pyr[t.forw].lv[0].px;
+        LVI_HIP(hipMemcpyAsync(dst0, stage, (size_t)w * h, hipMemcpyHostToDevice, S.c.stream));
+        LVI_HIP(hipEventRecord(t.ev_frame[t.frame_slot], S.c.stream));
+    }
+    if (S[0].equalize) {                                                       // readImage's EQUALIZE branch (:86-90), all slots alike
+        TBatch<ClaheArgs> B{};
+        int ntile = 0; double px = 0;
+        for (int s = 0; s < S.n; s++) {
+            if (!take[s]) continue;
+            lvi_tracker& t = S[s];
+            B.a[s] = clahe_args(t, t.d_stage, t.pyr[t.forw].lv[0].px, w, h, t.clahe_clip, t.clahe_tx, t.clahe_ty);
+            ntile = B.a[s].tilesX * B.a[s].tilesY; px += (double)w * h;
+        }
+        run_clahe(S, B, ntile, w, h, px);
+    }
+    build_pyramids(S, take, false);
+    if (any_first) {                                                           // prev = cur = forw = img (:94-97)
+        for (int s = 0; s < S.n; s++) {
+            if (!first[s]) continue;
+            lvi_tracker& t = S[s];
+            LVI_HIP(hipMemcpyAsync(t.pyr[t.cur].lv[0].px, t.pyr[t.forw].lv[0].px, (size_t)w * h, hipMemcpyDeviceToDevice, S.c.stream));
+        }
+        build_pyramids(S, first, true);
+    }
+    // no stream sync: the caller's buffers were consumed by the host copies above
+    for (int s = 0; s < S.n; s++) {
+        if (!take[s]) continue;
+        lvi_tracker& t = S[s];
+        if (first[s]) t.have_cur = true;
+        t.have_forw = true; t.have_lk = false; t.have_gftt = false;
+    }
+}
+
+void stage_set_points(const TSlots& S, const float* const* cur_xy, const int32_t* n)
+{
+    for (int s = 0; s < S.n; s++) {
+        if (n[s] < 0) continue;
+        lvi_tracker& t = S[s];
+        if (n[s]) {
+            float* dst = pinned_next(t.h_pts, t.ev_pts, t.pts_slot);
+            std::memcpy(dst, cur_xy[s], sizeof(float) * 2 * (size_t)n[s]);
+            t.cur_src = dst; t.cur_slot = t.pts_slot;                          // lk_kernel reads them in place
+        }
+        t.n_pts = n[s]; t.have_lk = false;
+    }
+}
+
+// LK for the slots of `take`, each from its last set_points; true if a kernel was launched
+bool stage_run_lk(const TSlots& S, const bool* take)
+{
+    TBatch<LkArgs> B{};
+    int nmax = 0; double bytes = 0;
+    for (int s = 0; s < S.n; s++) {
+        if (!take[s]) continue;
+        lvi_tracker& t = S[s];
+        LkArgs& a = B.a[s];
+        a.prev = t.pyr[t.cur]; a.next = t.pyr[t.forw];
+        const size_t F = (size_t)std::max(t.P.max_features, 64);
+        a.prev_xy = t.cur_src ? t.cur_src : t.d_cur_xy; a.next_xy = t.d_forw_xy; a.status = t.d_status; a.err = t.d_err;
+        a.h_next_xy = t.h_lk; a.h_err = t.h_lk + 2 * F; a.h_status = reinterpret_cast<uint8_t*>(t.h_lk + 3 * F);
+        a.n = t.n_pts; a.win = t.P.lk_win; a.max_level = std::min(a.prev.top, a.next.top);
+        a.max_count = std::min(std::max(t.P.lk_max_iters, 0), 100);
+        const double eps = std::min(std::max(t.P.lk_eps, 0.), 10.);
+        a.epsilon = eps * eps; a.min_eig = t.P.lk_min_eig_threshold;
+        nmax = std::max(nmax, a.n);
+        bytes += (double)a.n * (a.max_level + 1) * (24.0 * 24 + 22.0 * 22 * 4);
+    }
+    if (nmax > 0) {
+        LVI_TLAUNCH(S, "lk_track", bytes, lk_kernel, dim3(nmax), 64, B);
+        for (int s = 0; s < S.n; s++) {
+            lvi_tracker& t = S[s];                                             // the points' slot is free again once this kernel has read it
+            if (take[s] && t.n_pts > 0 && t.cur_slot >= 0) LVI_HIP(hipEventRecord(t.ev_pts[t.cur_slot], S.c.stream));
+        }
+    }
+    for (int s = 0; s < S.n; s++) if (take[s]) S[s].have_lk = true;
+    return nmax > 0;
+}
+
+// the results lk_kernel wrote into the slot's pinned block; wait: the stream has not been waited for since run_lk
+int32_t get_lk(const Ctx& c, lvi_tracker* t, bool wait, float* forw_xy, uint8_t* status, float* err, int32_t capacity, int32_t* n)
+{
+    if (!t->have_lk) return fail(LVI_ERR_STATE, "LK not run");
+    *n = t->n_pts;
+    if (capacity < *n) return fail(LVI_ERR_CAPACITY, "capacity too small");
+    return guarded(t->device, [&]() -> int32_t {
+        const int m = *n;
+        const size_t F = (size_t)std::max(t->P.max_features, 64);
+        if (wait) LVI_HIP(hipStreamSynchronize(c.stream));
+        if (m && forw_xy) std::memcpy(forw_xy, t->h_lk, sizeof(float) * 2 * (size_t)m);
+        if (m && err) std::memcpy(err, t->h_lk + 2 * F, sizeof(float) * (size_t)m);
+        if (m && status) std::memcpy(status, t->h_lk + 3 * F, (size_t)m);
+        return LVI_OK;
+    });
+}
+
+// setMask's raster half for the slots with n[s] >= 0
+void stage_mask_circles(const TSlots& S, const float* const* centers_xy, const int32_t* n, int radius)
+{
+    TBatch<CircleArgs> B{};
+    bool read[LVI_TRACKER_MAX_BATCH] = {}; int nmax = 0, gfill = 0; double px = 0;
+    for (int s = 0; s < S.n; s++) {
+        if (n[s] < 0) continue;
+        lvi_tracker& t = S[s];
+        B.a[s] = CircleArgs{t.d_mask, t.w, t.h, t.d_centers, n[s], radius};
+        if (n[s]) {
+            float* dst = pinned_next(t.h_centers, t.ev_centers, t.centers_slot);
+            std::memcpy(dst, centers_xy[s], sizeof(float) * 2 * (size_t)n[s]);
+            B.a[s].centers = dst; read[s] = true;                               // read in place (pinned host memory)
+        }
+        nmax = std::max(nmax, n[s]); gfill = std::max(gfill, div_up(div_up(t.w * t.h, 16), 256)); px += (double)t.w * t.h;
+    }
+    LVI_TLAUNCH(S, "mask_fill", px, mask_fill_kernel, dim3(gfill), 256, B);
+    if (nmax) {
+        LVI_TLAUNCH(S, "mask_circles", 0, mask_circles_kernel, dim3(nmax), 64, B);
+        for (int s = 0; s < S.n; s++) if (read[s]) LVI_HIP(hipEventRecord(S[s].ev_centers[S[s].centers_slot], S.c.stream));
+    }
+    for (int s = 0; s < S.n; s++) if (n[s] >= 0) S[s].have_mask = true;
+}
+
+GfttArgs gftt_args(lvi_tracker& t)
+{
+    GfttArgs a{};
+    a.img = t.pyr[t.forw].lv[0].px; a.mask = t.have_mask ? t.d_mask : nullptr; a.w = t.w; a.h = t.h;
+    a.gx = div_up(t.w, 32); a.npartial = a.gx * div_up(t.h, 8); a.nblk = div_up(t.w * t.h, CAND_TILE);
+    a.eig = t.d_eig; a.maxord = t.d_maxord; a.maxPartial = t.d_maxPartial; a.thr = t.d_thr; a.blockCnt = t.d_blockCnt; a.total = t.d_total;
+    a.keysA = t.sort.keysA; a.valsA = t.sort.valsA; a.d_n = t.d_n; a.d_nbits = t.d_nbits; a.quality = t.P.gftt_quality;
+    return a;
+}
+PickArgs pick_args(lvi_tracker& t, int32_t max_corners)
+{
+    PickArgs p{};
+    p.keysA = t.sort.keysA; p.valsA = t.sort.valsA; p.valsB = t.sort.valsB; p.d_nbits = t.d_nbits; p.total = t.d_total;
+    p.w = t.w; p.h = t.h; p.max_corners = max_corners; p.cap = t.P.max_features; p.min_dist = t.P.min_dist;
+    p.out_xy = t.d_gftt_xy; p.out_n = t.d_out_n; p.ncand = t.d_ncand; p.dbg = t.d_dbg;
+    return p;
+}
+// goodFeaturesToTrack on forw for the slots of `take`, enqueued only.  lds_form: the candidates of every slot are sorted and picked
+// by ONE workgroup in LDS (a slot beyond what that form holds reports -2 in d_out_n and is redone in the radix form by whoever
+// fetches the result).  The radix form (12-launch sort + one-wavefront pick) runs slot by slot: the rare path is not batched.
+void enqueue_gftt(const TSlots& S, const bool* take, const int32_t* max_corners, bool lds_form)
+{
+    if (!lds_form && S.n > 1) {
+        for (int s = 0; s < S.n; s++) if (take[s]) enqueue_gftt(S.one(s), TAKE_ALL, max_corners + s, false);
+        return;
+    }
+    TBatch<GfttArgs> G{}; TBatch<PickArgs> K{};
+    int gx = 0, gy = 0, nblk = 0; double npx = 0;
+    for (int s = 0; s < S.n; s++) {
+        if (!take[s]) continue;
+        G.a[s] = gftt_args(S[s]); K.a[s] = pick_args(S[s], max_corners[s]);
+        gx = std::max(gx, G.a[s].gx); gy = std::max(gy, div_up(G.a[s].h, 8)); nblk = std::max(nblk, G.a[s].nblk);
+        npx += (double)G.a[s].w * G.a[s].h;
+    }
+    LVI_TLAUNCH(S, "gftt_mineig", 6.0 * npx, mineig_kernel, dim3(gx, gy), 256, G);
+    LVI_TLAUNCH(S, "gftt_count", 5.0 * npx, gftt_count_kernel, dim3(nblk), 256, G);
+    LVI_TLAUNCH(S, "gftt_emit", 5.0 * npx, gftt_emit_kernel, dim3(nblk), 256, G);
+    if (lds_form) {
+        LVI_TLAUNCH(S, "gftt_sortpick", 0, gftt_sortpick_kernel, dim3(1), 1024, K);
+    } else {
+        lvi_tracker& t = S[0];
+        radix_sort_pairs(S.c, t.sort, t.d_n, t.d_nbits, 4, "gftt", 0.02 * npx);
+        LVI_LAUNCH(S.c, "gftt_pick", 0, hipLaunchKernelGGL(gftt_pick_kernel, dim3(1), dim3(64), 0, S.c.stream, K.a[0]));
+    }
+}
+
+void stage_gftt_async(const TSlots& S, const bool* take, const int32_t* max_corners)
+{
+    enqueue_gftt(S, take, max_corners, !S[0].gftt_force_radix);       // LVI_GFTT_RADIX=1: every slot through the radix form
+    for (int s = 0; s < S.n; s++) {
+        if (!take[s]) continue;
+        lvi_tracker& t = S[s];
+        t.gftt_pending = true; t.gftt_pending_max = max_corners[s]; t.have_gftt = false;
+    }
+}
+
+// The frame end of the slots with n_kept[s] >= 0: [kept ; the corners of a pending run_gftt_async] and their undistorted points,
+// two kernels that write into pinned host memory and ONE wait.  A slot beyond the LDS form (-2) is redone alone in the radix form
+// on its own state, its two frame-end kernels run again (the kept points are still in the pinned slot the first attempt read) and
+// a second wait follows; the other slots' results stand.  redone: bit s = slot s was redone.  A capacity error found in a slot's
+// result is returned after every slot has been served (the last one, if several).
+int32_t stage_frame_end(const TSlots& S, const lvi_mei_params* cams, const float* const* kept_xy, const int32_t* n_kept,
+                        float* const* new_xy, int32_t new_capacity, int32_t* n_new, float* const* un_xy, int32_t& redone)
+{
+    const int F = S[0].P.max_features;
+    TBatch<ConcatArgs> C{}; TBatch<MeiArgs> M{};
+    bool with_gftt[LVI_TRACKER_MAX_BATCH] = {}, read[LVI_TRACKER_MAX_BATCH] = {};
+    for (int s = 0; s < S.n; s++) {
+        if (n_kept[s] < 0) continue;
+        lvi_tracker& t = S[s];
+        with_gftt[s] = t.gftt_pending;
+        const float* kept_src = t.d_un_in;
+        if (n_kept[s]) {
+            float* dst = pinned_next(t.h_kept, t.ev_kept, t.kept_slot);
+            std::memcpy(dst, kept_xy[s], sizeof(float) * 2 * (size_t)n_kept[s]);
+            kept_src = dst; read[s] = true;                                     // read in place
+        }
+        int* d_hdr = reinterpret_cast<int*>(t.d_frame_out);
+        C.a[s] = ConcatArgs{kept_src, t.d_gftt_xy, t.d_out_n, t.d_ncand, t.d_all_xy, d_hdr, reinterpret_cast<int*>(t.h_frame_out), t.h_frame_out + 4,
+                            n_kept[s], with_gftt[s] ? 1 : 0, F};
+        if (cams) M.a[s] = MeiArgs{cams[s], t.d_all_xy, t.h_frame_out + 4 + 2 * (size_t)F, d_hdr + 2, F};
+    }
+    auto frame_end_kernels = [&](const TSlots& Q, const TBatch<ConcatArgs>& Cq, const TBatch<MeiArgs>& Mq, const bool* readq) {
+        LVI_TLAUNCH(Q, "frame_concat", 0, frame_concat_kernel, dim3(1), 64, Cq);
+        for (int s = 0; s < Q.n; s++) if (readq[s]) LVI_HIP(hipEventRecord(Q[s].ev_kept[Q[s].kept_slot], Q.c.stream));
+        if (cams) LVI_TLAUNCH(Q, "mei_undistort", 16.0 * F, mei_undistort_kernel, dim3(div_up(F, 64)), 64, Mq);
+    };
+    frame_end_kernels(S, C, M, read);
+    LVI_HIP(hipStreamSynchronize(S.c.stream));                      // the ONE wait of the frame end, all slots
+    redone = 0;
+    for (int s = 0; s < S.n; s++) {
+        if (n_kept[s] < 0 || !with_gftt[s]) continue;
+        lvi_tracker& t = S[s];
+        if (reinterpret_cast<const int*>(t.h_frame_out)[0] != -2) continue;
+        redone |= 1 << s;
+        enqueue_gftt(S.one(s), TAKE_ALL, &t.gftt_pending_max, false);
+        TBatch<ConcatArgs> C1{}; TBatch<MeiArgs> M1{};
+        C1.a[0] = C.a[s]; M1.a[0] = M.a[s];
+        frame_end_kernels(S.one(s), C1, M1, read + s);
+    }
+    if (redone) LVI_HIP(hipStreamSynchronize(S.c.stream));
+    int32_t rc = LVI_OK;
+    for (int s = 0; s < S.n; s++) {
+        if (n_kept[s] < 0) continue;
+        lvi_tracker& t = S[s];
+        const int* hdr = reinterpret_cast<const int*>(t.h_frame_out);
+        t.gftt_pending = false;
+        const int nn = with_gftt[s] ? hdr[0] : 0;
+        if (nn < 0) { rc = fail(LVI_ERR_CAPACITY, "more corners than the pick kernel's accepted-list capacity"); continue; }
+        if (nn > F || n_kept[s] + nn > F) { rc = fail(LVI_ERR_CAPACITY, "more corners than max_features"); continue; }
+        if (nn > new_capacity) { rc = fail(LVI_ERR_CAPACITY, "capacity too small"); continue; }
+        n_new[s] = nn;
+        if (with_gftt[s]) { t.gftt_n = nn; t.gftt_ncand = hdr[1]; t.have_gftt = true; }
+        if (nn && new_xy && new_xy[s]) std::memcpy(new_xy[s], t.h_frame_out + 4, sizeof(float) * 2 * (size_t)nn);
+        if (cams && un_xy && un_xy[s]) std::memcpy(un_xy[s], t.h_frame_out + 4 + 2 * (size_t)F, sizeof(float) * 2 * (size_t)(n_kept[s] + nn));
+    }
+    return rc;
+}
+
+TSlots one_slot(lvi_tracker* t) { return TSlots{t->ctx, t, 1}; }
 
 }  // namespace
 
@@ -1154,27 +1415,7 @@ int32_t lvi_tracker_push_image(lvi_tracker* t, const uint8_t* img, int32_t w, in
 {
     if (!t || !img || w <= 0 || h <= 0 || stride < w) return fail(LVI_ERR_INVALID_ARG, "bad image");
     if (w > t->P.max_width || h > t->P.max_height) return fail(LVI_ERR_CAPACITY, "image exceeds capacity");
-    return guarded(t->device, [&]() -> int32_t {
-        if (t->have_forw && (w != t->w || h != t->h)) { t->have_forw = t->have_cur = false; }
-        if (t->have_forw) { std::swap(t->cur, t->forw); t->have_cur = true; }     // cur_img = forw_img (:203)
-        t->w = w; t->h = h;
-        const int slot = (t->frame_slot ^= 1);
-        LVI_HIP(hipEventSynchronize(t->ev_frame[slot]));                           // the copy that last used this staging buffer (two frames ago)
-        for (int y = 0; y < h; y++) std::memcpy(t->h_frame[slot] + (size_t)y * w, img + (size_t)y * stride, (size_t)w);
-        uint8_t* dst0 = t->equalize ? t->d_stage : t->pyr[t->forw].lv[0].px;
-        LVI_HIP(hipMemcpyAsync(dst0, t->h_frame[slot], (size_t)w * h, hipMemcpyHostToDevice, t->ctx.stream));
-        LVI_HIP(hipEventRecord(t->ev_frame[slot], t->ctx.stream));
-        if (t->equalize) run_clahe(*t, t->d_stage, t->pyr[t->forw].lv[0].px, w, h, t->clahe_clip, t->clahe_tx, t->clahe_ty);   // readImage's EQUALIZE branch (:86-90)
-        build_pyramid(*t, t->forw);
-        if (!t->have_forw) {                                                       // prev = cur = forw = img (:94-97)
-            LVI_HIP(hipMemcpyAsync(t->pyr[t->cur].lv[0].px, t->pyr[t->forw].lv[0].px, (size_t)w * h, hipMemcpyDeviceToDevice, t->ctx.stream));
-            build_pyramid(*t, t->cur);
-            t->have_cur = true;
-        }
-        // no stream sync: the caller's buffer was consumed by the host copy above
-        t->have_forw = true; t->have_lk = false; t->have_gftt = false;
-        return LVI_OK;
-    });
+    return guarded(t->device, [&]() -> int32_t { stage_push(one_slot(t), &img, TAKE_ALL, w, h, stride); return LVI_OK; });
 }
 
 int32_t lvi_clahe(lvi_tracker* t, const uint8_t* img, int32_t w, int32_t h, int32_t stride, double clip_limit, int32_t tiles_x, int32_t tiles_y,
@@ -1185,7 +1426,9 @@ int32_t lvi_clahe(lvi_tracker* t, const uint8_t* img, int32_t w, int32_t h, int3
     if (w > t->P.max_width || h > t->P.max_height) return fail(LVI_ERR_CAPACITY, "image exceeds capacity");
     return guarded(t->device, [&]() -> int32_t {
         LVI_HIP(hipMemcpy2DAsync(t->d_stage, (size_t)w, img, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, t->ctx.stream));
-        run_clahe(*t, t->d_stage, t->d_eq, w, h, clip_limit, tiles_x, tiles_y);
+        TBatch<ClaheArgs> B{};
+        B.a[0] = clahe_args(*t, t->d_stage, t->d_eq, w, h, clip_limit, tiles_x, tiles_y);
+        run_clahe(one_slot(t), B, tiles_x * tiles_y, w, h, (double)w * h);
         LVI_HIP(hipMemcpy2DAsync(out, (size_t)out_stride, t->d_eq, (size_t)w, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, t->ctx.stream));
         LVI_HIP(hipStreamSynchronize(t->ctx.stream));
         return LVI_OK;
@@ -1207,7 +1450,9 @@ int32_t lvi_undistort_points(lvi_tracker* t, const lvi_mei_params* cam, const fl
     if (n == 0) return LVI_OK;
     return guarded(t->device, [&]() -> int32_t {
         LVI_HIP(hipMemcpyAsync(t->d_un_in, xy, sizeof(float) * 2 * n, hipMemcpyHostToDevice, t->ctx.stream));
-        LVI_LAUNCH(t->ctx, "mei_undistort", 16.0 * n, hipLaunchKernelGGL(mei_undistort_kernel, dim3(div_up(n, 64)), dim3(64), 0, t->ctx.stream, *cam, t->d_un_in, n, t->d_un_out, (const int*)nullptr));
+        TBatch<MeiArgs> M{};
+        M.a[0] = MeiArgs{*cam, t->d_un_in, t->d_un_out, nullptr, n};
+        LVI_TLAUNCH(one_slot(t), "mei_undistort", 16.0 * n, mei_undistort_kernel, dim3(div_up(n, 64)), 64, M);
         LVI_HIP(hipMemcpyAsync(un_xy, t->d_un_out, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, t->ctx.stream));
         LVI_HIP(hipStreamSynchronize(t->ctx.stream));
         return LVI_OK;
@@ -1218,56 +1463,19 @@ int32_t lvi_tracker_set_points(lvi_tracker* t, const float* cur_xy, int32_t n)
 {
     if (!t || n < 0 || (n > 0 && !cur_xy)) return fail(LVI_ERR_INVALID_ARG, "bad points");
     if (n > t->P.max_features) return fail(LVI_ERR_CAPACITY, "too many points");
-    return guarded(t->device, [&]() -> int32_t {
-        if (n) {
-            const int slot = (t->pts_slot ^= 1);
-            LVI_HIP(hipEventSynchronize(t->ev_pts[slot]));
-            std::memcpy(t->h_pts[slot], cur_xy, sizeof(float) * 2 * (size_t)n);
-            t->cur_src = t->h_pts[slot]; t->cur_slot = slot;               // lk_kernel reads them in place
-        }
-        t->n_pts = n; t->have_lk = false;
-        return LVI_OK;
-    });
+    return guarded(t->device, [&]() -> int32_t { stage_set_points(one_slot(t), &cur_xy, &n); return LVI_OK; });
 }
 
 int32_t lvi_tracker_run_lk(lvi_tracker* t)
 {
     if (!t || !t->have_forw || !t->have_cur) return fail(LVI_ERR_STATE, "no image pair");
-    return guarded(t->device, [&]() -> int32_t {
-        LkArgs a{};
-        a.prev = t->pyr[t->cur]; a.next = t->pyr[t->forw];
-        const size_t F = (size_t)std::max(t->P.max_features, 64);
-        a.prev_xy = t->cur_src ? t->cur_src : t->d_cur_xy; a.next_xy = t->d_forw_xy; a.status = t->d_status; a.err = t->d_err;
-        a.h_next_xy = t->h_lk; a.h_err = t->h_lk + 2 * F; a.h_status = reinterpret_cast<uint8_t*>(t->h_lk + 3 * F);
-        a.n = t->n_pts; a.win = t->P.lk_win; a.max_level = std::min(a.prev.top, a.next.top);
-        a.max_count = std::min(std::max(t->P.lk_max_iters, 0), 100);
-        double eps = std::min(std::max(t->P.lk_eps, 0.), 10.);
-        a.epsilon = eps * eps; a.min_eig = t->P.lk_min_eig_threshold;
-        if (a.n > 0) {
-            const double bytes = (double)a.n * (a.max_level + 1) * (24.0 * 24 + 22.0 * 22 * 4);
-            LVI_LAUNCH(t->ctx, "lk_track", bytes, hipLaunchKernelGGL(lk_kernel, dim3(a.n), dim3(64), 0, t->ctx.stream, a));
-            if (t->cur_slot >= 0) LVI_HIP(hipEventRecord(t->ev_pts[t->cur_slot], t->ctx.stream));      // the slot is free again once this kernel has read it
-        }
-        t->have_lk = true;
-        return LVI_OK;
-    });
+    return guarded(t->device, [&]() -> int32_t { stage_run_lk(one_slot(t), TAKE_ALL); return LVI_OK; });     // (again with the last points, if called again)
 }
 
 int32_t lvi_tracker_get_lk(lvi_tracker* t, float* forw_xy, uint8_t* status, float* err, int32_t capacity, int32_t* n)
 {
     if (!t || !n) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    if (!t->have_lk) return fail(LVI_ERR_STATE, "LK not run");
-    *n = t->n_pts;
-    if (capacity < *n) return fail(LVI_ERR_CAPACITY, "capacity too small");
-    return guarded(t->device, [&]() -> int32_t {
-        const int m = *n;
-        const size_t F = (size_t)std::max(t->P.max_features, 64);
-        LVI_HIP(hipStreamSynchronize(t->ctx.stream));                      // lk_kernel wrote the results into pinned host memory
-        if (m && forw_xy) std::memcpy(forw_xy, t->h_lk, sizeof(float) * 2 * (size_t)m);
-        if (m && err) std::memcpy(err, t->h_lk + 2 * F, sizeof(float) * (size_t)m);
-        if (m && status) std::memcpy(status, t->h_lk + 3 * F, (size_t)m);
-        return LVI_OK;
-    });
+    return get_lk(t->ctx, t, true, forw_xy, status, err, capacity, n);
 }
 
 int32_t lvi_tracker_set_mask(lvi_tracker* t, const uint8_t* mask, int32_t w, int32_t h, int32_t stride)
@@ -1283,50 +1491,13 @@ int32_t lvi_tracker_set_mask(lvi_tracker* t, const uint8_t* mask, int32_t w, int
     });
 }
 
-namespace {
-// goodFeaturesToTrack on forw, enqueued only.  lds_form: the candidates are sorted and picked by ONE workgroup in LDS (a frame with
-// more than GFTT_LDS_MAX candidates reports -2 in d_out_n and is redone in the radix form by whoever fetches the result).
-GfttArgs gftt_args(lvi_tracker* t)
-{
-    GfttArgs a{};
-    a.img = t->pyr[t->forw].lv[0].px; a.mask = t->have_mask ? t->d_mask : nullptr; a.w = t->w; a.h = t->h;
-    a.eig = t->d_eig; a.maxord = t->d_maxord; a.maxPartial = t->d_maxPartial; a.thr = t->d_thr; a.blockCnt = t->d_blockCnt; a.total = t->d_total;
-    a.keysA = t->sort.keysA; a.valsA = t->sort.valsA; a.d_n = t->d_n; a.d_nbits = t->d_nbits; a.quality = t->P.gftt_quality;
-    return a;
-}
-PickArgs pick_args(lvi_tracker* t, int32_t max_corners)
-{
-    PickArgs p{};
-    p.keysA = t->sort.keysA; p.valsA = t->sort.valsA; p.valsB = t->sort.valsB; p.d_nbits = t->d_nbits; p.total = t->d_total;
-    p.w = t->w; p.h = t->h; p.max_corners = max_corners; p.cap = t->P.max_features; p.min_dist = t->P.min_dist;
-    p.out_xy = t->d_gftt_xy; p.out_n = t->d_out_n; p.ncand = t->d_ncand; p.dbg = t->d_dbg;
-    return p;
-}
-void enqueue_gftt(lvi_tracker* t, int32_t max_corners, bool lds_form)
-{
-    const int w = t->w, h = t->h, npx = w * h;
-    const GfttArgs a = gftt_args(t);
-    const int nblk = div_up(npx, CAND_TILE);
-    LVI_LAUNCH(t->ctx, "gftt_mineig", 2.0 * npx + 4.0 * npx, hipLaunchKernelGGL(mineig_kernel, dim3(div_up(w, 32), div_up(h, 8)), dim3(256), 0, t->ctx.stream, a));
-    LVI_LAUNCH(t->ctx, "gftt_count", 5.0 * npx, hipLaunchKernelGGL(gftt_count_kernel, dim3(nblk), dim3(256), 0, t->ctx.stream, a, div_up(w, 32) * div_up(h, 8)));
-    LVI_LAUNCH(t->ctx, "gftt_emit", 5.0 * npx, hipLaunchKernelGGL(gftt_emit_kernel, dim3(nblk), dim3(256), 0, t->ctx.stream, a, nblk));
-    const PickArgs p = pick_args(t, max_corners);
-    if (lds_form) {
-        LVI_LAUNCH(t->ctx, "gftt_sortpick", 0, hipLaunchKernelGGL(gftt_pick_kernel<true>, dim3(1), dim3(1024), 0, t->ctx.stream, p));
-    } else {
-        radix_sort_pairs(t->ctx, t->sort, t->d_n, t->d_nbits, 4, "gftt", 0.02 * npx);
-        LVI_LAUNCH(t->ctx, "gftt_pick", 0, hipLaunchKernelGGL(gftt_pick_kernel<false>, dim3(1), dim3(64), 0, t->ctx.stream, p));
-    }
-}
-}  // namespace
-
 int32_t lvi_tracker_run_gftt(lvi_tracker* t, int32_t max_corners)
 {
     if (!t || !t->have_forw) return fail(LVI_ERR_STATE, "no image");
     return guarded(t->device, [&]() -> int32_t {
         int res[2] = {0, 0};
         for (int attempt = 0; attempt < 2; attempt++) {
-            enqueue_gftt(t, max_corners, attempt == 0 && !t->gftt_force_radix);
+            enqueue_gftt(one_slot(t), TAKE_ALL, &max_corners, attempt == 0 && !t->gftt_force_radix);
             LVI_HIP(hipMemcpyAsync(&res[0], t->d_out_n, sizeof(int), hipMemcpyDeviceToHost, t->ctx.stream));
             LVI_HIP(hipMemcpyAsync(&res[1], t->d_ncand, sizeof(int), hipMemcpyDeviceToHost, t->ctx.stream));
             LVI_HIP(hipStreamSynchronize(t->ctx.stream));
@@ -1345,33 +1516,13 @@ int32_t lvi_tracker_set_mask_circles(lvi_tracker* t, const float* centers_xy, in
     if (!t || n < 0 || (n > 0 && !centers_xy) || radius < 0 || radius > 120) return fail(LVI_ERR_INVALID_ARG, "bad circle list");
     if (!t->have_forw) return fail(LVI_ERR_STATE, "no image");
     if (n > t->P.max_features) return fail(LVI_ERR_CAPACITY, "too many circles");
-    return guarded(t->device, [&]() -> int32_t {
-        CircleArgs a{t->d_mask, t->w, t->h, t->d_centers, n, radius};
-        int slot = -1;
-        if (n) {
-            slot = (t->centers_slot ^= 1);
-            LVI_HIP(hipEventSynchronize(t->ev_centers[slot]));
-            std::memcpy(t->h_centers[slot], centers_xy, sizeof(float) * 2 * (size_t)n);
-            a.centers = t->h_centers[slot];                                 // read in place (pinned host memory)
-        }
-        LVI_LAUNCH(t->ctx, "mask_fill", (double)t->w * t->h, hipLaunchKernelGGL(mask_fill_kernel, dim3(div_up(div_up(t->w * t->h, 16), 256)), dim3(256), 0, t->ctx.stream, a));
-        if (n) {
-            LVI_LAUNCH(t->ctx, "mask_circles", 0, hipLaunchKernelGGL(mask_circles_kernel, dim3(n), dim3(64), 0, t->ctx.stream, a));
-            LVI_HIP(hipEventRecord(t->ev_centers[slot], t->ctx.stream));
-        }
-        t->have_mask = true;
-        return LVI_OK;
-    });
+    return guarded(t->device, [&]() -> int32_t { stage_mask_circles(one_slot(t), &centers_xy, &n, radius); return LVI_OK; });
 }
 
 int32_t lvi_tracker_run_gftt_async(lvi_tracker* t, int32_t max_corners)
 {
     if (!t || !t->have_forw) return fail(LVI_ERR_STATE, "no image");
-    return guarded(t->device, [&]() -> int32_t {
-        enqueue_gftt(t, max_corners, !t->gftt_force_radix);
-        t->gftt_pending = true; t->gftt_pending_max = max_corners; t->have_gftt = false;
-        return LVI_OK;
-    });
+    return guarded(t->device, [&]() -> int32_t { stage_gftt_async(one_slot(t), TAKE_ALL, &max_corners); return LVI_OK; });
 }
 
 int32_t lvi_tracker_finish_frame(lvi_tracker* t, const lvi_mei_params* cam, const float* kept_xy, int32_t n_kept,
@@ -1380,39 +1531,8 @@ int32_t lvi_tracker_finish_frame(lvi_tracker* t, const lvi_mei_params* cam, cons
     if (!t || n_kept < 0 || (n_kept > 0 && !kept_xy) || !n_new) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     if (n_kept > t->P.max_features) return fail(LVI_ERR_CAPACITY, "too many points");
     return guarded(t->device, [&]() -> int32_t {
-        const int F = t->P.max_features;
-        for (int attempt = 0; attempt < 2; attempt++) {
-            const bool with_gftt = t->gftt_pending;
-            const float* kept_src = t->d_un_in;
-            int slot = -1;
-            if (n_kept) {
-                slot = (t->kept_slot ^= 1);
-                LVI_HIP(hipEventSynchronize(t->ev_kept[slot]));
-                std::memcpy(t->h_kept[slot], kept_xy, sizeof(float) * 2 * (size_t)n_kept);
-                kept_src = t->h_kept[slot];                                 // read in place
-            }
-            int* d_hdr = reinterpret_cast<int*>(t->d_frame_out);
-            int* h_hdr = reinterpret_cast<int*>(t->h_frame_out);
-            LVI_LAUNCH(t->ctx, "frame_concat", 0, hipLaunchKernelGGL(frame_concat_kernel, dim3(1), dim3(64), 0, t->ctx.stream, kept_src, n_kept, t->d_gftt_xy, t->d_out_n, t->d_ncand,
-                                                                     with_gftt ? 1 : 0, F, t->d_all_xy, d_hdr, h_hdr, t->h_frame_out + 4));
-            if (slot >= 0) LVI_HIP(hipEventRecord(t->ev_kept[slot], t->ctx.stream));
-            if (cam) LVI_LAUNCH(t->ctx, "mei_undistort", 16.0 * F, hipLaunchKernelGGL(mei_undistort_kernel, dim3(div_up(F, 64)), dim3(64), 0, t->ctx.stream, *cam, t->d_all_xy, F,
-                                                                                       t->h_frame_out + 4 + 2 * (size_t)F, (const int*)(d_hdr + 2)));
-            LVI_HIP(hipStreamSynchronize(t->ctx.stream));                   // the ONE wait of the frame end: both kernels wrote into pinned host memory
-            const int* hdr = reinterpret_cast<const int*>(t->h_frame_out);
-            if (with_gftt && hdr[0] == -2 && attempt == 0) { enqueue_gftt(t, t->gftt_pending_max, false); continue; }   // beyond the LDS form: redo in the radix form
-            t->gftt_pending = false;
-            const int nn = with_gftt ? hdr[0] : 0;
-            if (nn < 0) return fail(LVI_ERR_CAPACITY, "more corners than the pick kernel's accepted-list capacity");
-            if (nn > F || n_kept + nn > F) return fail(LVI_ERR_CAPACITY, "more corners than max_features");
-            if (nn > new_capacity) return fail(LVI_ERR_CAPACITY, "capacity too small");
-            *n_new = nn;
-            if (with_gftt) { t->gftt_n = nn; t->gftt_ncand = hdr[1]; t->have_gftt = true; }
-            if (nn && new_xy) std::memcpy(new_xy, t->h_frame_out + 4, sizeof(float) * 2 * (size_t)nn);
-            if (cam && un_xy) std::memcpy(un_xy, t->h_frame_out + 4 + 2 * (size_t)F, sizeof(float) * 2 * (size_t)(n_kept + nn));
-            return LVI_OK;
-        }
-        return LVI_OK;
+        int32_t redone;
+        return stage_frame_end(one_slot(t), cam, &kept_xy, &n_kept, &new_xy, new_capacity, n_new, &un_xy, redone);
     });
 }
 
@@ -1550,7 +1670,8 @@ int32_t lvi_tracker_prof_read(lvi_tracker* t, lvi_kernel_stat* stats, int32_t ca
 // =============================================================================================
 // lvi_tbatch (include/lvi_tbatch.h): up to 8 tracker states in one arena on one stream, every stage one launch for all
 // slots.  A slot IS an lvi_tracker state (same buffers, same pinned double slots, same flags) whose launches go through the
-// handle's stream and profiler; the host side of every call is the single handle's, slot by slot, around one batched launch.
+// handle's stream and profiler.  Every call checks its tables for all slots and runs the stage routine of the single handle
+// over the set of its S slots; what the handle adds is which slots set_points armed and whether an LK result is awaited.
 // =============================================================================================
 struct lvi_tbatch {
     lvi_tracker_params P;
@@ -1564,40 +1685,7 @@ struct lvi_tbatch {
 
 namespace {
 
-template <class K, class T>
-void launch_batch(lvi_tbatch* b, const char* name, double bytes, K kernel, dim3 grid, int threads, const TBatch<T>& B)
-{
-    grid.z = (unsigned)b->S;
-    LVI_LAUNCH(b->ctx, name, bytes, hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, b->ctx.stream, B));
-}
-
-// build_pyramid for the slots of `take`: one launch per level; a slot whose pyramid ends early has a zeroed block in the deeper launches
-void build_pyramids(lvi_tbatch* b, const bool* take, bool cur_side)
-{
-    int maxtop = 0;
-    for (int s = 0; s < b->S; s++) {
-        if (!take[s]) continue;
-        lvi_tracker& t = b->slot[s];
-        Pyr& p = t.pyr[cur_side ? t.cur : t.forw];
-        plan_pyramid(p, t.w, t.h, t.P);
-        maxtop = std::max(maxtop, p.top);
-    }
-    for (int level = 1; level <= maxtop; level++) {
-        TBatch<PyrArgs> B{};
-        int gx = 0, gy = 0; double bytes = 0;
-        for (int s = 0; s < b->S; s++) {
-            if (!take[s]) continue;
-            lvi_tracker& t = b->slot[s];
-            const Pyr& p = t.pyr[cur_side ? t.cur : t.forw];
-            if (level > p.top) continue;
-            B.a[s] = PyrArgs{p.lv[level - 1].px, p.lv[level].px, p.lv[level - 1].w, p.lv[level - 1].h, p.lv[level].w, p.lv[level].h};
-            gx = std::max(gx, div_up(p.lv[level].w, 32)); gy = std::max(gy, div_up(p.lv[level].h, 8));
-            bytes += (double)p.lv[level - 1].w * p.lv[level - 1].h + (double)p.lv[level].w * p.lv[level].h;
-        }
-        launch_batch(b, "pyrdown", bytes, pyrdown_batch_kernel, dim3(gx, gy), 256, B);
-    }
-}
-
+TSlots all_slots(lvi_tbatch* b) { return TSlots{b->ctx, b->slot, b->S}; }
 int32_t bad_slot(const lvi_tbatch* b, int32_t slot) { return !b || slot < 0 || slot >= b->S; }
 
 }  // namespace
@@ -1665,54 +1753,10 @@ int32_t lvi_tbatch_push_images(lvi_tbatch* b, const uint8_t* const* imgs, int32_
 {
     if (!b || !imgs || w <= 0 || h <= 0 || stride < w) return fail(LVI_ERR_INVALID_ARG, "bad image table");
     if (w > b->P.max_width || h > b->P.max_height) return fail(LVI_ERR_CAPACITY, "image exceeds capacity");
-    bool take[LVI_TRACKER_MAX_BATCH] = {}, first[LVI_TRACKER_MAX_BATCH] = {}, any = false;
+    bool take[LVI_TRACKER_MAX_BATCH] = {}, any = false;
     for (int s = 0; s < b->S; s++) { take[s] = imgs[s] != nullptr; any = any || take[s]; }
     if (!any) return LVI_OK;
-    return guarded(b->device, [&]() -> int32_t {
-        bool any_first = false;
-        for (int s = 0; s < b->S; s++) {
-            if (!take[s]) continue;
-            lvi_tracker* t = &b->slot[s];
-            if (t->have_forw && (w != t->w || h != t->h)) { t->have_forw = t->have_cur = false; }
-            if (t->have_forw) { std::swap(t->cur, t->forw); t->have_cur = true; }     // cur_img = forw_img (:203), this slot's own rotation
-            first[s] = !t->have_forw; any_first = any_first || first[s];
-            t->w = w; t->h = h;
-            const int fs = (t->frame_slot ^= 1);
-            LVI_HIP(hipEventSynchronize(t->ev_frame[fs]));
-            for (int y = 0; y < h; y++) std::memcpy(t->h_frame[fs] + (size_t)y * w, imgs[s] + (size_t)y * stride, (size_t)w);
-            uint8_t* dst0 = t->equalize ? t->d_stage : t->pyr[t->forw].lv[0].px;
-            LVI_HIP(hipMemcpyAsync(dst0, t->h_frame[fs], (size_t)w * h, hipMemcpyHostToDevice, b->ctx.stream));
-            LVI_HIP(hipEventRecord(t->ev_frame[fs], b->ctx.stream));
-        }
-        if (b->slot[0].equalize) {                                                  // readImage's EQUALIZE branch (:86-90), all slots alike
-            TBatch<ClaheArgs> B{};
-            int ntile = 0; double px = 0;
-            for (int s = 0; s < b->S; s++) {
-                if (!take[s]) continue;
-                lvi_tracker& t = b->slot[s];
-                B.a[s] = clahe_args(t, t.d_stage, t.pyr[t.forw].lv[0].px, w, h, t.clahe_clip, t.clahe_tx, t.clahe_ty);
-                ntile = B.a[s].tilesX * B.a[s].tilesY; px += (double)w * h;
-            }
-            launch_batch(b, "clahe_lut", px, clahe_lut_batch_kernel, dim3(ntile), 1024, B);
-            launch_batch(b, "clahe_interp", 2.0 * px, clahe_interp_batch_kernel, dim3(div_up(w, 64), div_up(h, 4)), 256, B);
-        }
-        build_pyramids(b, take, false);
-        if (any_first) {                                                            // prev = cur = forw = img (:94-97)
-            for (int s = 0; s < b->S; s++) {
-                if (!first[s]) continue;
-                lvi_tracker& t = b->slot[s];
-                LVI_HIP(hipMemcpyAsync(t.pyr[t.cur].lv[0].px, t.pyr[t.forw].lv[0].px, (size_t)w * h, hipMemcpyDeviceToDevice, b->ctx.stream));
-            }
-            build_pyramids(b, first, true);
-        }
-        for (int s = 0; s < b->S; s++) {
-            if (!take[s]) continue;
-            lvi_tracker& t = b->slot[s];
-            if (first[s]) t.have_cur = true;
-            t.have_forw = true; t.have_lk = false; t.have_gftt = false;
-        }
-        return LVI_OK;
-    });
+    return guarded(b->device, [&]() -> int32_t { stage_push(all_slots(b), imgs, take, w, h, stride); return LVI_OK; });
 }
 
 int32_t lvi_tbatch_set_points(lvi_tbatch* b, const float* const* cur_xy, const int32_t* n)
@@ -1723,18 +1767,8 @@ int32_t lvi_tbatch_set_points(lvi_tbatch* b, const float* const* cur_xy, const i
         if (n[s] > b->P.max_features) return fail(LVI_ERR_CAPACITY, "too many points");
     }
     return guarded(b->device, [&]() -> int32_t {
-        for (int s = 0; s < b->S; s++) {
-            if (n[s] < 0) continue;
-            lvi_tracker* t = &b->slot[s];
-            if (n[s]) {
-                const int ps = (t->pts_slot ^= 1);
-                LVI_HIP(hipEventSynchronize(t->ev_pts[ps]));
-                std::memcpy(t->h_pts[ps], cur_xy[s], sizeof(float) * 2 * (size_t)n[s]);
-                t->cur_src = t->h_pts[ps]; t->cur_slot = ps;
-            }
-            t->n_pts = n[s]; t->have_lk = false;
-            b->armed[s] = true;
-        }
+        stage_set_points(all_slots(b), cur_xy, n);
+        for (int s = 0; s < b->S; s++) if (n[s] >= 0) b->armed[s] = true;
         return LVI_OK;
     });
 }
@@ -1745,32 +1779,8 @@ int32_t lvi_tbatch_run_lk(lvi_tbatch* b)
     for (int s = 0; s < b->S; s++)
         if (b->armed[s] && (!b->slot[s].have_forw || !b->slot[s].have_cur)) return fail(LVI_ERR_STATE, "no image pair");
     return guarded(b->device, [&]() -> int32_t {
-        TBatch<LkArgs> B{};
-        int nmax = 0; double bytes = 0;
-        for (int s = 0; s < b->S; s++) {
-            if (!b->armed[s]) continue;
-            lvi_tracker* t = &b->slot[s];
-            LkArgs& a = B.a[s];
-            a.prev = t->pyr[t->cur]; a.next = t->pyr[t->forw];
-            const size_t F = (size_t)std::max(t->P.max_features, 64);
-            a.prev_xy = t->cur_src ? t->cur_src : t->d_cur_xy; a.next_xy = t->d_forw_xy; a.status = t->d_status; a.err = t->d_err;
-            a.h_next_xy = t->h_lk; a.h_err = t->h_lk + 2 * F; a.h_status = reinterpret_cast<uint8_t*>(t->h_lk + 3 * F);
-            a.n = t->n_pts; a.win = t->P.lk_win; a.max_level = std::min(a.prev.top, a.next.top);
-            a.max_count = std::min(std::max(t->P.lk_max_iters, 0), 100);
-            const double eps = std::min(std::max(t->P.lk_eps, 0.), 10.);
-            a.epsilon = eps * eps; a.min_eig = t->P.lk_min_eig_threshold;
-            nmax = std::max(nmax, a.n);
-            bytes += (double)a.n * (a.max_level + 1) * (24.0 * 24 + 22.0 * 22 * 4);
-        }
-        if (nmax > 0) {
-            launch_batch(b, "lk_track", bytes, lk_batch_kernel, dim3(nmax), 64, B);
-            for (int s = 0; s < b->S; s++) {
-                lvi_tracker* t = &b->slot[s];
-                if (b->armed[s] && t->n_pts > 0 && t->cur_slot >= 0) LVI_HIP(hipEventRecord(t->ev_pts[t->cur_slot], b->ctx.stream));
-            }
-            b->lk_in_flight = true;
-        }
-        for (int s = 0; s < b->S; s++) if (b->armed[s]) { b->slot[s].have_lk = true; b->armed[s] = false; }
+        if (stage_run_lk(all_slots(b), b->armed)) b->lk_in_flight = true;       // only the slots armed by set_points: no re-run
+        for (int s = 0; s < b->S; s++) b->armed[s] = false;
         return LVI_OK;
     });
 }
@@ -1778,19 +1788,9 @@ int32_t lvi_tbatch_run_lk(lvi_tbatch* b)
 int32_t lvi_tbatch_get_lk(lvi_tbatch* b, int32_t slot, float* forw_xy, uint8_t* status, float* err, int32_t capacity, int32_t* n)
 {
     if (bad_slot(b, slot) || !n) return fail(LVI_ERR_INVALID_ARG, "bad slot or null argument");
-    lvi_tracker* t = &b->slot[slot];
-    if (!t->have_lk) return fail(LVI_ERR_STATE, "LK not run");
-    *n = t->n_pts;
-    if (capacity < *n) return fail(LVI_ERR_CAPACITY, "capacity too small");
-    return guarded(b->device, [&]() -> int32_t {
-        const int m = *n;
-        const size_t F = (size_t)std::max(t->P.max_features, 64);
-        if (b->lk_in_flight) { LVI_HIP(hipStreamSynchronize(b->ctx.stream)); b->lk_in_flight = false; }     // the one wait for all slots
-        if (m && forw_xy) std::memcpy(forw_xy, t->h_lk, sizeof(float) * 2 * (size_t)m);
-        if (m && err) std::memcpy(err, t->h_lk + 2 * F, sizeof(float) * (size_t)m);
-        if (m && status) std::memcpy(status, t->h_lk + 3 * F, (size_t)m);
-        return LVI_OK;
-    });
+    const int32_t st = get_lk(b->ctx, &b->slot[slot], b->lk_in_flight, forw_xy, status, err, capacity, n);       // the one wait for all slots
+    if (st == LVI_OK) b->lk_in_flight = false;
+    return st;
 }
 
 int32_t lvi_tbatch_set_mask_circles(lvi_tbatch* b, const float* const* centers_xy, const int32_t* n, int32_t radius)
@@ -1804,66 +1804,20 @@ int32_t lvi_tbatch_set_mask_circles(lvi_tbatch* b, const float* const* centers_x
         any = any || n[s] >= 0;
     }
     if (!any) return LVI_OK;
-    return guarded(b->device, [&]() -> int32_t {
-        TBatch<CircleArgs> B{};
-        int cs[LVI_TRACKER_MAX_BATCH]; int nmax = 0, gfill = 0; double px = 0;
-        for (int s = 0; s < b->S; s++) {
-            cs[s] = -1;
-            if (n[s] < 0) continue;
-            lvi_tracker* t = &b->slot[s];
-            B.a[s] = CircleArgs{t->d_mask, t->w, t->h, t->d_centers, n[s], radius};
-            if (n[s]) {
-                cs[s] = (t->centers_slot ^= 1);
-                LVI_HIP(hipEventSynchronize(t->ev_centers[cs[s]]));
-                std::memcpy(t->h_centers[cs[s]], centers_xy[s], sizeof(float) * 2 * (size_t)n[s]);
-                B.a[s].centers = t->h_centers[cs[s]];
-            }
-            nmax = std::max(nmax, n[s]); gfill = std::max(gfill, div_up(div_up(t->w * t->h, 16), 256)); px += (double)t->w * t->h;
-        }
-        launch_batch(b, "mask_fill", px, mask_fill_batch_kernel, dim3(gfill), 256, B);
-        if (nmax) {
-            launch_batch(b, "mask_circles", 0, mask_circles_batch_kernel, dim3(nmax), 64, B);
-            for (int s = 0; s < b->S; s++) if (cs[s] >= 0) LVI_HIP(hipEventRecord(b->slot[s].ev_centers[cs[s]], b->ctx.stream));
-        }
-        for (int s = 0; s < b->S; s++) if (n[s] >= 0) b->slot[s].have_mask = true;
-        return LVI_OK;
-    });
+    return guarded(b->device, [&]() -> int32_t { stage_mask_circles(all_slots(b), centers_xy, n, radius); return LVI_OK; });
 }
 
 int32_t lvi_tbatch_run_gftt_async(lvi_tbatch* b, const int32_t* max_corners)
 {
     if (!b || !max_corners) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    bool any = false;
+    bool take[LVI_TRACKER_MAX_BATCH] = {}, any = false;
     for (int s = 0; s < b->S; s++) {
-        if (max_corners[s] >= 0 && !b->slot[s].have_forw) return fail(LVI_ERR_STATE, "no image");
-        any = any || max_corners[s] >= 0;
+        take[s] = max_corners[s] >= 0;
+        if (take[s] && !b->slot[s].have_forw) return fail(LVI_ERR_STATE, "no image");
+        any = any || take[s];
     }
     if (!any) return LVI_OK;
-    return guarded(b->device, [&]() -> int32_t {
-        if (b->slot[0].gftt_force_radix) {                          // LVI_GFTT_RADIX=1: every slot through the radix form, slot by slot
-            for (int s = 0; s < b->S; s++) if (max_corners[s] >= 0) enqueue_gftt(&b->slot[s], max_corners[s], false);
-        } else {
-            TBatch<GfttArgs> G{}; TBatch<PickArgs> K{};
-            int gx = 0, gy = 0, nblk = 0; double npx = 0;
-            for (int s = 0; s < b->S; s++) {
-                if (max_corners[s] < 0) continue;
-                lvi_tracker* t = &b->slot[s];
-                G.a[s] = gftt_args(t); K.a[s] = pick_args(t, max_corners[s]);
-                gx = std::max(gx, div_up(t->w, 32)); gy = std::max(gy, div_up(t->h, 8)); nblk = std::max(nblk, div_up(t->w * t->h, CAND_TILE));
-                npx += (double)t->w * t->h;
-            }
-            launch_batch(b, "gftt_mineig", 6.0 * npx, mineig_batch_kernel, dim3(gx, gy), 256, G);
-            launch_batch(b, "gftt_count", 5.0 * npx, gftt_count_batch_kernel, dim3(nblk), 256, G);
-            launch_batch(b, "gftt_emit", 5.0 * npx, gftt_emit_batch_kernel, dim3(nblk), 256, G);
-            launch_batch(b, "gftt_sortpick", 0, gftt_sortpick_batch_kernel, dim3(1), 1024, K);
-        }
-        for (int s = 0; s < b->S; s++) {
-            if (max_corners[s] < 0) continue;
-            lvi_tracker& t = b->slot[s];
-            t.gftt_pending = true; t.gftt_pending_max = max_corners[s]; t.have_gftt = false;
-        }
-        return LVI_OK;
-    });
+    return guarded(b->device, [&]() -> int32_t { stage_gftt_async(all_slots(b), take, max_corners); return LVI_OK; });
 }
 
 int32_t lvi_tbatch_finish_frame(lvi_tbatch* b, const lvi_mei_params* cams, const float* const* kept_xy, const int32_t* n_kept,
@@ -1878,63 +1832,8 @@ int32_t lvi_tbatch_finish_frame(lvi_tbatch* b, const lvi_mei_params* cams, const
     }
     if (!any) return LVI_OK;
     return guarded(b->device, [&]() -> int32_t {
-        const int F = b->P.max_features;
-        TBatch<ConcatArgs> C{}; TBatch<MeiArgs> M{};
-        const float* kept_src[LVI_TRACKER_MAX_BATCH]; bool with_gftt[LVI_TRACKER_MAX_BATCH]; int ks[LVI_TRACKER_MAX_BATCH];
-        for (int s = 0; s < b->S; s++) {
-            ks[s] = -1; with_gftt[s] = false; kept_src[s] = nullptr;
-            if (n_kept[s] < 0) continue;
-            lvi_tracker* t = &b->slot[s];
-            with_gftt[s] = t->gftt_pending;
-            kept_src[s] = t->d_un_in;
-            if (n_kept[s]) {
-                ks[s] = (t->kept_slot ^= 1);
-                LVI_HIP(hipEventSynchronize(t->ev_kept[ks[s]]));
-                std::memcpy(t->h_kept[ks[s]], kept_xy[s], sizeof(float) * 2 * (size_t)n_kept[s]);
-                kept_src[s] = t->h_kept[ks[s]];
-            }
-            int* d_hdr = reinterpret_cast<int*>(t->d_frame_out);
-            C.a[s] = ConcatArgs{kept_src[s], t->d_gftt_xy, t->d_out_n, t->d_ncand, t->d_all_xy, d_hdr, reinterpret_cast<int*>(t->h_frame_out), t->h_frame_out + 4,
-                                n_kept[s], with_gftt[s] ? 1 : 0, F};
-            if (cams) M.a[s] = MeiArgs{cams[s], t->d_all_xy, t->h_frame_out + 4 + 2 * (size_t)F, d_hdr + 2, F};
-        }
-        launch_batch(b, "frame_concat", 0, frame_concat_batch_kernel, dim3(1), 64, C);
-        for (int s = 0; s < b->S; s++) if (ks[s] >= 0) LVI_HIP(hipEventRecord(b->slot[s].ev_kept[ks[s]], b->ctx.stream));
-        if (cams) launch_batch(b, "mei_undistort", 16.0 * F, mei_undistort_batch_kernel, dim3(div_up(F, 64)), 64, M);
-        LVI_HIP(hipStreamSynchronize(b->ctx.stream));                   // the ONE wait of the frame end, all slots
-        b->lk_in_flight = false;
-        // a slot beyond the LDS form: redone alone in the radix form on its own state, its two frame-end kernels re-read (the kept
-        // points are still in the pinned slot the first attempt read); the other slots' results stand
-        b->redo_mask = 0;
-        for (int s = 0; s < b->S; s++) {
-            if (n_kept[s] < 0 || !with_gftt[s]) continue;
-            lvi_tracker* t = &b->slot[s];
-            if (reinterpret_cast<const int*>(t->h_frame_out)[0] != -2) continue;
-            b->redo_mask |= 1 << s;
-            enqueue_gftt(t, t->gftt_pending_max, false);
-            int* d_hdr = reinterpret_cast<int*>(t->d_frame_out);
-            LVI_LAUNCH(b->ctx, "frame_concat", 0, hipLaunchKernelGGL(frame_concat_kernel, dim3(1), dim3(64), 0, b->ctx.stream, kept_src[s], n_kept[s], t->d_gftt_xy, t->d_out_n,
-                                                                     t->d_ncand, 1, F, t->d_all_xy, d_hdr, reinterpret_cast<int*>(t->h_frame_out), t->h_frame_out + 4));
-            if (ks[s] >= 0) LVI_HIP(hipEventRecord(t->ev_kept[ks[s]], b->ctx.stream));
-            if (cams) LVI_LAUNCH(b->ctx, "mei_undistort", 16.0 * F, hipLaunchKernelGGL(mei_undistort_kernel, dim3(div_up(F, 64)), dim3(64), 0, b->ctx.stream, cams[s], t->d_all_xy, F,
-                                                                                       t->h_frame_out + 4 + 2 * (size_t)F, (const int*)(d_hdr + 2)));
-        }
-        if (b->redo_mask) LVI_HIP(hipStreamSynchronize(b->ctx.stream));
-        int32_t rc = LVI_OK;
-        for (int s = 0; s < b->S; s++) {
-            if (n_kept[s] < 0) continue;
-            lvi_tracker* t = &b->slot[s];
-            const int* hdr = reinterpret_cast<const int*>(t->h_frame_out);
-            t->gftt_pending = false;
-            const int nn = with_gftt[s] ? hdr[0] : 0;
-            if (nn < 0) { rc = fail(LVI_ERR_CAPACITY, "more corners than the pick kernel's accepted-list capacity"); continue; }
-            if (nn > F || n_kept[s] + nn > F) { rc = fail(LVI_ERR_CAPACITY, "more corners than max_features"); continue; }
-            if (nn > new_capacity) { rc = fail(LVI_ERR_CAPACITY, "capacity too small"); continue; }
-            n_new[s] = nn;
-            if (with_gftt[s]) { t->gftt_n = nn; t->gftt_ncand = hdr[1]; t->have_gftt = true; }
-            if (nn && new_xy && new_xy[s]) std::memcpy(new_xy[s], t->h_frame_out + 4, sizeof(float) * 2 * (size_t)nn);
-            if (cams && un_xy && un_xy[s]) std::memcpy(un_xy[s], t->h_frame_out + 4 + 2 * (size_t)F, sizeof(float) * 2 * (size_t)(n_kept[s] + nn));
-        }
+        const int32_t rc = stage_frame_end(all_slots(b), cams, kept_xy, n_kept, new_xy, new_capacity, n_new, un_xy, b->redo_mask);
+        b->lk_in_flight = false;                                       // (the frame end waited for the stream)
         return rc;
     });
 }
