@@ -587,6 +587,7 @@ __device__ __forceinline__ bool gftt_is_cand(const GfttArgs& a, int x, int y, fl
 {
     // the 3 x 3 neighbourhood and the mask byte are loaded unconditionally (coordinates clamped into the interior) and tested
     // afterwards: with the tests in between, a pixel was up to ten round trips in a row
+    if (a.w < 3 || a.h < 3) return false;          // no interior (candidates are 1..size-2): the clamp below would leave the image
     const int xc = min(max(x, 1), a.w - 2), yc = min(max(y, 1), a.h - 2);
     const float* e = a.eig + (size_t)yc * a.w + xc;
     float nv[9];

@@ -1,7 +1,10 @@
 """GPU tier (-m gpu): HIP LK + GFTT against the CPU oracle (restated OpenCV algorithms) through the
 same C-ABI.  LK patch arithmetic is fixed point with exact integer sums → positions, status and err
 must be bit-exact; the min-eigenvalue map follows a fixed f32 operation order → bit-exact; GFTT
-output coordinates are integers → exact.  PARITY UNPINNED (OpenCV is not in the reference tree)."""
+output coordinates are integers → exact.
+What is pinned elsewhere: the algorithms AS SURVEY APP. A.6 / A.7 STATE THEM — tests/test_gpu_tracker_ref.py holds the kernels to an
+exact / float64 reference that shares nothing with the oracle, also at non-default windows, levels, iteration limits and thresholds.
+What is still not pinned: OpenCV itself (it is not in the reference tree; the appendix is a recollection of it)."""
 import numpy as np
 import pytest
 

@@ -3,22 +3,14 @@ LK on images with known motion, min-eigenvalue / GFTT on synthetic corners."""
 import numpy as np
 import pytest
 
+from tracker_ref import pyrdown as _pyrdown_numpy        # independent of the oracle (tests/tracker_ref.py)
+
 
 @pytest.fixture()
 def T(pkg, oracle):
     t = pkg.TrackerHotpath(oracle, max_width=1280, max_height=720)
     yield t
     t.close()
-
-
-def _pyrdown_numpy(img):
-    """[1 4 6 4 1]x[1 4 6 4 1], REFLECT_101, (sum + 128) >> 8, size (w+1)/2 x (h+1)/2 — independent of the oracle"""
-    k = np.array([1, 4, 6, 4, 1], np.int64)
-    p = np.pad(img.astype(np.int64), 2, mode="reflect")
-    h, w = img.shape
-    tmp = sum(k[i] * p[:, i:i + w] for i in range(5))
-    full = sum(k[j] * tmp[j:j + h, :] for j in range(5))
-    return ((full[::2, ::2] + 128) >> 8).astype(np.uint8)
 
 
 def test_pyramid_levels(pkg, T):
