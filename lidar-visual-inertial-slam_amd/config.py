@@ -93,6 +93,16 @@ def load_camera_lidar_yaml(path):
     return dict(use_lidar=int(d["use_lidar"]), lidar_skip=int(d["lidar_skip"]), point_cloud_topic=str(d["point_cloud_topic"]))
 
 
+def load_estimator_yaml(path):
+    """→ what the marginalisation reads of the camera yaml (vins_estimator's parameters.cpp:79, 120-135): dict(estimate_td,
+    td, rolling_shutter_tr (0 without a rolling shutter), image_height, and the lvi_marg_params tr_over_row = TR / ROW and
+    half_row = ROW / 2)"""
+    d = _opencv_yaml(path)
+    row = float(d["image_height"])
+    tr = float(d["rolling_shutter_tr"]) if int(d.get("rolling_shutter", 0)) else 0.0
+    return dict(estimate_td=bool(int(d["estimate_td"])), td=float(d["td"]), rolling_shutter_tr=tr, image_height=row, tr_over_row=tr / row, half_row=row / 2)
+
+
 def load_brief_pattern(path):
     """→ (x1, y1, x2, y2): the BRIEF pair offsets of support_files/brief_pattern.yml (OpenCV FileStorage yaml; what
     BriefExtractor's constructor reads, keyframe.cpp:273-291), 256 ints each within ±24: the pattern argument of

@@ -49,6 +49,8 @@ PNP_SOURCES = ("lvi_pnp_capi.cpp",)
 PGO_SOURCES = ("lvi_pgo_capi.cpp",)
 # the camera rig's (include/lvi_tbatch.h, the same restriction; its cameras may take the device RANSAC, so FMAT_SOURCES go with it)
 TBATCH_SOURCES = ("lvi_tbatch_capi.cpp",)
+# the window marginalisation's (include/lvi_marg.h, the same restriction)
+MARG_SOURCES = ("lvi_marg_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -64,7 +66,8 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
                  os.path.join(HOST_DIR, "lvi_bow_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_bow.h"),
                  os.path.join(HOST_DIR, "lvi_bow_capi_detail.hpp"), os.path.join(HOST_DIR, "lvi_pnp_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pnp.h"),
                  os.path.join(HOST_DIR, "lvi_tbatch_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_tbatch.h"),
-                 os.path.join(HOST_DIR, "lvi_pgo_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pgo.h")]
+                 os.path.join(HOST_DIR, "lvi_pgo_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pgo.h"),
+                 os.path.join(HOST_DIR, "lvi_marg_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_marg.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
         return out_path
     cxx = which("g++") or "g++"
@@ -196,6 +199,20 @@ class HostLibrary:
             d.lvh_seq_use_gps.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float]
             d.lvh_seq_gps_push.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
             d.lvh_seq_gps_last.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        self.has_marg = hasattr(d, "lvh_marg_create")      # the HIP host library only
+        if self.has_marg:
+            from .marg import MargInfo, MargParams
+            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+            d.lvh_marg_last_error.restype = C.c_char_p
+            d.lvh_marg_create.restype = C.c_void_p
+            d.lvh_marg_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(MargParams)]
+            d.lvh_marg_destroy.argtypes = [C.c_void_p]
+            d.lvh_marg_handle.restype = C.c_void_p
+            d.lvh_marg_handle.argtypes = [C.c_void_p]
+            d.lvh_marg_set_window.argtypes = [C.c_void_p, dp, dp, dp, C.c_double]
+            d.lvh_marg_set_features.argtypes = [C.c_void_p, C.c_int32, ip, ip, dp, dp]
+            d.lvh_marg_set_imu.argtypes = [C.c_void_p, C.c_double, dp, dp]
+            d.lvh_marg_run.argtypes = [C.c_void_p, C.c_int32, ip, C.POINTER(MargInfo)]
         self.has_rig = hasattr(d, "lvh_rig_create")      # the HIP host library only
         if self.has_rig:
             d.lvh_rig_last_error.restype = C.c_char_p
@@ -856,6 +873,81 @@ class PoseGraphBackend:
         self.hl.dll.lvh_pgo_last(self._p, C.byref(info), pose, cnt)
         return dict(updates=cnt[0], loops_added=cnt[1], loops_queued=cnt[2], status=cnt[3], iterations=info.iterations, converged=bool(info.converged),
                     chi2_before=info.chi2_before, chi2_after=info.chi2_after, max_step=info.max_step, pose_to=np.array(pose[:], np.float32))
+
+
+class VinsMarginalizer:
+    """lvi_host::VinsMarginalizer (host/lvi_marg_host.hpp): the MARGIN_OLD and MARGIN_SECOND_NEW branches of
+    Estimator::optimization (estimator.cpp:813-976) over include/lvi_marg.h, the prior resident on the device.  HIP host
+    library only.  `marg` is a marg.Marginalizer view of the handle the C++ side owns (layout, prior, debug_system)."""
+    MARGIN_OLD, MARGIN_SECOND_NEW = 0, 1
+    WINDOW_SIZE = 10
+
+    def __init__(self, hostlib, abi_lib, device=0, max_features=150, estimate_td=True, **params):
+        from .marg import Marginalizer, MargParams, bind as marg_bind
+        if not hostlib.has_marg:
+            raise RuntimeError("this host library has no marginalisation (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        p = MargParams()
+        marg_bind(abi_lib).dll.lvi_marg_params_default(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"lvi_marg_params has no field {k}")
+            setattr(p, k, v)
+        self._p = hostlib.dll.lvh_marg_create(int(device), int(max_features), int(bool(estimate_td)), C.byref(p))
+        if not self._p:
+            raise A.LviError(-1, "lvh_marg_create", hostlib.dll.lvh_marg_last_error().decode(errors="replace"))
+        self.marg = Marginalizer(abi_lib, handle=hostlib.dll.lvh_marg_handle(self._p))       # never destroyed from here
+        self.marg.params = p
+
+    def close(self):
+        if self._p:
+            self.hl.dll.lvh_marg_destroy(self._p)
+            self._p = None
+            self.marg._h = C.c_void_p()                  # the view's handle went with the C++ object
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_marg_last_error().decode(errors="replace"))
+        return code
+
+    def set_window(self, pose, speed_bias, ex_pose, td):
+        """vector2double: para_Pose [11, 7], para_SpeedBias [11, 9], para_Ex_Pose [7], para_Td"""
+        dp = C.POINTER(C.c_double)
+        a, b, c = (np.ascontiguousarray(x, np.float64) for x in (pose, speed_bias, ex_pose))
+        assert a.shape == (self.WINDOW_SIZE + 1, 7) and b.shape == (self.WINDOW_SIZE + 1, 9) and c.shape == (7,)
+        self._check(self.hl.dll.lvh_marg_set_window(self._p, a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp), float(td)), "lvh_marg_set_window")
+
+    def set_features(self, features):
+        """f_manager.feature: dicts of start_frame, inv_dep and obs (dicts of point [3], velocity [2], cur_td, uv_y)"""
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        start = np.array([f["start_frame"] for f in features], np.int32)
+        n_obs = np.array([len(f["obs"]) for f in features], np.int32)
+        inv = np.array([f["inv_dep"] for f in features], np.float64)
+        obs = np.array([[*o["point"], *o["velocity"], o["cur_td"], o["uv_y"]] for f in features for o in f["obs"]], np.float64).reshape(-1, 7)
+        self._check(self.hl.dll.lvh_marg_set_features(self._p, len(features), start.ctypes.data_as(ip), n_obs.ctypes.data_as(ip), inv.ctypes.data_as(dp),
+                                                      obs.ctypes.data_as(dp)), "lvh_marg_set_features")
+
+    def set_imu(self, sum_dt, residual=None, jacobians=None):
+        """pre_integrations[1]->sum_dt and IMUFactor evaluated by the caller: residual [15], jacobians [15, 7], [15, 9], [15, 7], [15, 9]"""
+        dp = C.POINTER(C.c_double)
+        if residual is None:
+            return self._check(self.hl.dll.lvh_marg_set_imu(self._p, float(sum_dt), None, None), "lvh_marg_set_imu")
+        r = np.ascontiguousarray(residual, np.float64).reshape(15)
+        J = np.concatenate([np.ascontiguousarray(j, np.float64).reshape(15, s).ravel() for j, s in zip(jacobians, (7, 9, 7, 9))])
+        return self._check(self.hl.dll.lvh_marg_set_imu(self._p, float(sum_dt), r.ctypes.data_as(dp), J.ctypes.data_as(dp)), "lvh_marg_set_imu")
+
+    def run(self, flag):
+        """one pass through estimator.cpp:813-976 -> dict(ran, status, m, n, rank, ...)"""
+        from .marg import MargInfo
+        info, ran = MargInfo(), C.c_int32(0)
+        st = self._check(self.hl.dll.lvh_marg_run(self._p, int(flag), C.byref(ran), C.byref(info)), "lvh_marg_run")
+        return dict(ran=bool(ran.value), status=st, **{k: getattr(info, k) for k, _ in MargInfo._fields_})
 
 
 class TrackerRig:
