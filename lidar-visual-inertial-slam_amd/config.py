@@ -103,6 +103,17 @@ def load_estimator_yaml(path):
     return dict(estimate_td=bool(int(d["estimate_td"])), td=float(d["td"]), rolling_shutter_tr=tr, image_height=row, tr_over_row=tr / row, half_row=row / 2)
 
 
+def load_window_yaml(path):
+    """→ what the window solve reads of the camera yaml (vins_estimator's parameters.cpp): dict(max_solver_time (seconds),
+    max_num_iterations, estimate_extrinsic (0 fixed, 1 refined, 2 calibrated from scratch), estimate_td, acc_n, gyr_n, acc_w,
+    gyr_w, g_norm, and G = [0, 0, g_norm], the lvi_win_params gravity before the initialisation aligns it)"""
+    d = _opencv_yaml(path)
+    g = float(d["g_norm"])
+    return dict(max_solver_time=float(d["max_solver_time"]), max_num_iterations=int(d["max_num_iterations"]), estimate_extrinsic=int(d["estimate_extrinsic"]),
+                estimate_td=bool(int(d["estimate_td"])), acc_n=float(d["acc_n"]), gyr_n=float(d["gyr_n"]), acc_w=float(d["acc_w"]), gyr_w=float(d["gyr_w"]),
+                g_norm=g, G=[0.0, 0.0, g])
+
+
 def load_brief_pattern(path):
     """→ (x1, y1, x2, y2): the BRIEF pair offsets of support_files/brief_pattern.yml (OpenCV FileStorage yaml; what
     BriefExtractor's constructor reads, keyframe.cpp:273-291), 256 ints each within ±24: the pattern argument of

@@ -29,6 +29,7 @@
 
 #include "lvi_dev.hpp"
 #include "lvi_marg_math.hpp"
+#include "lvi_marg_view.hpp"
 #include "../../include/lvi_marg.h"
 
 using namespace lvi;
@@ -450,6 +451,17 @@ void appear(lvi_marg* h, int b, bool drop)
 }
 
 }  // namespace
+
+// the resident prior for the window solve (lvi_win_set_prior_from_marg): pointers into the buffers in use, nothing is copied
+bool lvi::marg_prior_view(lvi_marg* h, lvi::MargPriorView* out)
+{
+    if (!h || !out || !h->prior.valid) return false;
+    const Prior& p = h->prior;
+    out->device = h->device; out->n = p.n; out->count = (int)p.ids.size();
+    out->J = h->d_J[h->cur]; out->r = h->d_r[h->cur]; out->x0 = h->d_x[h->cur];
+    out->ids = p.ids.data(); out->sizes = p.sizes.data(); out->col = p.col.data();
+    return true;
+}
 
 extern "C" {
 

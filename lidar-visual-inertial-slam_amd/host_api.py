@@ -51,6 +51,8 @@ PGO_SOURCES = ("lvi_pgo_capi.cpp",)
 TBATCH_SOURCES = ("lvi_tbatch_capi.cpp",)
 # the window marginalisation's (include/lvi_marg.h, the same restriction)
 MARG_SOURCES = ("lvi_marg_capi.cpp",)
+# the window solve's (include/lvi_win.h, the same restriction; it optimises the marginaliser's window arrays, so MARG_SOURCES go with it)
+WIN_SOURCES = ("lvi_win_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -66,6 +68,7 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
                  os.path.join(HOST_DIR, "lvi_bow_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_bow.h"),
                  os.path.join(HOST_DIR, "lvi_bow_capi_detail.hpp"), os.path.join(HOST_DIR, "lvi_pnp_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pnp.h"),
                  os.path.join(HOST_DIR, "lvi_tbatch_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_tbatch.h"),
+                 os.path.join(HOST_DIR, "lvi_win_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_win.h"),
                  os.path.join(HOST_DIR, "lvi_pgo_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pgo.h"),
                  os.path.join(HOST_DIR, "lvi_marg_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_marg.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
@@ -213,6 +216,20 @@ class HostLibrary:
             d.lvh_marg_set_features.argtypes = [C.c_void_p, C.c_int32, ip, ip, dp, dp]
             d.lvh_marg_set_imu.argtypes = [C.c_void_p, C.c_double, dp, dp]
             d.lvh_marg_run.argtypes = [C.c_void_p, C.c_int32, ip, C.POINTER(MargInfo)]
+        self.has_win = hasattr(d, "lvh_win_create")       # the HIP host library only
+        if self.has_win:
+            from .win import WinImu, WinInfo, WinParams
+            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+            d.lvh_win_last_error.restype = C.c_char_p
+            d.lvh_win_create.restype = C.c_void_p
+            d.lvh_win_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(WinParams)]
+            d.lvh_win_destroy.argtypes = [C.c_void_p]
+            d.lvh_win_handle.restype = C.c_void_p
+            d.lvh_win_handle.argtypes = [C.c_void_p]
+            d.lvh_win_set_imu.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+            d.lvh_win_set_lidar_flags.argtypes = [C.c_void_p, C.c_int32, ip]
+            d.lvh_win_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(WinInfo)]
+            d.lvh_win_get_window.argtypes = [C.c_void_p, dp, dp, dp, dp, C.c_int32, ip, dp]
         self.has_rig = hasattr(d, "lvh_rig_create")      # the HIP host library only
         if self.has_rig:
             d.lvh_rig_last_error.restype = C.c_char_p
@@ -948,6 +965,73 @@ class VinsMarginalizer:
         info, ran = MargInfo(), C.c_int32(0)
         st = self._check(self.hl.dll.lvh_marg_run(self._p, int(flag), C.byref(ran), C.byref(info)), "lvh_marg_run")
         return dict(ran=bool(ran.value), status=st, **{k: getattr(info, k) for k, _ in MargInfo._fields_})
+
+
+class VinsWindowOptimizer:
+    """lvi_host::VinsWindowOptimizer (host/lvi_win_host.hpp): the first half of Estimator::optimization (estimator.cpp:696-811)
+    over include/lvi_win.h, on the window arrays of a VinsMarginalizer and with its resident prior: `optimize(flag)` then
+    `marginalizer.run(flag)` is the tail of Estimator::optimization with no prior on the bus.  HIP host library only."""
+
+    def __init__(self, hostlib, abi_lib, marginalizer, device=0, max_features=150, estimate_extrinsic=0, num_iterations=8, solver_time=0.0, **params):
+        from .win import WinParams, bind as win_bind
+        if not hostlib.has_win:
+            raise RuntimeError("this host library has no window solve (only the one linked against liblvi_hip.so has)")
+        self.hl, self.vm = hostlib, marginalizer
+        p = WinParams()
+        win_bind(abi_lib).dll.lvi_win_params_default(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"lvi_win_params has no field {k}")
+            setattr(p, k, (C.c_double * 3)(*v) if k == "G" else v)
+        self._p = hostlib.dll.lvh_win_create(marginalizer._p, int(device), int(max_features), int(estimate_extrinsic), int(num_iterations), float(solver_time),
+                                             C.byref(p))
+        if not self._p:
+            raise A.LviError(-1, "lvh_win_create", hostlib.dll.lvh_win_last_error().decode(errors="replace"))
+
+    def close(self):
+        if self._p:
+            self.hl.dll.lvh_win_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_win_last_error().decode(errors="replace"))
+        return code
+
+    def set_imu(self, j, record=None):
+        """pre_integrations[j], j = 1..WINDOW_SIZE: a one-element win.IMU_DTYPE array (its ids are ignored), or None for no factor"""
+        from .win import IMU_DTYPE
+        if record is None:
+            return self._check(self.hl.dll.lvh_win_set_imu(self._p, int(j), None), "lvh_win_set_imu")
+        r = np.ascontiguousarray(record, IMU_DTYPE).reshape(1)
+        return self._check(self.hl.dll.lvh_win_set_imu(self._p, int(j), r.ctypes.data_as(C.c_void_p)), "lvh_win_set_imu")
+
+    def set_lidar_flags(self, flags):
+        f = np.ascontiguousarray(flags, np.int32)
+        self._check(self.hl.dll.lvh_win_set_lidar_flags(self._p, len(f), f.ctypes.data_as(C.POINTER(C.c_int32))), "lvh_win_set_lidar_flags")
+
+    def optimize(self, flag):
+        """estimator.cpp:696-811 -> dict(status, iterations, termination, initial_cost, final_cost, ...)"""
+        from .win import WinInfo
+        info = WinInfo()
+        st = self._check(self.hl.dll.lvh_win_optimize(self._p, int(flag), C.byref(info)), "lvh_win_optimize")
+        return dict(status=st, **{k: getattr(info, k) for k, _ in WinInfo._fields_})
+
+    def window(self):
+        """-> dict(pose [11, 7], speed_bias [11, 9], ex_pose [7], td, inv_dep [features]): what double2vector reads"""
+        dp = C.POINTER(C.c_double)
+        n = C.c_int32(0)
+        self._check(self.hl.dll.lvh_win_get_window(self._p, None, None, None, None, 0, C.byref(n), None), "lvh_win_get_window")
+        pose, sb, ex, td, inv = np.zeros((11, 7)), np.zeros((11, 9)), np.zeros(7), C.c_double(0), np.zeros(max(1, n.value))
+        self._check(self.hl.dll.lvh_win_get_window(self._p, pose.ctypes.data_as(dp), sb.ctypes.data_as(dp), ex.ctypes.data_as(dp), C.byref(td), n.value, None,
+                                                   inv.ctypes.data_as(dp)), "lvh_win_get_window")
+        return dict(pose=pose, speed_bias=sb, ex_pose=ex, td=td.value, inv_dep=inv[:n.value])
 
 
 class TrackerRig:
