@@ -1,18 +1,9 @@
 // The marginalisation of vins_estimator's sliding window on the GPU (include/lvi_marg.h; the contract is DESIGN §21):
 // preMarginalize + marginalize of marginalization_factor.cpp:110-129, 174-296 with the factors of estimator.cpp:813-976.
-// All double.  With m dropped and n kept local columns, pos = m + n and P1 = pos + 1, every factor is a set of rows
-// [J | r] over the P1 columns of the augmented system; [J r]'[J r] holds A = sum J'J, b = sum J'r in its last column and
-// the cost in its corner.
+// All double.  With m dropped and n kept local columns, pos = m + n and P1 = pos + 1.  The augmented system A over the P1
+// columns (sum J'J, b = sum J'r in its last column, the cost in its corner) comes from the front end shared with the window
+// solve (lvi_winsys.hip); the prior's rows are written behind the dense rows the host sent.  Then:
 //
-//   marg_eval_proj   one thread per projection factor: residual, Jacobian and loss correction (lvi_marg_math.hpp), 2 rows of 21
-//   marg_prior_rows  one workgroup per row of the previous prior: dx from the blocks' current values (:344-362), the row
-//                    r0 + J dx and J's columns scattered to their new places, written behind the dense rows the host sent
-//   marg_accumulate  one workgroup per 16x16 tile of the augmented system and per chunk of 256 rows (LVI_MARG_SHARE
-//                    projection factors, or 256 dense rows): the rows' values at the tile's columns are staged in LDS 64
-//                    rows at a time and every thread sums its entry over them in row order; the chunk's partial tile is
-//                    written out.  Every factor of MARGIN_OLD shares pose 0, the extrinsic and td: nothing is scattered,
-//                    so nothing serialises on those columns, and there are no floating-point atomics.
-//   marg_reduce      one thread per entry: the partials summed in chunk order; a non-finite entry raises the flag
 //   marg_sym         Amm = (Amm + Amm') / 2 (:266), and the same for the Schur complement
 //   marg_eigh        one workgroup: parallel cyclic two-sided Jacobi over the disjoint pairs of a round-robin schedule
 //   marg_pinv        Amm_inv = V diag(lambda > eps ? 1 / lambda : 0) V' (:271)
@@ -28,25 +19,17 @@
 #include <vector>
 
 #include "lvi_dev.hpp"
-#include "lvi_marg_math.hpp"
 #include "lvi_marg_view.hpp"
-#include "../../include/lvi_marg.h"
+#include "lvi_winsys.hpp"
 
 using namespace lvi;
 using namespace lvi_marg_math;
+using namespace lvi_winsys;
 
 namespace {
 
-constexpr int TILE = 16;                 // the accumulation's tile edge; TILE x TILE threads
-constexpr int CH_ROWS = 2 * LVI_MARG_SHARE;   // rows of one chunk
-constexpr int SUB = 64;                  // rows staged in LDS at a time
 constexpr int EIG_THREADS = 1024;
 constexpr int FIN_THREADS = 256;
-constexpr int VAL = LVI_MARG_MAX_BLOCK_SIZE;
-constexpr int JF = 2 * (PROJ_COLS + 1);  // doubles of one evaluated projection factor
-
-struct ProjDev { int col[5]; int blk[5]; int use_td; int pad; ProjObs o; };
-struct PriorBlk { int size, idx0, blk, newcol; };
 struct DevInfo { int flags, sweeps[2], rank, rank_mm, pad; double off[2], cost; };
 
 struct Dev {
@@ -59,105 +42,11 @@ struct Dev {
     double loss_a, eps; ProjConst pc;
 };
 
-__global__ __launch_bounds__(64) void marg_eval_proj(Dev d)
+// what the shared front end reads of d: no costs, flag bit 2, the corner of A is the cost
+SysView sys_view(const Dev& d)
 {
-    const int f = blockIdx.x * 64 + threadIdx.x;
-    if (f >= d.P) return;
-    const ProjDev p = d.proj[f];
-    double r[2], J[2 * PROJ_COLS];
-    const double td = p.use_td ? d.vals[(size_t)VAL * p.blk[4]] : 0.;
-    projection_eval(d.vals + (size_t)VAL * p.blk[0], d.vals + (size_t)VAL * p.blk[1], d.vals + (size_t)VAL * p.blk[2], d.vals[(size_t)VAL * p.blk[3]], td, p.use_td,
-                    p.o, d.pc, r, J);
-    if (d.loss_type != LOSS_NONE) {
-        double rho[3];
-        loss_rho(d.loss_type, d.loss_a, r[0] * r[0] + r[1] * r[1], rho);
-        loss_correct(2, PROJ_COLS, PROJ_COLS, rho, r, J);
-    }
-    double* o = d.Jf + (size_t)JF * f;
-    for (int a = 0; a < 2; a++) {
-        for (int k = 0; k < PROJ_COLS; k++) o[(PROJ_COLS + 1) * a + k] = J[PROJ_COLS * a + k];
-        o[(PROJ_COLS + 1) * a + PROJ_COLS] = r[a];
-    }
-}
-
-__global__ __launch_bounds__(256) void marg_prior_rows(Dev d)
-{
-    __shared__ double dx[LVI_MARG_MAX_KEEP_DIM];
-    __shared__ int colmap[LVI_MARG_MAX_KEEP_DIM];
-    const int row = blockIdx.x, t = threadIdx.x;
-    for (int b = t; b < d.nkb0; b += 256) {
-        const PriorBlk pb = d.pb[b];
-        double v[VAL];
-        prior_dx(pb.size, d.vals + (size_t)VAL * pb.blk, d.x0 + (size_t)VAL * b, v);
-        const int ls = local_size(pb.size);
-        for (int k = 0; k < ls; k++) { dx[pb.idx0 + k] = v[k]; colmap[pb.idx0 + k] = pb.newcol + k; }
-    }
-    double* out = d.E + (size_t)(d.Rd + row) * d.P1;
-    for (int j = t; j < d.P1; j += 256) out[j] = 0.;
-    __syncthreads();
-    const double* Jr = d.J0 + (size_t)row * d.n0;
-    for (int k = t; k < d.n0; k += 256) out[colmap[k]] = Jr[k];
-    // r0 + J dx: n0 <= 256, one product per thread, summed by a tree whose shape is fixed
-    __shared__ double red[256];
-    red[t] = t < d.n0 ? Jr[t] * dx[t] : 0.;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) out[d.pos] = d.r0[row] + red[0];
-}
-
-// the value of row `row` of chunk c at global column g
-__device__ __forceinline__ double row_value(const Dev& d, int c, int row, int g)
-{
-    if (g >= d.P1) return 0.;
-    if (c < d.Cp) {
-        const int f = c * LVI_MARG_SHARE + (row >> 1), a = row & 1;
-        if (f >= d.P) return 0.;
-        const double* o = d.Jf + (size_t)JF * f + (PROJ_COLS + 1) * a;
-        if (g == d.pos) return o[PROJ_COLS];
-        const int* col = d.proj[f].col;
-#pragma unroll
-        for (int b = 0; b < 5; b++) {
-            const int off = col[b], sz = b < 3 ? 6 : 1, base = b < 3 ? 6 * b : 15 + b;
-            if (off >= 0 && g >= off && g < off + sz) return o[base + g - off];
-        }
-        return 0.;
-    }
-    const int r = (c - d.Cp) * CH_ROWS + row;
-    return r < d.Rd + d.n0 ? d.E[(size_t)r * d.P1 + g] : 0.;
-}
-
-__global__ __launch_bounds__(TILE * TILE) void marg_accumulate(Dev d)
-{
-    __shared__ double xs[SUB][TILE], ys[SUB][TILE];
-    const int tx = threadIdx.x, ty = threadIdx.y, t = ty * TILE + tx, c = blockIdx.z;
-    const int gx0 = blockIdx.x * TILE, gy0 = blockIdx.y * TILE;
-    double acc = 0.;
-    for (int r0 = 0; r0 < CH_ROWS; r0 += SUB) {
-        for (int e = t; e < SUB * TILE; e += TILE * TILE) {
-            const int rr = e / TILE, k = e % TILE;
-            xs[rr][k] = row_value(d, c, r0 + rr, gx0 + k);
-            ys[rr][k] = row_value(d, c, r0 + rr, gy0 + k);
-        }
-        __syncthreads();
-        for (int rr = 0; rr < SUB; rr++) acc += ys[rr][ty] * xs[rr][tx];
-        __syncthreads();
-    }
-    const int i = gy0 + ty, j = gx0 + tx;
-    if (i < d.P1 && j < d.P1) d.part[((size_t)c * d.P1 + i) * d.P1 + j] = acc;
-}
-
-__global__ __launch_bounds__(256) void marg_reduce(Dev d)
-{
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, NN = (size_t)d.P1 * d.P1;
-    if (e >= NN) return;
-    double s = 0.;
-    for (int c = 0; c < d.C; c++) s += d.part[(size_t)c * NN + e];
-    d.A[e] = s;
-    if (!isfinite(s)) atomicOr(&d.info->flags, 2);
-    if (e == NN - 1) d.info->cost = s;
+    return SysView{d.vals, d.proj, d.Jf, d.E, d.part, d.A, d.J0, d.r0, d.x0, d.pb, nullptr, &d.info->flags, 2, &d.info->cost,
+                   d.P, d.Rd, d.Rd + d.n0, d.n0, d.nkb0, d.P1, d.Cp, d.C, 0, d.loss_type, d.loss_a, d.pc};
 }
 
 // W [dim][dim] = (B + B') / 2 of the dim x dim block of B (leading dimension ld) that starts at (o, o)
@@ -376,8 +265,6 @@ struct Block { int id, size; double v[VAL]; int seen, drop; };
 struct Dense { int rows; std::vector<int> blk, drop; std::vector<double> r, J; };      // J: per block row-major [rows][local size]
 struct Prior { bool valid = false; int m = 0, n = 0; std::vector<int> ids, sizes, col; std::vector<double> x0; lvi_marg_info info{}; };
 
-bool finite_all(const double* v, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; }
-
 }  // namespace
 
 struct lvi_marg {
@@ -407,7 +294,7 @@ namespace {
 int Pmax(const lvi_marg* h) { return h->caps.max_drop_dim + h->caps.max_keep_dim + 1; }
 int max_chunks(const lvi_marg* h)
 {
-    return div_up(h->caps.max_projections, LVI_MARG_SHARE) + div_up(h->caps.max_dense_rows + h->caps.max_keep_dim, CH_ROWS) + 1;
+    return div_up(h->caps.max_projections, SHARE) + div_up(h->caps.max_dense_rows + h->caps.max_keep_dim, CH_ROWS) + 1;
 }
 
 template <class A> void carve(A& a, lvi_marg* h)
@@ -568,19 +455,11 @@ int32_t lvi_marg_add_projection(lvi_marg* h, int32_t count, const lvi_marg_proje
     if (!h || (count > 0 && !recs)) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (count < 0) return fail(LVI_ERR_INVALID_ARG, "negative count");
     if ((size_t)count + h->proj.size() > (size_t)h->caps.max_projections) return fail(LVI_ERR_CAPACITY, "more projection factors than max_projections");
-    static const int want[5] = {7, 7, 7, 1, 1};
+    const auto look = [&](int id) { const int b = find(h, id); return BlockRef{b, b < 0 ? 0 : h->blocks[b].size, false}; };
     for (int f = 0; f < count; f++) {
-        const lvi_marg_projection& p = recs[f];
-        const int ids[5] = {p.pose_i, p.pose_j, p.ex, p.feature, p.td};
-        int b[5];
-        for (int k = 0; k < 5; k++) {
-            if (k == 4 && p.td == -1) { b[k] = -1; continue; }
-            b[k] = find(h, ids[k]);
-            if (b[k] < 0) return fail(LVI_ERR_INVALID_ARG, "a projection factor names an id that was not declared");
-            if (h->blocks[b[k]].size != want[k]) return fail(LVI_ERR_INVALID_ARG, "a projection factor's blocks must have sizes 7, 7, 7, 1, 1");
-            for (int j = 0; j < k; j++) if (b[j] == b[k]) return fail(LVI_ERR_INVALID_ARG, "a projection factor names one block twice");
-        }
-        if (!finite_all(p.pts_i, 14)) return fail(LVI_ERR_INVALID_ARG, "a projection record is not finite");
+        const char* why = nullptr;
+        const int32_t st = check_projection(recs[f], look, false, &why);
+        if (st != LVI_OK) return fail(st, why);
     }
     for (int f = 0; f < count; f++) {
         const lvi_marg_projection& p = recs[f];
@@ -683,17 +562,8 @@ int32_t lvi_marg_marginalize(lvi_marg* h, lvi_marg_info* info_out)
         const int P1 = pos + 1, P = (int)h->proj.size(), Rd = h->dense_rows, nxt = 1 - h->cur;
         const Prior& pr = h->prior;
         for (int b = 0; b < nb; b++) std::memcpy(h->h_vals + (size_t)VAL * b, h->blocks[b].v, sizeof(double) * VAL);
-        for (int f = 0; f < P; f++) {
-            const lvi_marg_projection& p = h->proj[f];
-            ProjDev& q = h->h_proj[f];
-            const int ids[5] = {p.pose_i, p.pose_j, p.ex, p.feature, p.td};
-            q.use_td = p.td != -1; q.pad = 0;
-            for (int k = 0; k < 5; k++) {
-                const int b = (k == 4 && !q.use_td) ? -1 : find(h, ids[k]);
-                q.blk[k] = b < 0 ? 0 : b; q.col[k] = b < 0 ? -1 : col[b];
-            }
-            std::memcpy(q.o.pts_i, p.pts_i, sizeof(double) * 14);
-        }
+        const auto fnd = [&](int id) { return find(h, id); };
+        for (int f = 0; f < P; f++) stage_projection(h->proj[f], fnd, col.data(), h->h_proj[f]);
         int row = 0;
         for (const Dense& D : h->dense) {
             size_t at = 0;
@@ -711,10 +581,7 @@ int32_t lvi_marg_marginalize(lvi_marg* h, lvi_marg_info* info_out)
             row += D.rows;
         }
         const int n0 = h->use_prior ? pr.n : 0, nkb0 = h->use_prior ? (int)pr.ids.size() : 0;
-        for (int k = 0; k < nkb0; k++) {
-            const int b = find(h, pr.ids[k]);
-            h->h_pb[k] = PriorBlk{pr.sizes[k], pr.col[k], b, col[b]};
-        }
+        stage_prior_blocks(nkb0, pr.ids.data(), pr.sizes.data(), pr.col.data(), fnd, col.data(), h->h_pb);
         for (size_t k = 0; k < kept.size(); k++) h->h_keepblk[k] = kept[k];
 
         Dev d = h->d;
@@ -722,7 +589,7 @@ int32_t lvi_marg_marginalize(lvi_marg* h, lvi_marg_info* info_out)
         d.J0 = h->d_J[h->cur]; d.r0 = h->d_r[h->cur]; d.x0 = h->d_x[h->cur];
         d.J1 = h->d_J[nxt]; d.r1 = h->d_r[nxt]; d.x1 = h->d_x[nxt];
         d.P = P; d.Rd = Rd; d.n0 = n0; d.nkb0 = nkb0; d.m = m; d.n = n; d.pos = pos; d.P1 = P1;
-        d.Cp = div_up(P, LVI_MARG_SHARE); d.C = d.Cp + div_up(Rd + n0, CH_ROWS); d.nkeep = (int)kept.size();
+        d.Cp = div_up(P, SHARE); d.C = d.Cp + div_up(Rd + n0, CH_ROWS); d.nkeep = (int)kept.size();
         d.loss_type = h->P.loss_type; d.max_sweeps = h->P.max_sweeps; d.loss_a = h->P.loss_a; d.eps = h->P.eps;
         d.pc = ProjConst{h->P.sqrt_info, h->P.tr_over_row, h->P.half_row};
 
@@ -732,11 +599,10 @@ int32_t lvi_marg_marginalize(lvi_marg* h, lvi_marg_info* info_out)
         if (nkb0 > 0) LVI_HIP(hipMemcpyAsync(h->d_pb, h->h_pb, sizeof(PriorBlk) * nkb0, hipMemcpyHostToDevice, s));
         LVI_HIP(hipMemcpyAsync(h->d_keepblk, h->h_keepblk, sizeof(int) * kept.size(), hipMemcpyHostToDevice, s));
         LVI_HIP(hipMemsetAsync(d.info, 0, sizeof(DevInfo), s));
-        if (P > 0) hipLaunchKernelGGL(marg_eval_proj, dim3(div_up(P, 64)), dim3(64), 0, s, d);
-        if (n0 > 0) hipLaunchKernelGGL(marg_prior_rows, dim3(n0), dim3(256), 0, s, d);
-        const int Tn = div_up(P1, TILE);
-        hipLaunchKernelGGL(marg_accumulate, dim3(Tn, Tn, d.C), dim3(TILE, TILE), 0, s, d);
-        hipLaunchKernelGGL(marg_reduce, dim3(div_up(P1 * P1, 256)), dim3(256), 0, s, d);
+        const SysView v = sys_view(d);
+        launch_eval_proj(v, s, 1);
+        launch_prior_rows(v, s, 1);
+        launch_build(v, s);
         hipLaunchKernelGGL(marg_sym, dim3(div_up(m * m, 256)), dim3(256), 0, s, d, (const double*)d.A, P1, 0, d.Wm, m);
         hipLaunchKernelGGL(marg_eigh, dim3(1), dim3(EIG_THREADS), 0, s, d, d.Wm, d.Vm, m, 0);
         hipLaunchKernelGGL(marg_pinv, dim3(div_up(m * m, 256)), dim3(256), 0, s, d);

@@ -2,15 +2,13 @@
 // estimator.cpp:696-789 and a trust-region loop with a traditional dogleg step over a dense Schur system, as
 // tests/win_ref.py states it.  All double.  With D columns of the reduced (camera-side) system, P1 = D + 1 and E eliminated
 // scalar blocks, the camera side of every factor is a set of rows [J | r] over P1 columns; sc, sf are the Jacobi scales of
-// the columns and of the eliminated blocks, dg the trust region's diagonal.
+// the columns and of the eliminated blocks, dg the trust region's diagonal.  The projection factors, the prior's rows and
+// Hcc = sum Jc'Jc, g = sum Jc'r come from the front end shared with the marginaliser (lvi_winsys.hip), with
+// the per-factor costs on.  Beside and after it:
 //
 //   win_imu_info     one workgroup per IMU factor, once per solve: sqrt_info = LLT(covariance^-1).matrixL()'
-//   win_eval_proj    one thread per projection factor: residual, Jacobian, loss correction, cost 0.5 rho(s)
 //   win_eval_imu     one workgroup per IMU factor: residual and Jacobians, multiplied by sqrt_info, 15 rows of P1
-//   win_eval_prior   one workgroup per row of the prior: dx, r0 + J dx and J's columns at the window's places
 //   win_feat         one workgroup per eliminated block: its factors in order, w = sum Jc' jf, h = sum jf^2, gf = sum jf r
-//   win_accumulate   one workgroup per 16x16 tile and chunk of 256 rows, as marg_accumulate: Hcc = sum Jc'Jc, g = sum Jc'r
-//   win_reduce       the partials summed in chunk order; a non-finite entry raises the flag
 //   win_grad         one workgroup: the cost, (first) the Jacobi scales, the diagonal, the gradient, its norms, the Cauchy alpha
 //   win_schur        one workgroup per 16x16 tile: S = sc Hcc sc + mu dg^2 - sum_k ws_k ws_k' / (hs_k + mu dg_k^2) and its
 //                    right-hand side, the eliminated blocks gathered in index order
@@ -30,29 +28,22 @@
 
 #include "lvi_dev.hpp"
 #include "lvi_imu_math.hpp"
-#include "lvi_marg_math.hpp"
 #include "lvi_marg_view.hpp"
-#include "../../include/lvi_win.h"
+#include "lvi_winsys.hpp"
 
 using namespace lvi;
 using namespace lvi_marg_math;
+using namespace lvi_winsys;
 using namespace lvi_imu_math;
 
 namespace {
 
-constexpr int TILE = 16;
-constexpr int CH_ROWS = 2 * LVI_WIN_SHARE;
-constexpr int SUB = 64;
 constexpr int ONE = 1024;                // threads of the one-workgroup kernels
 constexpr int NB = LVI_WIN_CHOL_BLOCK;
-constexpr int VAL = LVI_WIN_MAX_BLOCK_SIZE;
-constexpr int JF = 2 * (PROJ_COLS + 1);
 constexpr int MAXD = LVI_WIN_MAX_DIM;
 constexpr int F_SYSTEM = 1, F_CHOL = 2, F_STEP = 4, F_COV = 8;
 
-struct ProjDev { int col[5]; int blk[5]; int elim; int use_td; ProjObs o; };
 struct ImuDev { int blk[4]; int col[4]; ImuPre p; double cov[225]; };
-struct PriorBlk { int size, idx0, blk, newcol; };
 struct BlkDev { int size, col, elim, pad; };
 struct GradInfo { int flags, pad; double cost, grad_max, grad_norm, alpha, x_norm; };
 struct StepInfo { int flags, kind; double gn_norm, cauchy_norm, dogleg_norm, model_cost_change, step_norm, cand_cost; };
@@ -103,26 +94,6 @@ __global__ __launch_bounds__(64) void win_imu_info(Dev d)
     if (!imu_sqrt_info(d.imu[i].cov, d.Sinfo + 225 * (size_t)i, d.imu_work + 675 * (size_t)i)) atomicOr(&d.gi->flags, F_SYSTEM | F_COV);
 }
 
-__global__ __launch_bounds__(64) void win_eval_proj(Dev d, int cand)
-{
-    const int f = blockIdx.x * 64 + threadIdx.x;
-    if (f >= d.P) return;
-    const double* v = cand ? d.xc : d.x;
-    const ProjDev p = d.proj[f];
-    double r[2], J[2 * PROJ_COLS], rho[3];
-    const double td = p.use_td ? v[(size_t)VAL * p.blk[4]] : 0.;
-    projection_eval(v + (size_t)VAL * p.blk[0], v + (size_t)VAL * p.blk[1], v + (size_t)VAL * p.blk[2], v[(size_t)VAL * p.blk[3]], td, p.use_td, p.o, d.pc, r, J);
-    loss_rho(d.loss_type, d.loss_a, r[0] * r[0] + r[1] * r[1], rho);
-    d.fc[f] = 0.5 * rho[0];
-    if (cand) return;
-    if (d.loss_type != LOSS_NONE) loss_correct(2, PROJ_COLS, PROJ_COLS, rho, r, J);
-    double* o = d.Jf + (size_t)JF * f;
-    for (int a = 0; a < 2; a++) {
-        for (int k = 0; k < PROJ_COLS; k++) o[(PROJ_COLS + 1) * a + k] = J[PROJ_COLS * a + k];
-        o[(PROJ_COLS + 1) * a + PROJ_COLS] = r[a];
-    }
-}
-
 __global__ __launch_bounds__(64) void win_eval_imu(Dev d, int cand)
 {
     __shared__ double r[IMU_ROWS], J[IMU_ROWS * IMU_COLS], rs[IMU_ROWS];
@@ -151,40 +122,6 @@ __global__ __launch_bounds__(64) void win_eval_imu(Dev d, int cand)
         double s = 0.;
         for (int k = 0; k < IMU_ROWS; k++) s += rs[k] * rs[k];
         d.fc[d.P + i] = 0.5 * s;
-    }
-}
-
-__global__ __launch_bounds__(256) void win_eval_prior(Dev d, int cand)
-{
-    __shared__ double dx[LVI_WIN_MAX_PRIOR_ROWS], red[256];
-    __shared__ int colmap[LVI_WIN_MAX_PRIOR_ROWS];
-    const int row = blockIdx.x, t = threadIdx.x;
-    const double* v = cand ? d.xc : d.x;
-    for (int b = t; b < d.nkb0; b += 256) {
-        const PriorBlk pb = d.pb[b];
-        double w[VAL];
-        prior_dx(pb.size, v + (size_t)VAL * pb.blk, d.x0 + (size_t)VAL * b, w);
-        const int ls = local_size(pb.size);
-        for (int k = 0; k < ls; k++) { dx[pb.idx0 + k] = w[k]; colmap[pb.idx0 + k] = pb.newcol < 0 ? -1 : pb.newcol + k; }
-    }
-    double* out = d.E + (size_t)(IMU_ROWS * d.I + row) * d.P1;
-    if (!cand)
-        for (int j = t; j < d.P1; j += 256) out[j] = 0.;
-    __syncthreads();
-    const double* Jr = d.J0 + (size_t)row * d.n0;
-    if (!cand)
-        for (int k = t; k < d.n0; k += 256)
-            if (colmap[k] >= 0) out[colmap[k]] = Jr[k];
-    red[t] = t < d.n0 ? Jr[t] * dx[t] : 0.;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) {
-        const double rr = d.r0[row] + red[0];
-        if (!cand) out[d.D] = rr;
-        d.fc[d.P + d.I + row] = 0.5 * (rr * rr);
     }
 }
 
@@ -219,56 +156,6 @@ __global__ __launch_bounds__(64) void win_feat(Dev d)
     __syncthreads();
     for (int j = t; j < d.P1; j += 64) d.W[(size_t)k * d.P1 + j] = acc[j];
     if (t == 0) d.h[k] = hh;
-}
-
-__device__ __forceinline__ double row_value(const Dev& d, int c, int row, int g)
-{
-    if (g >= d.P1) return 0.;
-    if (c < d.Cp) {
-        const int f = c * LVI_WIN_SHARE + (row >> 1), a = row & 1;
-        if (f >= d.P) return 0.;
-        const double* o = d.Jf + (size_t)JF * f + (PROJ_COLS + 1) * a;
-        if (g == d.D) return o[PROJ_COLS];
-        const int* col = d.proj[f].col;
-#pragma unroll
-        for (int b = 0; b < 5; b++) {
-            const int off = col[b], sz = b < 3 ? 6 : 1, base = b < 3 ? 6 * b : 15 + b;
-            if (off >= 0 && g >= off && g < off + sz) return o[base + g - off];
-        }
-        return 0.;
-    }
-    const int r = (c - d.Cp) * CH_ROWS + row;
-    return r < d.Rd ? d.E[(size_t)r * d.P1 + g] : 0.;
-}
-
-__global__ __launch_bounds__(TILE * TILE) void win_accumulate(Dev d)
-{
-    __shared__ double xs[SUB][TILE], ys[SUB][TILE];
-    const int tx = threadIdx.x, ty = threadIdx.y, t = ty * TILE + tx, c = blockIdx.z;
-    const int gx0 = blockIdx.x * TILE, gy0 = blockIdx.y * TILE;
-    double acc = 0.;
-    for (int r0 = 0; r0 < CH_ROWS; r0 += SUB) {
-        for (int e = t; e < SUB * TILE; e += TILE * TILE) {
-            const int rr = e / TILE, k = e % TILE;
-            xs[rr][k] = row_value(d, c, r0 + rr, gx0 + k);
-            ys[rr][k] = row_value(d, c, r0 + rr, gy0 + k);
-        }
-        __syncthreads();
-        for (int rr = 0; rr < SUB; rr++) acc += ys[rr][ty] * xs[rr][tx];
-        __syncthreads();
-    }
-    const int i = gy0 + ty, j = gx0 + tx;
-    if (i < d.P1 && j < d.P1) d.part[((size_t)c * d.P1 + i) * d.P1 + j] = acc;
-}
-
-__global__ __launch_bounds__(256) void win_reduce(Dev d)
-{
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, NN = (size_t)d.P1 * d.P1;
-    if (e >= NN) return;
-    double s = 0.;
-    for (int c = 0; c < d.C; c++) s += d.part[(size_t)c * NN + e];
-    d.A[e] = s;
-    if (!isfinite(s)) atomicOr(&d.gi->flags, F_SYSTEM);
 }
 
 // u' H u over the whole system: uc [D] in LDS, uf [E] in global memory; H = [Hcc W'; W diag(h)]
@@ -543,8 +430,6 @@ struct HostPrior {
     const double *dJ = nullptr, *dr = nullptr, *dx0 = nullptr;       // the resident route
 };
 
-bool finite_all(const double* v, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; }
-
 }  // namespace
 
 struct lvi_win {
@@ -572,7 +457,7 @@ namespace {
 
 int P1max(const lvi_win* h) { return h->caps.max_dim + 1; }
 int dense_rows_max(const lvi_win* h) { return IMU_ROWS * h->caps.max_imu + h->caps.max_prior_rows; }
-int max_chunks(const lvi_win* h) { return div_up(h->caps.max_projections, LVI_WIN_SHARE) + div_up(dense_rows_max(h), CH_ROWS) + 1; }
+int max_chunks(const lvi_win* h) { return div_up(h->caps.max_projections, SHARE) + div_up(dense_rows_max(h), CH_ROWS) + 1; }
 
 template <class A> void carve(A& a, lvi_win* h)
 {
@@ -651,17 +536,11 @@ int32_t upload(lvi_win* h, Dev& d)
         h->h_blk[b] = BlkDev{h->blocks[b].size, col[b], elim[b], 0};
     }
     std::vector<std::vector<int>> of(Ne);
+    const auto fnd = [&](int id) { return find(h, id); };
     for (int f = 0; f < P; f++) {
-        const lvi_marg_projection& p = h->proj[f];
-        ProjDev& q = h->h_proj[f];
-        const int ids[5] = {p.pose_i, p.pose_j, p.ex, p.feature, p.td};
-        q.use_td = p.td != -1; q.elim = -1;
-        for (int k = 0; k < 5; k++) {
-            const int b = (k == 4 && !q.use_td) ? -1 : find(h, ids[k]);
-            q.blk[k] = b < 0 ? 0 : b; q.col[k] = b < 0 ? -1 : col[b];
-            if (k == 3 && elim[b] >= 0) { q.elim = elim[b]; of[elim[b]].push_back(f); }
-        }
-        std::memcpy(q.o.pts_i, p.pts_i, sizeof(double) * 14);
+        stage_projection(h->proj[f], fnd, col.data(), h->h_proj[f]);
+        const int e = elim[h->h_proj[f].blk[3]];
+        if (e >= 0) of[e].push_back(f);
     }
     int at = 0;
     for (int k = 0; k < Ne; k++) {
@@ -681,14 +560,11 @@ int32_t upload(lvi_win* h, Dev& d)
         std::memcpy(q.cov, r.covariance, sizeof(double) * 225);
     }
     const int n0 = pr.valid ? pr.n : 0, nkb0 = pr.valid ? (int)pr.ids.size() : 0;
-    for (int k = 0; k < nkb0; k++) {
-        const int b = find(h, pr.ids[k]);
-        h->h_pb[k] = PriorBlk{pr.sizes[k], pr.col[k], b, col[b]};
-    }
+    stage_prior_blocks(nkb0, pr.ids.data(), pr.sizes.data(), pr.col.data(), fnd, col.data(), h->h_pb);
     d = h->d;
     d.proj = h->d_proj; d.imu = h->d_imu; d.pb = h->d_pb; d.blk = h->d_blk; d.feat_ptr = h->d_fptr; d.feat_fac = h->d_ffac;
     d.P = P; d.I = I; d.n0 = n0; d.nkb0 = nkb0; d.nb = nb; d.D = D; d.P1 = D + 1; d.Ne = Ne; d.Rd = IMU_ROWS * I + n0;
-    d.Cp = div_up(P, LVI_WIN_SHARE); d.C = d.Cp + div_up(d.Rd, CH_ROWS);
+    d.Cp = div_up(P, SHARE); d.C = d.Cp + div_up(d.Rd, CH_ROWS);
     d.loss_type = h->P.loss_type; d.jacobi = h->P.jacobi_scaling; d.loss_a = h->P.loss_a;
     for (int k = 0; k < 3; k++) d.G[k] = h->P.G[k];
     d.min_diag = h->P.min_diagonal; d.max_diag = h->P.max_diagonal;
@@ -716,11 +592,20 @@ int32_t upload(lvi_win* h, Dev& d)
     return LVI_OK;
 }
 
+// what the shared front end reads of d at the blocks' values vals: the costs in fc, flag bit F_SYSTEM, no corner
+SysView sys_view(const Dev& d, const double* vals)
+{
+    return SysView{vals, d.proj, d.Jf, d.E, d.part, d.A, d.J0, d.r0, d.x0, d.pb, d.fc, &d.gi->flags, F_SYSTEM, nullptr,
+                   d.P, IMU_ROWS * d.I, d.Rd, d.n0, d.nkb0, d.P1, d.Cp, d.C, d.P + d.I, d.loss_type, d.loss_a, d.pc};
+}
+
+// every factor at d.x, or at the candidate d.xc for the costs alone
 void launch_eval(const Dev& d, hipStream_t s, int cand)
 {
-    if (d.P > 0) hipLaunchKernelGGL(win_eval_proj, dim3(div_up(d.P, 64)), dim3(64), 0, s, d, cand);
+    const SysView v = sys_view(d, cand ? d.xc : d.x);
+    launch_eval_proj(v, s, !cand);
     if (d.I > 0) hipLaunchKernelGGL(win_eval_imu, dim3(d.I), dim3(64), 0, s, d, cand);
-    if (d.n0 > 0) hipLaunchKernelGGL(win_eval_prior, dim3(d.n0), dim3(256), 0, s, d, cand);
+    launch_prior_rows(v, s, !cand);
 }
 
 // factors, system, gradient at d.x -> *h->h_gi
@@ -729,9 +614,7 @@ void prepare(lvi_win* h, const Dev& d, int first)
     hipStream_t s = h->stream;
     launch_eval(d, s, 0);
     if (d.Ne > 0) hipLaunchKernelGGL(win_feat, dim3(d.Ne), dim3(64), 0, s, d);
-    const int Tn = div_up(d.P1, TILE);
-    hipLaunchKernelGGL(win_accumulate, dim3(Tn, Tn, d.C), dim3(TILE, TILE), 0, s, d);
-    hipLaunchKernelGGL(win_reduce, dim3(div_up(d.P1 * d.P1, 256)), dim3(256), 0, s, d);
+    launch_build(sys_view(d, d.x), s);
     hipLaunchKernelGGL(win_grad, dim3(1), dim3(ONE), 0, s, d, first);
     LVI_HIP(hipGetLastError());
     LVI_HIP(hipMemcpyAsync(h->h_gi, d.gi, sizeof(GradInfo), hipMemcpyDeviceToHost, s));
@@ -872,20 +755,14 @@ int32_t lvi_win_add_projection(lvi_win* h, int32_t count, const lvi_marg_project
     if (!h || (count > 0 && !recs)) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (count < 0) return fail(LVI_ERR_INVALID_ARG, "negative count");
     if ((size_t)count + h->proj.size() > (size_t)h->caps.max_projections) return fail(LVI_ERR_CAPACITY, "more projection factors than max_projections");
-    static const int want[5] = {7, 7, 7, 1, 1};
+    const auto look = [&](int id) {
+        const int b = find(h, id);
+        return b < 0 ? BlockRef{-1, 0, false} : BlockRef{b, h->blocks[b].size, (h->blocks[b].flags & LVI_WIN_ELIMINATED) != 0};
+    };
     for (int f = 0; f < count; f++) {
-        const lvi_marg_projection& p = recs[f];
-        const int ids[5] = {p.pose_i, p.pose_j, p.ex, p.feature, p.td};
-        int b[5];
-        for (int k = 0; k < 5; k++) {
-            if (k == 4 && p.td == -1) { b[k] = -1; continue; }
-            b[k] = find(h, ids[k]);
-            if (b[k] < 0) return fail(LVI_ERR_INVALID_ARG, "a projection factor names an id that was not declared");
-            if (h->blocks[b[k]].size != want[k]) return fail(LVI_ERR_INVALID_ARG, "a projection factor's blocks must have sizes 7, 7, 7, 1, 1");
-            if (k != 3 && (h->blocks[b[k]].flags & LVI_WIN_ELIMINATED)) return fail(LVI_ERR_INVALID_ARG, "an eliminated block outside the feature slot");
-            for (int j = 0; j < k; j++) if (b[j] == b[k]) return fail(LVI_ERR_INVALID_ARG, "a projection factor names one block twice");
-        }
-        if (!finite_all(p.pts_i, 14)) return fail(LVI_ERR_INVALID_ARG, "a projection record is not finite");
+        const char* why = nullptr;
+        const int32_t st = check_projection(recs[f], look, true, &why);
+        if (st != LVI_OK) return fail(st, why);
     }
     h->proj.insert(h->proj.end(), recs, recs + count);
     return LVI_OK;

@@ -415,6 +415,37 @@ def test_prior_routes_give_the_same_bits(pkg, hip, win):
         win2.close()
 
 
+# ---- the front end the two handles share --------------------------------------------------------------------
+def test_marginaliser_and_window_solve_build_the_same_matrix(pkg, hip, win):
+    """One factor set (S.shared_front_scene: 129 projection factors with td and CauchyLoss, one chunk boundary) given to a
+    Marginalizer that drops pose 0 and the features, and to a WindowSolver with every block free: A, b and H, g are the same
+    sums over the same rows in the same chunk order, so they are the same bits up to the column permutation
+    between the two layouts.  The costs are other quantities (sum r'r of the corrected residuals, sum rho / 2)."""
+    from test_gpu_marg import Device as MargDevice
+    blocks, recs = S.shared_front_scene()
+    perm = S.shared_front_permutation(blocks, recs)
+    marg = pkg.Marginalizer(hip, max_blocks=160, max_projections=160, max_dense_factors=1, max_dense_rows=1, max_drop_dim=144, max_keep_dim=32)
+    try:
+        marg.set_params(loss_type=M.LOSS_CAUCHY, loss_a=1.0, sqrt_info=M.SQRT_INFO, tr_over_row=0.0, half_row=240.0, eps=M.EPS, max_sweeps=30)
+        md, wd = MargDevice(marg), Device(win)
+        for b, v in blocks:
+            md.set_block(b, v)
+            wd.set_block(b, v, 0)
+        for rec in recs:
+            md.add_projection(rec)
+            wd.add_projection(rec)
+        info = md.marginalize()
+        A, b = marg.debug_system()
+    finally:
+        marg.close()
+    dev = wd.flush().w.debug_system()
+    assert info["status"] != pkg.marg.NOT_FINITE and (info["m"], info["n"]) == (135, 19) and dev["status"] == 0 and dev["H"].shape == (154, 154)
+    Ap, bp = A[np.ix_(perm, perm)], b[perm]
+    print(f"[win gpu] shared front end: {len(recs)} factors, m {info['m']} n {info['n']} D {len(bp)}; entries of A that differ from H {int((Ap != dev['H']).sum())}, "
+          f"of b from g {int((bp != dev['g']).sum())}; ||A|| {np.linalg.norm(A, 2):.3e}")
+    assert np.array_equal(Ap, dev["H"]) and np.array_equal(bp, dev["g"])
+
+
 # ---- other cases -----------------------------------------------------------------------------------------------
 def test_second_run_gives_the_same_bits(win):
     runs = []

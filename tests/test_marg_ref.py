@@ -1,6 +1,7 @@
 """CPU tier of the sliding-window marginalisation (include/lvi_marg.h): the ABI / host-library link checks, the
 reference tests/marg_ref.py against central differences, csrc/lvi_marg_math.hpp compiled alone (plain and under the host
-sanitizers) against the reference, and the conditions of the GPU tier's scenes."""
+sanitizers) against the reference, the host helpers of csrc/lvi_winsys.hpp in the same driver, and the conditions of the GPU
+tier's scenes."""
 import ctypes
 import os
 import re
@@ -248,17 +249,75 @@ def test_chain_reference():
 
 # ---- csrc/lvi_marg_math.hpp alone, under the host sanitizers ------------------------------------------------
 DRIVER = r"""
-// stand-alone driver of csrc/lvi_marg_math.hpp: the factor pieces the kernels call, run on the host
+// stand-alone driver of csrc/lvi_marg_math.hpp and of the host helpers of csrc/lvi_winsys.hpp: the factor pieces the kernels
+// call and the record checks and staging both handles call, run on the host
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include "lvi_marg_math.hpp"
+#include "lvi_winsys.hpp"
 using namespace lvi_marg_math;
+using namespace lvi_winsys;
 
 static void put(const double* v, int n) { for (int i = 0; i < n; i++) std::printf(" %a", v[i]); }
 
+// csrc/lvi_winsys.hpp's host helpers: one valid record and one of each refused kind -> 0, or the number of the case that went wrong
+static int check_records()
+{
+    // ids 0, 1: poses, 2: extrinsic, 3: feature, 4: td, 5: an eliminated feature, 6: a speed-bias; block index = id + 10
+    const std::map<int, BlockRef> table = {{0, {10, 7, false}}, {1, {11, 7, false}}, {2, {12, 7, false}}, {3, {13, 1, false}}, {4, {14, 1, false}},
+                                           {5, {15, 1, true}}, {6, {16, 9, false}}};
+    const auto look = [&](int id) { const auto it = table.find(id); return it == table.end() ? BlockRef{-1, 0, false} : it->second; };
+    const auto find = [&](int id) { return look(id).index; };
+    lvi_marg_projection ok;
+    std::memset(&ok, 0, sizeof(ok));
+    ok.pose_i = 0; ok.pose_j = 1; ok.ex = 2; ok.feature = 3; ok.td = 4;
+    double obs[14];                                          // pts_i .. row_j are 14 doubles in a row
+    for (int k = 0; k < 14; k++) obs[k] = 0.25 * k;
+    std::memcpy(reinterpret_cast<char*>(&ok) + offsetof(lvi_marg_projection, pts_i), obs, sizeof(obs));
+    const char* why = nullptr;
+    const auto refused = [&](const lvi_marg_projection& p, bool rule, const char* msg) {
+        why = nullptr;
+        return check_projection(p, look, rule, &why) == LVI_ERR_INVALID_ARG && why && !std::strcmp(why, msg);
+    };
+    lvi_marg_projection p = ok;
+    if (check_projection(p, look, true, &why) != LVI_OK) return 1;
+    p.td = -1;
+    if (check_projection(p, look, true, &why) != LVI_OK) return 2;
+    p = ok; p.ex = 9;
+    if (!refused(p, true, "a projection factor names an id that was not declared")) return 3;
+    p = ok; p.pose_j = 6;
+    if (!refused(p, true, "a projection factor's blocks must have sizes 7, 7, 7, 1, 1")) return 4;
+    p = ok; p.td = 5;
+    if (!refused(p, true, "an eliminated block outside the feature slot")) return 5;
+    if (check_projection(p, look, false, &why) != LVI_OK) return 6;         // the marginaliser has no such rule
+    p = ok; p.feature = 5;
+    if (check_projection(p, look, true, &why) != LVI_OK) return 7;
+    p = ok; p.pose_j = 0;
+    if (!refused(p, true, "a projection factor names one block twice")) return 8;
+    p = ok; p.row_j = INFINITY;
+    if (!refused(p, true, "a projection record is not finite")) return 9;
+    int col[17];
+    for (int k = 0; k < 17; k++) col[k] = k == 12 ? -1 : 100 * k;           // the extrinsic is constant
+    ProjDev q;
+    stage_projection(ok, find, col, q);
+    const int blk[5] = {10, 11, 12, 13, 14}, cols[5] = {1000, 1100, -1, 1300, 1400};
+    if (std::memcmp(q.blk, blk, sizeof(blk)) || std::memcmp(q.col, cols, sizeof(cols)) || !q.use_td || std::memcmp(q.o.pts_i, ok.pts_i, 14 * sizeof(double))) return 10;
+    p = ok; p.td = -1;
+    stage_projection(p, find, col, q);
+    if (q.use_td || q.blk[4] != 0 || q.col[4] != -1 || q.blk[3] != 13) return 11;
+    const int ids[2] = {1, 6}, sizes[2] = {7, 9}, idx0[2] = {9, 0};
+    PriorBlk pb[2];
+    stage_prior_blocks(2, ids, sizes, idx0, find, col, pb);
+    if (pb[0].size != 7 || pb[0].idx0 != 9 || pb[0].blk != 11 || pb[0].newcol != 1100 || pb[1].size != 9 || pb[1].idx0 != 0 || pb[1].blk != 16 || pb[1].newcol != 1600) return 12;
+    const double v[3] = {1., NAN, 2.};
+    return finite_all(v, 1) && !finite_all(v, 3) && finite_all(v + 2, 1) ? 0 : 13;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 2 && !std::strcmp(argv[1], "check")) return check_records();
     if (argc < 3) return 1;
     FILE* f = std::fopen(argv[2], "rb");
     if (!f) return 2;
@@ -402,3 +461,11 @@ def test_math_header_loss_branches_prior_dx_and_rotation(drivers, tmp_path, whic
     got = _run(drivers[which], "rot", tmp_path / "r.bin")
     for g, (app, aqq, apq) in zip(got, cases):
         assert abs(g[0] ** 2 + g[1] ** 2 - 1) < 1e-15 and abs(g[2]) <= 4e-16 * max(abs(app), abs(aqq), abs(apq)) and abs(g[1]) <= g[0]
+
+
+@pytest.mark.parametrize("which", ["plain", "san"])
+def test_shared_host_helpers_check_and_stage_records(drivers, which):
+    """csrc/lvi_winsys.hpp needs no HIP on its host side: the driver feeds its record check one valid record and one of every
+    refused kind (with and without the window solve's eliminated-slot rule), and its staging a record and a prior's blocks"""
+    r = subprocess.run([drivers[which], "check"], capture_output=True, text=True)
+    assert r.returncode == 0, f"case {r.returncode}: " + r.stdout + r.stderr

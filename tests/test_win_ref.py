@@ -304,6 +304,27 @@ def test_scene_shapes():
     assert len(S.problem("skipped_imu", R.F64).imu) == 1 and S.problem("no_prior", R.F64).prior is None
 
 
+def test_shared_front_scene_is_one_system_in_both_references():
+    """the scene of tests/test_gpu_win.py's comparison of the two handles: both references take it, its shapes are the ones
+    meant, and the permutation worked out from the two layout rules carries the marginaliser's A, b onto the window's H, g.
+    Both references add the factors' blocks up in factor order, so the float64 sums are the same numbers."""
+    blocks, recs = S.shared_front_scene()
+    perm = S.shared_front_permutation(blocks, recs)
+    mg, pr = M.Marg(M.F64), R.Problem(R.F64)
+    for b, v in blocks:
+        mg.set_block(b, v)
+        pr.set_block(b, v, 0)
+    for rec in recs:
+        mg.add_projection(rec)
+        pr.add_projection(rec)
+    A, b, m, n = mg.system()
+    sys = pr.system(pr.x0())
+    assert len(recs) == R.SHARE + 1 == M.SHARE + 1 and (m, n) == (135, 19) and (sys["D"], sys["E"]) == (154, 0)
+    assert sorted(perm) == list(range(154)) and list(perm[:6]) == list(range(6)) and perm[6] == 135 and perm[18 + 6 + 1] == 6
+    assert np.array_equal(M.to_f64(A)[np.ix_(perm, perm)], M.to_f64(sys["H"])) and np.array_equal(M.to_f64(b)[perm], M.to_f64(sys["g"]))
+    assert mg.marginalize()["rank"] > 0
+
+
 def test_the_three_radii_give_the_three_step_kinds():
     kinds = [R.solve(S.problem("two_frames", R.F64, initial_radius=rad, max_iterations=1))["log"][1]["step_kind"] for rad in S.STEP_RADII]
     assert kinds == [R.STEP_GAUSS_NEWTON, R.STEP_INTERPOLATED, R.STEP_CAUCHY]

@@ -145,6 +145,40 @@ def scene(name):
     raise KeyError(name)
 
 
+def shared_front_scene():
+    """-> (blocks [(id, values)] in the order they are declared, projection records): the factor set the marginaliser and the
+    window solve build one matrix from.  Three poses, the extrinsic, td and SHARE + 1 features with one
+    projection factor with td each, from pose 0 to pose 1 or 2 in turn: 129 factors, one chunk boundary, D = 154."""
+    win, feats = M.make_window(15, R.SHARE + 1, frames_seen=[3])
+    blocks = [(ID_POSE + k, win["pose"][k]) for k in range(3)] + [(ID_EX, win["ex"]), (ID_TD, [win["td"]])]
+    recs = []
+    for k, f in enumerate(feats):
+        blocks.append((ID_FEATURE + k, [f["inv_dep"]]))
+        j = 1 + k % 2
+        recs.append(M._rec(ID_POSE, ID_POSE + j, ID_FEATURE + k, f["obs"][0], f["obs"][j]))
+    return blocks, recs
+
+
+def shared_front_permutation(blocks, recs):
+    """perm[c]: the marginaliser's column of the window solve's column c, when every pose_i and feature is dropped and the
+    window solve has every block free.  The marginaliser orders the dropped blocks by first appearance in a drop set, then
+    the kept blocks by first appearance (include/lvi_marg.h); the window solve keeps the order of declaration
+    (include/lvi_win.h)."""
+    size = {b: M.local_size(len(v)) for b, v in blocks}
+    seen, dropped = [], []
+    for r in recs:
+        for key in ("pose_i", "pose_j", "ex", "feature", "td"):
+            if r[key] not in seen:
+                seen.append(r[key])
+            if key in ("pose_i", "feature") and r[key] not in dropped:
+                dropped.append(r[key])
+    col, pos = {}, 0
+    for b in dropped + [b for b in seen if b not in dropped]:
+        col[b] = pos
+        pos += size[b]
+    return np.array([col[b] + k for b, _ in blocks for k in range(size[b])])
+
+
 SYSTEM_SCENES = ["two_frames", "three_td", "three_plain", "all_constant", "half_constant", "eleven_frames", "skipped_imu", "no_prior", "share", "share_plus_1",
                  "two_shares_plus_1", "chol_32", "chol_33", "chol_64", "chol_65"]
 F64_ONLY = ("eleven_frames", "share", "share_plus_1", "two_shares_plus_1", "chol_64", "chol_65")     # too slow in mpmath: compared with float64 at the floor alone
