@@ -42,54 +42,13 @@ struct GridArgs {
 };
 
 // d_status[1] is the status word of the map build: every build rewrites it (the scan-side word d_status[0] is cleared by
-// the scan upload, which may come before or after the build on the stream)
-__device__ int grid_meta_one(const GridArgs& a, int w, GridIndex::Meta& m)
-{
-    const int n = a.nout[w];
-    m.n = n; m.ok = 0; m.R = 1; m.edge = 0.5; m.inv_edge = 2.0;
-    m.dim[0] = m.dim[1] = m.dim[2] = 1; m.ncells = 1; m.origin[0] = m.origin[1] = m.origin[2] = 0.0;
-    if (n <= 0 || a.vox[w].n_valid == 0) return 0;
-    double lo[3], ext[3];
-    for (int d = 0; d < 3; d++) {
-        const double mn = floor((double)ord2f(a.vox[w].bb[d])), mx = floor((double)ord2f(a.vox[w].bb[3 + d]));
-        lo[d] = mn - 1.0;                       // one cell of padding on every side
-        ext[d] = mx - mn + 3.0;
-    }
-    int c = 1;                                  // cell edge in half metres, integer >= 1
-    for (;; c++) {
-        const double e = 0.5 * c;
-        const double nx = ceil(ext[0] / e), ny = ceil(ext[1] / e), nz = ceil(ext[2] / e);
-        if (nx * ny * nz <= (double)a.max_cells) { m.dim[0] = (int)nx; m.dim[1] = (int)ny; m.dim[2] = (int)nz; break; }
-        if (c > 1 << 20) return DEV_ERR_GRID_TOO_LARGE;
-    }
-    // cell = floor((p - lo) / edge); a neighbour within 1 m is at most R cells away on every axis
-    m.origin[0] = lo[0]; m.origin[1] = lo[1]; m.origin[2] = lo[2];
-    m.ncells = m.dim[0] * m.dim[1] * m.dim[2];
-    m.edge = 0.5 * c; m.inv_edge = 1.0 / m.edge; m.R = c == 1 ? 2 : 1;
-    m.ok = 1;
-    return 0;
-}
-
-__device__ __forceinline__ void cell_of(const GridIndex::Meta& m, float x, float y, float z, int c[3])
-{
-    // the same expression places the map points (grid_keys) and the queries (knn5_search_group)
-    c[0] = (int)floor(((double)x - m.origin[0]) * m.inv_edge);
-    c[1] = (int)floor(((double)y - m.origin[1]) * m.inv_edge);
-    c[2] = (int)floor(((double)z - m.origin[2]) * m.inv_edge);
-}
-
-__device__ __forceinline__ int cell_id_of(const GridIndex::Meta& m, const lvi_pt& p)
-{
-    int c[3];
-    cell_of(m, p.x, p.y, p.z, c);
-#pragma unroll
-    for (int d = 0; d < 3; d++) c[d] = min(max(c[d], 0), m.dim[d] - 1);
-    return (c[2] * m.dim[1] + c[1]) * m.dim[0] + c[0];
-}
+// the scan upload, which may come before or after the build on the stream).  Geometry (grid_meta_one), cell_id_of and the
+// count step itself (grid_count_wave) are in lvi_voxel.hpp: the binned map rebuild takes them inside its last kernel.
+__device__ __forceinline__ int grid_meta_one(const GridArgs& a, int w, GridIndex::Meta& m) { return grid_meta_one(a.vox, a.nout, a.max_cells, w, m); }
 
 // The index is a counting sort by cell WITHOUT a stable order: the 5-NN result is a minimum over a total order
 // of (distance, index) keys, so the order of the points inside a cell cannot change it.  count → exclusive scan
-// (two kernels, GRID_SCAN_BLOCKS chunks) → scatter.  Every kernel is a grid-stride loop over device-side counts: the
+// (GRID_SCAN_BLOCKS chunks) → scatter.  Every kernel is a grid-stride loop over device-side counts: the
 // launch geometry does not depend on the (device-only) map size.
 // Round 3: (1) the grid's geometry is derived by every workgroup of the count kernel itself (it follows from the map's bounding box:
 // a few hundred cycles; the one-thread kernel in front of the chain was 5 us of every map build) — the first workgroup of a
@@ -97,48 +56,33 @@ __device__ __forceinline__ int cell_id_of(const GridIndex::Meta& m, const lvi_pt
 // and the scatter advances THAT word, which ends as start(c) + count(c) = start(c + 1) — the array the search reads, with
 // cell_start[0] = 0 (2.6 MB less written per build, 2.6 MB less memory per slot); (3) the geometry is held in registers inside
 // the point loops (behind an atomic the compiler re-read origin / inv_edge / dim from global memory for every point).
+// Two launches after a binned map rebuild, three otherwise: (4) the chunk totals the scan needs are added up where the counts
+// are taken (grid_count_wave: one atomic per run of equal chunks in a wavefront) instead of by a pass over the whole count
+// array, 6 % occupied; blockSum is zero between builds like count: grid_scatter, which runs behind the scan that read it,
+// clears it; (5) the binned rebuild counts inside vb_copy, which holds every point of the map in registers one launch earlier
+// (GridCountHook, lvi_voxel.hpp): grid_count remains for the producers without one — the sorted tail and the incremental map.
 constexpr int GRID_PT_BLOCKS = 512;
-constexpr int GRID_SCAN_BLOCKS = 1024;
 
 __global__ __launch_bounds__(256) void grid_count_kernel(Batch<GridArgs> B_)
 {
     const GridArgs& a = B_.a[blockIdx.z];
     const int w = blockIdx.y;
-    __shared__ GridIndex::Meta sm[2];
-    __shared__ int serr[2];
-    const bool lead = blockIdx.x == 0 && w == 0;                  // this workgroup also reports the build's status word
-    if (threadIdx.x == 0) serr[w] = grid_meta_one(a, w, sm[w]);
-    if (threadIdx.x == 64 && lead) serr[1] = grid_meta_one(a, 1, sm[1]);
-    __syncthreads();
-    const GridIndex::Meta m = sm[w];
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.meta[w] = m;
-    if (lead && threadIdx.x == 0) a.d_status[1] = serr[0] | serr[1];
-    if (!m.ok) return;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < m.n; i += gridDim.x * 256) atomicAdd(&a.count[w][cell_id_of(m, a.ds[w][i])], 1);
-}
-
-// chunk b of the ncells entries: its total
-__global__ __launch_bounds__(256) void grid_scan_sum_kernel(Batch<GridArgs> B_)
-{
-    const GridArgs& a = B_.a[blockIdx.z];
-    const int w = blockIdx.y;
-    const int ncells = a.meta[w]->ncells, ok = a.meta[w]->ok;
-    const int L = (ncells + GRID_SCAN_BLOCKS - 1) / GRID_SCAN_BLOCKS;
-    const int c0 = blockIdx.x * L, c1 = min(ncells, c0 + L);
-    int v = 0;
-    if (ok) {
-        for (int c = c0 + threadIdx.x; c < c1; c += 8 * 256) {      // eight loads in flight
-            int t[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) t[u] = a.count[w][min(c + u * 256, max(c1 - 1, 0))];
-#pragma unroll
-            for (int u = 0; u < 8; u++) v += c + u * 256 < c1 ? t[u] : 0;
-        }
+    // every thread for itself, from uniform inputs (as vb_copy does under its hook): no LDS round trip, no barrier
+    GridIndex::Meta m;
+    const int err = grid_meta_one(a, w, m);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *a.meta[w] = m;
+        if (w == 0) { GridIndex::Meta m1; a.d_status[1] = err | grid_meta_one(a, 1, m1); }      // the build's status word
     }
-    __shared__ int ws[8];
-    int tot;
-    (void)block_excl_scan<256>(v, ws, &tot);
-    if (threadIdx.x == 0) a.blockSum[w][blockIdx.x] = tot;
+    if (!m.ok) return;
+    const int L = grid_chunk_len(m.ncells);
+    const lvi_pt* __restrict__ ds = a.ds[w];
+    int* __restrict__ cnt = a.count[w];
+    int* __restrict__ bsum = a.blockSum[w];
+    for (int base = blockIdx.x * 256; base < m.n; base += gridDim.x * 256) {      // (the same trip count in every lane: grid_count_wave is a wavefront's call)
+        const int i = base + threadIdx.x;
+        grid_count_wave(m, L, cnt, bsum, i < m.n, ds[min(i, m.n - 1)]);
+    }
 }
 
 // cell_start[0] = 0, cell_start[c + 1] = points in cells < c (the scatter's cursor of cell c; start(c + 1) once the scatter is through);
@@ -148,23 +92,27 @@ __global__ __launch_bounds__(256) void grid_scan_apply_kernel(Batch<GridArgs> B_
     const GridArgs& a = B_.a[blockIdx.z];
     const int w = blockIdx.y;
     const int ncells = a.meta[w]->ncells, ok = a.meta[w]->ok;
-    const int L = (ncells + GRID_SCAN_BLOCKS - 1) / GRID_SCAN_BLOCKS;
+    const int L = grid_chunk_len(ncells);
     const int c0 = blockIdx.x * L, c1 = min(ncells, c0 + L);
     if (blockIdx.x == 0 && threadIdx.x == 0) a.cell_start[w][0] = 0;
     if (c0 >= c1) return;
     __shared__ int ws[8];
+    int* __restrict__ cnt = a.count[w];
+    int* __restrict__ cs = a.cell_start[w];
+    // the counts of a step are loaded one step ahead, the first ones in front of the carry: nobody has read the count array
+    // since the atomics of the count step, and its empty lines (94 % of them) come from HBM
+    int vn = cnt[min(c0 + (int)threadIdx.x, c1 - 1)];
     int carry;
     {
         int v = 0;
         for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) v += a.blockSum[w][j];
         (void)block_excl_scan<256>(v, ws, &carry);
     }
-    int* __restrict__ cnt = a.count[w];
-    int* __restrict__ cs = a.cell_start[w];
     for (int base = c0; base < c1; base += 256) {
         const int c = base + threadIdx.x;
         const bool live = c < c1 && ok;
-        const int v = live ? cnt[c] : 0;
+        const int v = live ? vn : 0;
+        vn = cnt[min(c + 256, c1 - 1)];                              // (unconditional, clamped: masked by `live` when used)
         int tot;
         const int ex = carry + block_excl_scan<256>(v, ws, &tot);
         if (c < c1) cs[c + 1] = ex;
@@ -178,6 +126,8 @@ __global__ __launch_bounds__(256) void grid_scatter_kernel(Batch<GridArgs> B_)
     const GridArgs& a = B_.a[blockIdx.z];
     const int w = blockIdx.y;
     const GridIndex::Meta m = *a.meta[w];
+    // grid_scan_apply has read the chunk totals: zero for the next build's count step, whichever kernel takes it
+    if (blockIdx.x == 0) for (int j = threadIdx.x; j < GRID_SCAN_BLOCKS; j += 256) a.blockSum[w][j] = 0;
     if (!m.ok) return;
     int* __restrict__ cs = a.cell_start[w];
     lvi_pt* __restrict__ sorted = a.sorted[w];
@@ -1625,6 +1575,15 @@ static GridArgs grid_args(LidarDev& d)
     return g;
 }
 
+// what vb_copy of the slot's binned map rebuild needs to take the index's count step (the same arrays grid_args hands grid_count)
+static GridCountHook grid_count_hook(LidarDev& d)
+{
+    GridCountHook h{};
+    for (int w = 0; w < 2; w++) { h.meta[w] = d.grid[w].meta; h.count[w] = d.grid[w].count; h.blockSum[w] = d.grid[w].blockSum; }
+    h.d_status = d.d_status; h.max_cells = d.max_cells;
+    return h;
+}
+
 // The map build does not depend on the current scan, so it runs on its own stream and overlaps the
 // scan-side stages (organise / sector kernel / scan voxel grids, which occupy only a few CUs); the
 // main stream joins it right before scan matching.  Batch: every slot re-voxelises and re-indexes the (shared) raw map
@@ -1656,12 +1615,13 @@ void stage_map_build(const Slots& sl)
         LidarDev& q = sl[z];
         q.n_map_corner = d.n_map_corner; q.n_map_surf = d.n_map_surf;
         q.voxMap.n_host[0] = d.n_map_corner; q.voxMap.n_host[1] = d.n_map_surf; q.voxMap.use_n_host = true;       // raw map counts are host-known here: kernel arguments instead of a 1-thread launch writing d_dyn
+        q.voxMap.index = grid_count_hook(q);
         plans[z] = &q.voxMap; st[z] = map_vox_state(d, q.voxMap);
         q.have_map = true;
     }
     const double n = ((double)d.n_map_corner + (double)d.n_map_surf) * sl.n;
-    voxel_downsample_batch(cx, plans, st, sl.n, "map", n);
-    stage_map_index(sl, cx);
+    const VoxSchedule sc = voxel_downsample_batch(cx, plans, st, sl.n, "map", n);
+    stage_map_index(sl, cx, voxel_run_indexed(d.voxMap, sc));
     if (forked) {
         LVI_HIP(hipEventRecord(d.evMap, cx.stream));
         d.map_pending = true;
@@ -1678,15 +1638,14 @@ VoxPlanState map_vox_state(const LidarDev& owner, const VoxelPlan& slot_plan)
 }
 
 // the replacement of the two KdTreeFLANN::setInputCloud calls (mapOptimization.cpp:1322-1323) over every slot's DS map
-void stage_map_index(const Slots& sl, const Ctx& cx)
+void stage_map_index(const Slots& sl, const Ctx& cx, bool counted)
 {
     Batch<GridArgs> G;
     double nds = 0;
     for (int z = 0; z < sl.n; z++) { G.a[z] = grid_args(sl[z]); nds += 0.02 * ((double)sl[z].n_map_corner + (double)sl[z].n_map_surf); }   // nominal DS size, byte accounting only
     for (int z = sl.n; z < MAX_BATCH; z++) G.a[z] = G.a[0];
     const unsigned S = (unsigned)sl.n;
-    LVI_LAUNCH(cx, "grid_count", 16.0 * nds, hipLaunchKernelGGL(grid_count_kernel, dim3(GRID_PT_BLOCKS, 2, S), dim3(256), 0, cx.stream, G));
-    LVI_LAUNCH(cx, "grid_scan_sum", 0, hipLaunchKernelGGL(grid_scan_sum_kernel, dim3(GRID_SCAN_BLOCKS, 2, S), dim3(256), 0, cx.stream, G));
+    if (!counted) LVI_LAUNCH(cx, "grid_count", 16.0 * nds, hipLaunchKernelGGL(grid_count_kernel, dim3(GRID_PT_BLOCKS, 2, S), dim3(256), 0, cx.stream, G));
     LVI_LAUNCH(cx, "grid_scan_apply", 0, hipLaunchKernelGGL(grid_scan_apply_kernel, dim3(GRID_SCAN_BLOCKS, 2, S), dim3(256), 0, cx.stream, G));
     LVI_LAUNCH(cx, "grid_scatter", 32.0 * nds, hipLaunchKernelGGL(grid_scatter_kernel, dim3(GRID_PT_BLOCKS, 2, S), dim3(256), 0, cx.stream, G));
 }
@@ -1764,7 +1723,7 @@ bool stage_map_update(LidarDev& d, const int32_t* keys, int n_keys)
     if (na) LVI_HIP(hipMemcpyAsync(m.d_active, m.h_active, sizeof(int) * (size_t)na, hipMemcpyHostToDevice, cx.stream));
     incmap_emit(cx, m, na, leaf, d.voxMap.d_grid, d.voxMap.d_nout, d.mapCornerDS, d.mapSurfDS, d.map_cap);
     d.n_map_corner = (int)std::min<long long>(tc, d.map_cap); d.n_map_surf = (int)std::min<long long>(ts, d.map_cap);
-    stage_map_index(OneSlot(d).s, cx);
+    stage_map_index(OneSlot(d).s, cx, false);
     LVI_HIP(hipMemcpyAsync(m.h_status, m.d_status, sizeof(int), hipMemcpyDeviceToHost, cx.stream));
     LVI_HIP(hipMemcpyAsync(m.h_status + 1, m.d_nocc, sizeof(int) * 2, hipMemcpyDeviceToHost, cx.stream));
     if (forked) { LVI_HIP(hipEventRecord(d.evMap, cx.stream)); d.map_pending = true; }

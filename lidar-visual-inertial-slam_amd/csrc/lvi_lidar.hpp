@@ -15,7 +15,7 @@ constexpr int KNN_G = 8;                // lanes that share one KNN query (measu
 constexpr int ICP_BLOCK = 64 * KNN_G;   // residual workgroup: 64 features x KNN_G lanes
 
 // device status bits (sticky until the next upload)
-enum { DEV_ERR_SECTOR_TOO_LARGE = 1, DEV_ERR_GRID_TOO_LARGE = 2, DEV_ERR_SECTOR_HANDOVER = 4 };
+enum { DEV_ERR_SECTOR_TOO_LARGE = 1, DEV_ERR_GRID_TOO_LARGE = GRID_ERR_TOO_LARGE, DEV_ERR_SECTOR_HANDOVER = 4 };
 
 struct IcpPose {                         // written by icp_solve for the next residual pass
     float T[6];                          // transformTobeMapped: roll pitch yaw x y z
@@ -50,9 +50,11 @@ struct IcpHostResult {
 struct GridIndex {                       // uniform 0.5 m grid over one DS map (a-6 replacement for the kd-tree)
     int* cell_start = nullptr;           // [max_cells + 2]
     int* count = nullptr;                // [max_cells + 2] points per cell (zero between builds)
-    int* blockSum = nullptr;             // [1024] chunk totals of the cell scan
+    int* blockSum = nullptr;             // [GRID_SCAN_BLOCKS] chunk totals of the cell scan, added to where the counts are taken; zero between builds
+                                         // (the arena is cleared at creation, grid_scatter clears it behind grid_scan_apply)
     lvi_pt* sorted = nullptr;            // [cap] xyz + original DS index in the intensity slot (as int bits)
-    struct Meta { double origin[3]; double edge, inv_edge; int dim[3]; int ncells; int n; int ok; int R; }* meta = nullptr;   // device
+    using Meta = GridMeta;
+    Meta* meta = nullptr;                // device
 };
 
 struct GmapDev;                                         // lvi_gmap.hip: the global-map arena (include/lvi_gmap.h)
@@ -182,7 +184,8 @@ void stage_map_build(const Slots& s);
 void stage_scan_match_enqueue(const Slots& s, const lvi_imu_hint* imu, void* d_records, int it_begin = 0, int it_end = -1);
 void set_pose_init(const Slots& s, const float* pose_init, bool clear_status);          // [n][6]; clear_status: also zero the scan-side device status words
 bool stage_map_update(LidarDev& d, const int32_t* keys, int n_keys);       // f-4 incremental: false = not applicable / device said no → the caller assembles
-void stage_map_index(const Slots& s, const Ctx& cx);                     // the KNN grid index over every slot's DS map
+// the KNN grid index over every slot's DS map; counted: the map's producer took the count step (vb_copy of a binned rebuild)
+void stage_map_index(const Slots& s, const Ctx& cx, bool counted);
 void stage_map_assemble(LidarDev& d, const int32_t* keys, int n_keys);      // f-4: fuse the keyframes into the raw map buffers (the caller builds)
 void stage_organize(LidarDev& d);
 void stage_extract(LidarDev& d);

@@ -54,7 +54,9 @@ struct VoxArgs {
     unsigned* wprefix;                                 // [nseg][VB_WG][VB_NB] points of bin b in the ranges of workgroups < w (deterministic partition)
     int ch;                                            // points per accumulate chunk of this launch sequence: VB_CH, or a multiple of it when many slots fill the chip anyway (<= 32768: chunk-table counts are 16 bits)
     int sx;                                            // slots of this launch folded into blockIdx.x (vb_block); 1: blockIdx.z is the slot
+    GridCountHook index;                               // vb_copy<true>: the KNN index's count step on what it writes (null for every plan but the local map)
 };
+static_assert(sizeof(Batch<VoxArgs>) <= 4096, "the argument blocks of a batch are one kernel argument");
 
 // Block decode of the passes over the raw local map.  Every slot of a batch reads the SAME map, and with the slot in blockIdx.z
 // slot z + 1 streams a line a whole 78 MB sweep after slot z did: long gone from the 4 MB L2 of the XCD, so S slots fetch the
@@ -591,22 +593,7 @@ __global__ __launch_bounds__(256) void vox_centroid_kernel(Batch<VoxArgs> B_)
 // is 1024 consecutive voxel indices and fits LDS; larger grids get wider bins that are swept once per
 // occupied 1024-voxel sub-range.  Nothing is sorted and nothing needs a stable order: integer sums commute.
 // =====================================================================================================
-// Runs of equal consecutive values across the lanes of a wave (consecutive points of a cloud mostly share a
-// bin / a voxel, and same-address LDS atomics serialise).  head = first lane of its run; hpos = that lane;
-// len (valid on head lanes) = lanes in the run.
-struct WaveRun { bool head; int hpos; int len; };
-__device__ __forceinline__ WaveRun wave_runs(unsigned v)
-{
-    const int l = lane_id();
-    const unsigned prev = __shfl_up(v, 1, 64);
-    WaveRun r;
-    r.head = l == 0 || prev != v;
-    const uint64_t hm = __ballot(r.head);
-    r.hpos = 63 - __clzll(hm & ((2ull << l) - 1ull));
-    const uint64_t above = l == 63 ? 0ull : hm & ~((2ull << l) - 1ull);
-    r.len = (above ? __ffsll((unsigned long long)above) - 1 : 64) - l;
-    return r;
-}
+// (wave_runs, lvi_voxel.hpp: consecutive points of a cloud mostly share a bin / a voxel, and same-address LDS atomics serialise)
 
 __global__ __launch_bounds__(256) void vb_hist_kernel(Batch<VoxArgs> B_)
 {
@@ -1246,21 +1233,56 @@ __global__ __launch_bounds__(256) void vb_outscan_kernel(Batch<VoxArgs> B_)
     }
 }
 
+// INDEX (two-segment plans with a.index set, the local map): every point written is also counted into its cell of the KNN grid
+// index and its chunk of the cell scan — the index's first step, which would otherwise read the output back one launch later.
+// The index's geometry needs nout[] and the bounding box, both final since vb_outscan: every thread that counts derives it, the
+// first workgroup of a segment stores it (and the build's status word) for grid_scan_apply / grid_scatter and the searches.
+// A bin of the map holds some eighty voxels: under INDEX a WAVEFRONT owns a bin (four consecutive bins per workgroup), and the
+// workgroups past the last bin leave before they derive anything — a quarter of the grid does the work, in a quarter of the rounds.
+template <bool INDEX>
 __global__ __launch_bounds__(256) void vb_copy_kernel(Batch<VoxArgs> B_)
 {
     const VoxArgs& a = B_.a[blockIdx.z];
     const int s = blockIdx.y;
     const VoxGrid& g = a.grid[s];
+    const int overflow = g.overflow, nbins = g.nbins;              // (not read again behind the atomics)
     lvi_pt* __restrict__ out = (a.concat ? a.st[0].out : a.st[s].out) + g.out_off;
     const int tid = threadIdx.x;
-    if (!g.overflow) {
+    GridMeta m;
+    int L = 1;
+    int* __restrict__ cnt = nullptr;
+    int* __restrict__ bsum = nullptr;
+    if constexpr (INDEX) {
+        if (!overflow && (int)blockIdx.x * 4 >= nbins && blockIdx.x != 0) return;
+        // every thread for itself, from uniform inputs: no LDS round trip and no barrier in front of the copy
+        const int err = grid_meta_one(a.grid, a.nout, a.index.max_cells, s, m);
+        if (blockIdx.x == 0 && tid == 0) {
+            *a.index.meta[s] = m;
+            if (s == 0) { GridMeta m1; a.index.d_status[1] = err | grid_meta_one(a.grid, a.nout, a.index.max_cells, 1, m1); }   // the build's status word
+        }
+        L = grid_chunk_len(m.ncells);
+        cnt = a.index.count[s]; bsum = a.index.blockSum[s];
+    }
+    if (!overflow) {
         const int* bs = a.binStart + (size_t)s * (VB_NB + 1);
         const int* bv = a.binVox + (size_t)s * VB_NB;
         const int* bo = a.binOut + (size_t)s * VB_NB;
         const lvi_pt* __restrict__ stg = a.staging + (size_t)s * a.seg_cap;
-        for (int b = blockIdx.x; b < g.nbins; b += gridDim.x) {
-            const int nv = bv[b], src = bs[b], dst = bo[b];
-            for (int j = tid; j < nv; j += 256) out[dst + j] = stg[src + j];
+        if constexpr (INDEX) {
+            for (int b = (int)blockIdx.x * 4 + wave_id(); b < nbins; b += (int)gridDim.x * 4) {
+                const int nv = bv[b], src = bs[b], dst = bo[b];
+                for (int j0 = 0; j0 < nv; j0 += 64) {              // (the same trip count in every lane: grid_count_wave is a wavefront's call)
+                    const int j = j0 + lane_id();
+                    const lvi_pt p = stg[src + min(j, nv - 1)];
+                    if (j < nv) out[dst + j] = p;
+                    grid_count_wave(m, L, cnt, bsum, j < nv && m.ok, p);
+                }
+            }
+        } else {
+            for (int b = blockIdx.x; b < nbins; b += gridDim.x) {
+                const int nv = bv[b], src = bs[b], dst = bo[b];
+                for (int j = tid; j < nv; j += 256) out[dst + j] = stg[src + j];
+            }
         }
         return;
     }
@@ -1286,7 +1308,13 @@ __global__ __launch_bounds__(256) void vb_copy_kernel(Batch<VoxArgs> B_)
         const bool keep = j < i1 && (!mask || mask[j]);
         int tot;
         const int r = block_excl_scan<256>(keep ? 1 : 0, ws, &tot);
-        if (keep) out[basep + r] = in[j];
+        if constexpr (INDEX) {
+            const lvi_pt p = in[min(j, i1 - 1)];
+            if (keep) out[basep + r] = p;
+            grid_count_wave(m, L, cnt, bsum, keep && m.ok, p);
+        } else {
+            if (keep) out[basep + r] = in[j];
+        }
         basep += tot;
     }
 }
@@ -1384,7 +1412,7 @@ static VoxArgs make_args(const VoxelPlan& p)
                    p.d_binCount, p.d_binStart, p.d_cursor, p.d_binVox, p.d_binOut, p.d_bucketed, p.d_staging, p.d_stagingKC, p.h_ncells,
                    p.d_chunkStart, p.d_multiStart, p.d_chunkBin, p.max_chunks, p.d_lightBin, p.d_multiOwner, p.d_chunkTabV, p.d_chunkTabC, p.max_multi,
                    {p.n_host[0], p.n_host[1], p.n_host[2], p.n_host[3]}, (p.use_n_host && p.nseg <= 4) ? 1 : 0,
-                   {p.n_dev[0], p.n_dev[1], p.n_dev[2], p.n_dev[3]}, p.bin_pts, p.bin_max, nullptr, p.d_binCountCached, p.d_planMiss, 0, p.d_wprefix, VB_CH, 1};
+                   {p.n_dev[0], p.n_dev[1], p.n_dev[2], p.n_dev[3]}, p.bin_pts, p.bin_max, nullptr, p.d_binCountCached, p.d_planMiss, 0, p.d_wprefix, VB_CH, 1, p.index};
 }
 
 void VoxelPlan::set_static(const Ctx& ctx, const VoxSegStatic* host_segs)
@@ -1770,7 +1798,8 @@ struct VoxRun {
         VOX_LAUNCH("vb_accum", 16.0 * n_hint, vb_accum_kernel<256>, ga);
         VOX_LAUNCH("vb_merge", 0, vb_merge_kernel, dim3(std::max(1, std::min(p.max_multi, VB_ACC_BLOCKS)), p.nseg, S));
         VOX_LAUNCH("vb_outscan", 0, vb_outscan_kernel, dim3(1, 1, S));
-        VOX_LAUNCH("vb_copy", 0, vb_copy_kernel, gb);
+        if (voxel_run_indexed(p, sc)) VOX_LAUNCH("vb_copy", 0, vb_copy_kernel<true>, gb);
+        else VOX_LAUNCH("vb_copy", 0, vb_copy_kernel<false>, gb);
     }
     void sorted_tail()                                   // S = 1
     {

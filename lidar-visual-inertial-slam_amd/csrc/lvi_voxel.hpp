@@ -45,6 +45,20 @@ struct VoxGrid {                 // device, per segment
     int plan_ok;                 // vb_plan's histogram (taken under the PREVIOUS run's geometry, in the pass that takes the bbox) is valid for this run's geometry
 };
 
+// ---- KNN grid index over a downsampled map (built in lvi_icp.hip).  Its first step — one counter per point's cell, one per
+//      chunk of the cell scan — is taken by whoever writes the downsampled map last: vb_copy of the binned map rebuild through
+//      the hook below, grid_count (lvi_icp.hip) for every other producer.  Both use the device code at the end of this file.
+struct GridMeta { double origin[3]; double edge, inv_edge; int dim[3]; int ncells; int n; int ok; int R; };
+constexpr int GRID_SCAN_BLOCKS = 1024;       // chunks of the cell scan: chunk = cell / ceil(ncells / GRID_SCAN_BLOCKS)
+constexpr int GRID_ERR_TOO_LARGE = 2;        // status bit of a map no cell edge up to 2^19 m fits into max_cells (DEV_ERR_GRID_TOO_LARGE)
+struct GridCountHook {                       // all null: the plan's output is not indexed where it is written
+    GridMeta* meta[2];                       // per segment (corner, surf): the geometry, stored by the segment's first workgroup
+    int* count[2];                           // [max_cells + 1] points per cell, zero between builds
+    int* blockSum[2];                        // [GRID_SCAN_BLOCKS] points per chunk, zero between builds
+    int* d_status;                           // [1] = the build's status word
+    int max_cells;
+};
+
 constexpr int VOX_HT = 1024;     // keys per workgroup in the head (segment boundary) kernels
 constexpr int VB_NB = 4096;      // binned path: bins per segment (LDS histogram of the partition kernels)
 constexpr int VB_CL_LOG = 10;    // binned path: voxels accumulated in LDS per sweep = 1 << VB_CL_LOG
@@ -105,6 +119,7 @@ struct VoxelPlan {
     unsigned* d_binCountCached = nullptr;     // [nseg][VB_NB] points per bin of the current input (vb_colscan)
     int* d_planMiss = nullptr;                // [nseg] a point fell outside the previous geometry (vb_plan)
     bool slot_major = true;                   // batch launches of the raw-map passes fold the slot into blockIdx.x (vb_block; LVI_VB_SLOT_ORDER=0: blockIdx.z = slot)
+    GridCountHook index = {};                 // two-segment plans whose output gets a KNN index (the local map): vb_copy counts what it writes
 
     template <class AR> void allocate(AR& ar, int nseg_, int seg_cap_, bool concat)
     {
@@ -209,6 +224,8 @@ void incmap_emit(const Ctx& ctx, const IncMap& m, int n_active, const float leaf
 // under VoxSchedule::fold_slots: the slot folded into blockIdx.x); n_hint = points of all slots.
 VoxSchedule voxel_downsample_batch(const Ctx& ctx, const VoxelPlan* const* plans, const VoxPlanState* st, int S, const char* tag, double n_hint);
 VoxSchedule voxel_downsample_batch(const Ctx& ctx, const VoxelPlan& plan, const char* tag, double n_hint);
+// whether a run of `plan` under schedule `sc` leaves the count step of the KNN index done (GridCountHook): binned runs of a plan with the hook
+inline bool voxel_run_indexed(const VoxelPlan& plan, const VoxSchedule& sc) { return sc.part != VOX_PART_NONE && plan.nseg == 2 && plan.index.count[0] != nullptr; }
 // what the plan itself tells about its next run: the resolved mode, the tables it owns, its lengths' source; not per-run, nothing valid
 VoxPlanState voxel_plan_state(const VoxelPlan& plan);
 // the bbox partial records of the plan's current input as a pass of its own, and — when the plan resolves to BINNED and owns
@@ -223,5 +240,94 @@ void voxel_tiny(const Ctx& ctx, const lvi_pt* in_pinned, int n, float leaf, int 
                 int* cells_pinned, int* counts_pinned, int* keys_pinned);
 // debug views of the plan's latest run over n_in points: per-point voxel idx, the occupied voxels and their point counts
 void voxel_debug_fetch(const Ctx& ctx, const VoxelPlan& p, int n_in, std::vector<int32_t>& keys, std::vector<int32_t>& cells, std::vector<int32_t>& counts);
+
+#ifdef __HIPCC__
+// Runs of equal consecutive values across the lanes of a wave (consecutive points of a cloud mostly share a
+// bin / a voxel, and same-address atomics serialise).  head = first lane of its run; hpos = that lane;
+// len (valid on head lanes) = lanes in the run.  Every lane of the wavefront calls it.
+struct WaveRun { bool head; int hpos; int len; };
+__device__ __forceinline__ WaveRun wave_runs(unsigned v)
+{
+    const int l = lane_id();
+    const unsigned prev = __shfl_up(v, 1, 64);
+    WaveRun r;
+    r.head = l == 0 || prev != v;
+    const uint64_t hm = __ballot(r.head);
+    r.hpos = 63 - __clzll(hm & ((2ull << l) - 1ull));
+    const uint64_t above = l == 63 ? 0ull : hm & ~((2ull << l) - 1ull);
+    r.len = (above ? __ffsll((unsigned long long)above) - 1 : 64) - l;
+    return r;
+}
+
+// ---- KNN grid index: geometry and the count step (GridMeta / GridCountHook above)
+// The geometry of segment w's index follows from the bounding box of the raw map (vox[w].bb) and the size of the downsampled one
+// (nout[w]): a hundred cycles for 0.5 m cells, so every thread that counts derives it itself from the (uniform) records — no
+// one-thread kernel in front, no barrier.  Returns the segment's status bits.
+__device__ inline int grid_meta_one(const VoxGrid* vox, const int* nout, int max_cells, int w, GridMeta& m)
+{
+    const int n = nout[w];
+    m.n = n; m.ok = 0; m.R = 1; m.edge = 0.5; m.inv_edge = 2.0;
+    m.dim[0] = m.dim[1] = m.dim[2] = 1; m.ncells = 1; m.origin[0] = m.origin[1] = m.origin[2] = 0.0;
+    if (n <= 0 || vox[w].n_valid == 0) return 0;
+    double lo[3], ext[3];
+    for (int d = 0; d < 3; d++) {
+        const double mn = floor((double)ord2f(vox[w].bb[d])), mx = floor((double)ord2f(vox[w].bb[3 + d]));
+        lo[d] = mn - 1.0;                       // one cell of padding on every side
+        ext[d] = mx - mn + 3.0;
+    }
+    int c = 1;                                  // cell edge in half metres, integer >= 1
+    // c = 1, the cell every map of ordinary extent gets: ext / 0.5 is ext * 2 and 1 / 0.5 is 2, exactly — no f64 division
+    // (tens of instructions each on gfx950) in front of the workgroup's first point
+    double nx = ceil(ext[0] * 2.0), ny = ceil(ext[1] * 2.0), nz = ceil(ext[2] * 2.0);
+    while (!(nx * ny * nz <= (double)max_cells)) {
+        if (c > 1 << 20) return GRID_ERR_TOO_LARGE;
+        c++;
+        const double e = 0.5 * c;
+        nx = ceil(ext[0] / e); ny = ceil(ext[1] / e); nz = ceil(ext[2] / e);
+    }
+    m.dim[0] = (int)nx; m.dim[1] = (int)ny; m.dim[2] = (int)nz;
+    // cell = floor((p - lo) / edge); a neighbour within 1 m is at most R cells away on every axis
+    m.origin[0] = lo[0]; m.origin[1] = lo[1]; m.origin[2] = lo[2];
+    m.ncells = m.dim[0] * m.dim[1] * m.dim[2];
+    m.edge = 0.5 * c; m.inv_edge = c == 1 ? 2.0 : 1.0 / m.edge; m.R = c == 1 ? 2 : 1;
+    m.ok = 1;
+    return 0;
+}
+
+__device__ __forceinline__ void cell_of(const GridMeta& m, float x, float y, float z, int c[3])
+{
+    // the same expression places the map points (grid_count_wave, grid_scatter) and the queries (knn5_search_acc)
+    c[0] = (int)floor(((double)x - m.origin[0]) * m.inv_edge);
+    c[1] = (int)floor(((double)y - m.origin[1]) * m.inv_edge);
+    c[2] = (int)floor(((double)z - m.origin[2]) * m.inv_edge);
+}
+
+__device__ __forceinline__ int cell_id_of(const GridMeta& m, const lvi_pt& p)
+{
+    int c[3];
+    cell_of(m, p.x, p.y, p.z, c);
+#pragma unroll
+    for (int d = 0; d < 3; d++) c[d] = min(max(c[d], 0), m.dim[d] - 1);
+    return (c[2] * m.dim[1] + c[1]) * m.dim[0] + c[0];
+}
+
+// cells per chunk of the cell scan (grid_scan_apply)
+__device__ __forceinline__ int grid_chunk_len(int ncells) { return (ncells + GRID_SCAN_BLOCKS - 1) / GRID_SCAN_BLOCKS; }
+
+// One point per lane (act: the lane has one; p is a real point of the map on every lane): its cell's counter, and its chunk's
+// total where the counts are taken instead of a pass over the whole count array behind them.  The downsampled map comes in
+// voxel order, so the points of a wavefront fall into a few chunks: one atomic per run of equal chunks.  Every lane of the
+// wavefront calls it; m and L live in registers (behind an atomic the compiler would read them again for every point).
+__device__ __forceinline__ void grid_count_wave(const GridMeta& m, int L, int* __restrict__ count, int* __restrict__ blockSum, bool act, const lvi_pt& p)
+{
+    const int cell = cell_id_of(m, p);
+    const unsigned chunk = act ? (unsigned)(cell / L) : ~0u;          // (< GRID_SCAN_BLOCKS: cell < ncells <= L * GRID_SCAN_BLOCKS)
+    const WaveRun r = wave_runs(chunk);
+    if (act) {
+        atomicAdd(&count[cell], 1);
+        if (r.head) atomicAdd(&blockSum[chunk], r.len);
+    }
+}
+#endif
 
 }  // namespace lvi

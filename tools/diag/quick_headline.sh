@@ -5,5 +5,5 @@ python3 bench.py --no-cpu --no-tracker --sequential-scans 0 --cached-plan-steps 
 python3 - <<'PY'
 import json
 d=json.loads(open('gpurun_out/qh.json').read().strip().splitlines()[-1])
-print("value", d["value"], d["unit"], "ms/step", d["ms_per_step"], "windows", d.get("windows") or d.get("config",{}).get("windows"))
+print("value", d["value"], d["unit"], "ms/step", d["ms_per_step"], "windows", (d.get("value_windows") or {}).get("scans_per_sec", {}).get("all"))
 PY
