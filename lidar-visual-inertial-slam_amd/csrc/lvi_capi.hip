@@ -183,9 +183,7 @@ int32_t lvi_lidar_create(const lvi_lidar_params* p, int32_t device, lvi_lidar** 
     if (p->icp_max_iters < 0) return fail(LVI_ERR_INVALID_ARG, "icp_max_iters < 0");
     if (p->max_map_points > (1 << 25) || p->max_raw_points > (1 << 25)) return fail(LVI_ERR_INVALID_ARG, "capacities above 2^25 points are not supported");
     if (p->voxel_mode < 0 || p->voxel_mode > 2) return fail(LVI_ERR_INVALID_ARG, "voxel_mode must be 0 (auto), 1 (sorted) or 2 (binned)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (const int32_t bad = check_device(device)) return bad;
     if (p->batch_scans < 0 || p->batch_scans > LVI_MAX_BATCH) return fail(LVI_ERR_INVALID_ARG, "batch_scans must be 0..LVI_MAX_BATCH");
     lvi_lidar* h = new lvi_lidar();
     h->slots.push_back(&h->d);

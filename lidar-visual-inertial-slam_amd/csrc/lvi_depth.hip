@@ -390,9 +390,7 @@ int32_t lvi_depth_create(int32_t device, int32_t max_clouds, int32_t max_cloud_p
     if (max_clouds < 1 || max_clouds > LVI_DEPTH_MAX_CLOUDS) return fail(LVI_ERR_INVALID_ARG, "max_clouds must be 1..LVI_DEPTH_MAX_CLOUDS");
     if (max_cloud_points < 1 || max_features < 1 || lidar_skip < 0 || !(window_s >= 0.0)) return fail(LVI_ERR_INVALID_ARG, "bad capacities");
     if ((long long)max_clouds * max_cloud_points > (1 << 25) || max_features > (1 << 20)) return fail(LVI_ERR_INVALID_ARG, "capacities above 2^25 window points are not supported");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (const int32_t bad = check_device(device)) return bad;
     lvi_depth* h = new lvi_depth();
     h->device = device; h->C = max_clouds; h->P = max_cloud_points; h->F = max_features; h->skip = lidar_skip; h->window = window_s;
     // float dist_sq_threshold = pow(sin(bin_res / 180.0 * M_PI) * 5.0, 2)

@@ -33,6 +33,15 @@ struct HipError { hipError_t e; const char* what; const char* file; int line; };
 // LVI_ERR_HIP with its text in lvi_last_error(); a negative device skips hipSetDevice.
 inline int32_t fail(int32_t code, const std::string& msg) { set_error(msg); return code; }
 
+// the device check of every create function: the code and the text a caller gets for a machine without a GPU or a bad index
+inline int32_t check_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    return LVI_OK;
+}
+
 template <class F>
 int32_t guarded(int device, F&& f)
 {
@@ -115,6 +124,7 @@ struct ArenaSizer {
 };
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
+inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }   // byte offsets of the parts of one buffer
 
 // Batched launches: one launch sequence serves up to LVI_MAX_BATCH independent scans (SURVEY §7.3-6 i).  Every kernel
 // of the lidar path takes the argument blocks of all scans of the batch and picks its own by blockIdx.z, so a batch of S

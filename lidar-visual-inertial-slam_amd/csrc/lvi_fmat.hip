@@ -1,90 +1,26 @@
 // rejectWithF's cv::findFundamentalMat(un_cur, un_forw, FM_RANSAC, F_THRESHOLD, 0.99, status) on the GPU
 // (feature_tracker.cpp:209-242; include/lvi_fmat.h; the contract is DESIGN §11).
 //
-//   host       the sample stream: cv::RNG((uint64)-1) and getSubset with the FM callback's checkSubset
-//              (OpenCV ptsetreg.cpp RANSACPointSetRegistrator::getSubset) — sequential integer work whose draws do not
-//              depend on any model, so the whole stream is known before the first hypothesis is scored
+//   host       the sample stream: getSubset with the FM callback's checkSubset (lvi_ransac.hpp)
 //   fmat_hyp   one wave per hypothesis: the 7-point kernel (fundam.cpp run7Point, with a Gauss-Jordan null space) in
 //              double, then every lane scores the 1..3 candidates over the points held in LDS
-//   fmat_walk  one wave replays the sequential RANSAC (ptsetreg.cpp RANSACPointSetRegistrator::run) or LMeDS
-//              (LMeDSPointSetRegistrator::run) walk from the counts / medians and writes the chosen model's status
+//   fmat_walk  one wave replays the sequential RANSAC (lvi_ransac.hpp) or LMeDS (LMeDSPointSetRegistrator::run) walk
+//              from the counts / medians and writes the chosen model's status
 //
 // Everything scored is double with -ffp-contract=off: for the same F bits the errors are those of the host restatement.
 #include <chrono>
 #include <cfloat>
 #include <cmath>
-#include <vector>
 
-#include "lvi_dev.hpp"
+#include "lvi_ransac.hpp"
 #include "../../include/lvi_fmat.h"
 
 using namespace lvi;
+using namespace lvi_ransac;
 
 namespace {
 
-constexpr int MODEL_POINTS = 7;
-constexpr int RANSAC_MAX_ATTEMPTS = 10000;   // RANSACPointSetRegistrator::run: getSubset(..., rng, 10000)
-constexpr int LMEDS_MAX_ATTEMPTS = 1000;     // LMeDSPointSetRegistrator::run: getSubset's default maxAttempts
-constexpr double LMEDS_OUTLIER_RATIO = 0.45;
-
-// ---------------------------------------------------------------------------------------------- host: the sample stream
-// cv::RNG: multiply-with-carry, state seeded with (uint64)-1; uniform(a, b) = a == b ? a : next() % (b - a) + a
-struct CvRng {
-    uint64_t s = ~(uint64_t)0;
-    uint32_t next() { s = (uint64_t)(uint32_t)s * 4164903690u + (uint32_t)(s >> 32); return (uint32_t)s; }
-    int uniform(int a, int b) { return a == b ? a : (int)(next() % (uint32_t)(b - a) + (uint32_t)a); }
-};
-
-// haveCollinearPoints (fundam.cpp): the last point of the subset against every pair of earlier ones, float differences
-bool have_collinear(const float* xy, const int* idx, int stride_off)
-{
-    const int i = MODEL_POINTS - 1;
-    auto X = [&](int k) { return xy[4 * idx[k] + stride_off]; };
-    auto Y = [&](int k) { return xy[4 * idx[k] + stride_off + 1]; };
-    for (int j = 0; j < i; j++) {
-        const double dx1 = X(j) - X(i), dy1 = Y(j) - Y(i);
-        for (int k = 0; k < j; k++) {
-            const double dx2 = X(k) - X(i), dy2 = Y(k) - Y(i);
-            if (std::fabs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (std::fabs(dx1) + std::fabs(dy1) + std::fabs(dx2) + std::fabs(dy2))) return true;
-        }
-    }
-    return false;
-}
-
-// getSubset: redraw duplicates, then checkSubset; false after max_attempts rejected subsets
-bool get_subset(CvRng& rng, const float* xy, int n, int check, int max_attempts, int* idx)
-{
-    for (int it = 0; it < max_attempts; ++it) {
-        for (int i = 0; i < MODEL_POINTS; ++i) {
-            int k = rng.uniform(0, n);
-            while (std::find(idx, idx + i, k) != idx + i) k = rng.uniform(0, n);
-            idx[i] = k;
-        }
-        if (!check || (!have_collinear(xy, idx, 0) && !have_collinear(xy, idx, 2))) return true;
-    }
-    return false;
-}
-
-// RANSACUpdateNumIters(p, ep, 7, ·) needs log(1 - (1 - ep)^7) for ep = (n - goodCount) / n: one entry per goodCount,
-// computed with the host C library so the device walk never calls log/pow.  +inf marks denom < DBL_MIN (returns 0).
-double update_log(int n, int good)
-{
-    double ep = (double)(n - good) / n;
-    ep = std::max(ep, 0.); ep = std::min(ep, 1.);
-    const double denom = 1. - std::pow(1. - ep, MODEL_POINTS);
-    if (denom < DBL_MIN) return HUGE_VAL;
-    return std::log(denom);
-}
-int update_num_iters(double p, double ep, int max_iters)        // the host form, for LMeDS's fixed count
-{
-    p = std::max(p, 0.); p = std::min(p, 1.);
-    ep = std::max(ep, 0.); ep = std::min(ep, 1.);
-    double num = std::max(1. - p, DBL_MIN);
-    double denom = 1. - std::pow(1. - ep, MODEL_POINTS);
-    if (denom < DBL_MIN) return 0;
-    num = std::log(num); denom = std::log(denom);
-    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)std::lrint(num / denom);
-}
+constexpr int MODEL_POINTS = FM_MODEL_POINTS;
 
 // ---------------------------------------------------------------------------------------------- device
 struct HypArgs {
@@ -324,98 +260,62 @@ struct WalkArgs {
     unsigned char* status;
 };
 
-// RANSACUpdateNumIters(p, ep, 7, max_iters) from the precomputed log(denom)
-__device__ __forceinline__ int update_iters(double num, double ld, int max_iters)
-{
-    if (ld == HUGE_VAL) return 0;
-    return ld >= 0 || -num >= max_iters * (-ld) ? max_iters : (int)rint(num / ld);
-}
-
 __global__ __launch_bounds__(LVI_WAVE) void fmat_walk(WalkArgs a)
 {
     __shared__ int s_best;
     __shared__ float s_thr;
     const int lane = threadIdx.x;
     if (lane == 0) {
-        int iter = 0, best_iter = -1, best_root = -1, niters;
+        Walk w{0, -1, -1};
         double best_median = 0.;
         float thr = a.thr;
         if (a.path == LVI_FMAT_PATH_KERNEL) {
-            niters = 1; iter = 1;
-            if (a.nmodels[0] > 0) { best_iter = 0; best_root = 0; }
+            w.iter = 1;
+            if (a.nmodels[0] > 0) { w.best_iter = 0; w.best_root = 0; }
         } else if (a.path == LVI_FMAT_PATH_RANSAC) {
-            int max_good = 0;
-            for (niters = a.niters0; iter < niters; iter++) {
-                if (iter >= a.nsub) break;                     // getSubset failed (iter > 0 here, or nsub == 0)
-                const int nm = a.nmodels[iter];
-                for (int m = 0; m < nm; m++) {
-                    const int good = a.score[3 * iter + m];
-                    if (good > max(max_good, MODEL_POINTS - 1)) {
-                        best_iter = iter; best_root = m; max_good = good;
-                        niters = update_iters(a.num_log, a.logtab[good], niters);
-                    }
-                }
-            }
+            w = ransac_walk<MODEL_POINTS>(a.nmodels, a.score, 3, a.nsub, a.niters0, a.num_log, a.logtab);
         } else {                                                // LMeDS
             double min_median = DBL_MAX;
-            for (niters = a.niters0; iter < niters; iter++) {
-                if (iter >= a.nsub) break;
-                const int nm = a.nmodels[iter];
+            for (; w.iter < a.niters0; w.iter++) {
+                if (w.iter >= a.nsub) break;
+                const int nm = a.nmodels[w.iter];
                 for (int m = 0; m < nm; m++) {
-                    const double median = (double)__int_as_float(a.score[3 * iter + m]);
-                    if (median < min_median) { min_median = median; best_iter = iter; best_root = m; }
+                    const double median = (double)__int_as_float(a.score[3 * w.iter + m]);
+                    if (median < min_median) { min_median = median; w.best_iter = w.iter; w.best_root = m; }
                 }
             }
-            if (best_iter >= 0) {
+            if (w.best_iter >= 0) {
                 best_median = min_median;
                 double sigma = 2.5 * 1.4826 * (1 + 5. / (a.n - MODEL_POINTS)) * sqrt(min_median);
                 sigma = sigma > 0.001 ? sigma : 0.001;
                 thr = (float)(sigma * sigma);
             }
         }
-        s_best = best_iter >= 0 ? 3 * best_iter + best_root : -1;
+        s_best = w.best_iter >= 0 ? 3 * w.best_iter + w.best_root : -1;
         s_thr = thr;
         lvi_fmat_info* o = a.info;
-        o->path = a.path; o->iters = iter; o->n_subsets = a.nsub; o->best_iter = best_iter; o->best_root = best_root;
+        o->path = a.path; o->iters = w.iter; o->n_subsets = a.nsub; o->best_iter = w.best_iter; o->best_root = w.best_root;
         o->best_median = best_median;
-        for (int k = 0; k < 9; k++) o->F[k] = best_iter >= 0 ? a.F[9 * (size_t)s_best + k] : 0.;
+        for (int k = 0; k < 9; k++) o->F[k] = w.best_iter >= 0 ? a.F[9 * (size_t)s_best + k] : 0.;
     }
     __syncthreads();
     const int best = s_best;
     const float thr = s_thr;
     double F[9];
     for (int k = 0; k < 9; k++) F[k] = best >= 0 ? a.F[9 * (size_t)best + k] : 0.;
-    int good = 0;
-    for (int base = 0; base < a.n; base += LVI_WAVE) {
-        const int i = base + lane;
-        bool in = false;
-        if (i < a.n) {
-            in = a.path == LVI_FMAT_PATH_KERNEL ? true : best >= 0 && fm_err(F, a.pts[i]) <= thr;
-            a.status[i] = in ? 1 : 0;
-        }
-        good += __popcll(__ballot(in));
-    }
+    const int good = status_sweep(a.n, a.status, [&](int i) { return a.path == LVI_FMAT_PATH_KERNEL ? true : best >= 0 && fm_err(F, a.pts[i]) <= thr; });
     if (lane == 0) a.info->n_inliers = good;
 }
-
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- the handle
 struct lvi_fmat {
-    int device = 0, P = 0, I = 0, check = 1;
-    hipStream_t stream = nullptr;
-    char* d_in = nullptr;                  // pts [P] float4 | subsets [I][7] | logtab [P + 1]
-    char* h_in = nullptr;                  // pinned mirror of d_in
-    char* d_out = nullptr;                 // info | status [P]
-    char* h_out = nullptr;
+    int P = 0, I = 0, check = 1;
+    Io io;                                 // d_in: pts [P] float4 | subsets [I][7] | logtab [P + 1]; d_out: info | status [P]
     double* d_F = nullptr;                 // [I][27]
     int *d_nm = nullptr, *d_score = nullptr;
-    size_t off_sub = 0, off_log = 0, in_bytes = 0, out_bytes = 0;
-    // last call
-    int last_n = 0, last_nsub = 0;
-    std::vector<int> last_subsets;
+    size_t off_sub = 0, off_log = 0;
 };
 
 extern "C" {
@@ -428,26 +328,14 @@ int32_t lvi_fmat_create(int32_t device, int32_t max_points, int32_t max_iters, l
     *out = nullptr;
     if (max_points < MODEL_POINTS || max_points > LVI_FMAT_MAX_POINTS) return fail(LVI_ERR_INVALID_ARG, "max_points must be 7..LVI_FMAT_MAX_POINTS");
     if (max_iters < 1 || max_iters > LVI_FMAT_MAX_ITERS) return fail(LVI_ERR_INVALID_ARG, "max_iters must be 1..LVI_FMAT_MAX_ITERS");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
     lvi_fmat* h = new lvi_fmat();
-    h->device = device; h->P = max_points; h->I = max_iters;
+    h->P = max_points; h->I = max_iters;
     h->off_sub = align256(sizeof(float4) * (size_t)h->P);
     h->off_log = h->off_sub + align256(sizeof(int) * 7 * (size_t)h->I);
-    h->in_bytes = h->off_log + align256(sizeof(double) * ((size_t)h->P + 1));
-    h->out_bytes = align256(sizeof(lvi_fmat_info)) + align256((size_t)h->P);
-    const int32_t st = guarded(h->device, [&]() -> int32_t {
-        LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        LVI_HIP(hipMalloc((void**)&h->d_in, h->in_bytes));
-        LVI_HIP(hipMalloc((void**)&h->d_out, h->out_bytes));
-        LVI_HIP(hipMalloc((void**)&h->d_F, sizeof(double) * 27 * (size_t)h->I));
-        LVI_HIP(hipMalloc((void**)&h->d_nm, sizeof(int) * (size_t)h->I));
-        LVI_HIP(hipMalloc((void**)&h->d_score, sizeof(int) * 3 * (size_t)h->I));
-        LVI_HIP(hipHostMalloc((void**)&h->h_in, h->in_bytes, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_out, h->out_bytes, hipHostMallocDefault));
-        return LVI_OK;
-    });
+    const int32_t st = h->io.open(device, h->off_log + align256(sizeof(double) * ((size_t)h->P + 1)), align256(sizeof(lvi_fmat_info)) + align256((size_t)h->P),
+                                  {{(void**)&h->d_F, sizeof(double) * 27 * (size_t)h->I},
+                                   {(void**)&h->d_nm, sizeof(int) * (size_t)h->I},
+                                   {(void**)&h->d_score, sizeof(int) * 3 * (size_t)h->I}});
     if (st != LVI_OK) { lvi_fmat_destroy(h); return st; }
     *out = h;
     return LVI_OK;
@@ -456,16 +344,7 @@ int32_t lvi_fmat_create(int32_t device, int32_t max_points, int32_t max_iters, l
 void lvi_fmat_destroy(lvi_fmat* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_out) (void)hipFree(h->d_out);
-    if (h->d_F) (void)hipFree(h->d_F);
-    if (h->d_nm) (void)hipFree(h->d_nm);
-    if (h->d_score) (void)hipFree(h->d_score);
-    if (h->h_in) (void)hipHostFree(h->h_in);
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->io.close({h->d_F, h->d_nm, h->d_score});
     delete h;
 }
 
@@ -482,59 +361,45 @@ int32_t lvi_fmat_find(lvi_fmat* h, const float* pts1_xy, const float* pts2_xy, i
     if (!h || !pts1_xy || !pts2_xy || !status_out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (n < MODEL_POINTS) return fail(LVI_ERR_INVALID_ARG, "n < 7: findFundamentalMat has no model");
     if (n > h->P) return fail(LVI_ERR_INVALID_ARG, "n > max_points");
-    return guarded(h->device, [&]() -> int32_t {
+    Io& io = h->io;
+    return guarded(io.device, [&]() -> int32_t {
         // findFundamentalMat's argument defaults
         if (threshold <= 0) threshold = 3;
         if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
-        float* xy = reinterpret_cast<float*>(h->h_in);
+        float* xy = reinterpret_cast<float*>(io.h_in);
         for (int i = 0; i < n; i++) {
             xy[4 * i] = pts1_xy[2 * i]; xy[4 * i + 1] = pts1_xy[2 * i + 1];
             xy[4 * i + 2] = pts2_xy[2 * i]; xy[4 * i + 3] = pts2_xy[2 * i + 1];
         }
-        int* sub = reinterpret_cast<int*>(h->h_in + h->off_sub);
-        double* lt = reinterpret_cast<double*>(h->h_in + h->off_log);
+        int* sub = reinterpret_cast<int*>(io.h_in + h->off_sub);
+        double* lt = reinterpret_cast<double*>(io.h_in + h->off_log);
         const int path = n == MODEL_POINTS ? LVI_FMAT_PATH_KERNEL : n < 15 ? LVI_FMAT_PATH_LMEDS : LVI_FMAT_PATH_RANSAC;
         const auto t0 = std::chrono::steady_clock::now();
-        int nsub = 0, niters0 = 1;
+        int nsub = 1, niters0 = 1;
         if (path == LVI_FMAT_PATH_KERNEL) {
             for (int k = 0; k < MODEL_POINTS; k++) sub[k] = k;
-            nsub = 1;
         } else {
-            const bool ransac = path == LVI_FMAT_PATH_RANSAC;
-            niters0 = ransac ? std::max(h->I, 1) : std::max(update_num_iters(confidence, LMEDS_OUTLIER_RATIO, h->I), 3);
-            niters0 = std::min(niters0, h->I);                 // LMeDS's floor of 3 can exceed a tiny max_iters
-            CvRng rng;
-            while (nsub < niters0 && get_subset(rng, xy, n, h->check, ransac ? RANSAC_MAX_ATTEMPTS : LMEDS_MAX_ATTEMPTS, sub + 7 * nsub)) nsub++;
-            if (ransac) for (int g = 0; g <= n; g++) lt[g] = update_log(n, g);
+            nsub = fm_sample_stream(xy, n, path == LVI_FMAT_PATH_RANSAC, h->I, confidence, h->check, sub, &niters0);
+            if (path == LVI_FMAT_PATH_RANSAC) for (int g = 0; g <= n; g++) lt[g] = update_log<MODEL_POINTS>(n, g);
         }
         const double stream_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        h->last_n = n; h->last_nsub = nsub;
-        h->last_subsets.assign(sub, sub + 7 * nsub);
+        io.record(sub, MODEL_POINTS, nsub);
 
         const float thr = (float)(threshold * threshold);
-        const double num_log = std::log(std::max(1. - std::min(std::max(confidence, 0.), 1.), DBL_MIN));
         // one upload: the points, then (if any) the subsets and the log table
         const size_t up = path == LVI_FMAT_PATH_RANSAC ? h->off_log + sizeof(double) * (n + 1) : h->off_sub + sizeof(int) * 7 * (size_t)nsub;
-        LVI_HIP(hipMemcpyAsync(h->d_in, h->h_in, up, hipMemcpyHostToDevice, h->stream));
-        const float4* d_pts = reinterpret_cast<const float4*>(h->d_in);
-        if (nsub > 0) {
-            HypArgs ha{d_pts, reinterpret_cast<const int*>(h->d_in + h->off_sub), n, path == LVI_FMAT_PATH_LMEDS ? 1 : 0, thr, h->d_F, h->d_nm, h->d_score};
-            hipLaunchKernelGGL(fmat_hyp, dim3(nsub), dim3(LVI_WAVE), sizeof(float4) * (size_t)n, h->stream, ha);
+        io.run(up, n, stream_us, status_out, info_out, [&](lvi_fmat_info* d_info, unsigned char* d_status) {
+            const float4* d_pts = reinterpret_cast<const float4*>(io.d_in);
+            if (nsub > 0) {
+                HypArgs ha{d_pts, reinterpret_cast<const int*>(io.d_in + h->off_sub), n, path == LVI_FMAT_PATH_LMEDS ? 1 : 0, thr, h->d_F, h->d_nm, h->d_score};
+                hipLaunchKernelGGL(fmat_hyp, dim3(nsub), dim3(LVI_WAVE), sizeof(float4) * (size_t)n, io.stream, ha);
+                LVI_HIP(hipGetLastError());
+            }
+            WalkArgs wa{d_pts, reinterpret_cast<const double*>(io.d_in + h->off_log), h->d_F, h->d_nm, h->d_score, n, nsub, path, niters0, num_log(confidence), thr,
+                        d_info, d_status};
+            hipLaunchKernelGGL(fmat_walk, dim3(1), dim3(LVI_WAVE), 0, io.stream, wa);
             LVI_HIP(hipGetLastError());
-        }
-        lvi_fmat_info* d_info = reinterpret_cast<lvi_fmat_info*>(h->d_out);
-        unsigned char* d_status = reinterpret_cast<unsigned char*>(h->d_out + align256(sizeof(lvi_fmat_info)));
-        WalkArgs wa{d_pts, reinterpret_cast<const double*>(h->d_in + h->off_log), h->d_F, h->d_nm, h->d_score, n, nsub, path, niters0, num_log, thr,
-                    d_info, d_status};
-        hipLaunchKernelGGL(fmat_walk, dim3(1), dim3(LVI_WAVE), 0, h->stream, wa);
-        LVI_HIP(hipGetLastError());
-        LVI_HIP(hipMemcpyAsync(h->h_out, h->d_out, align256(sizeof(lvi_fmat_info)) + (size_t)n, hipMemcpyDeviceToHost, h->stream));
-        LVI_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(status_out, h->h_out + align256(sizeof(lvi_fmat_info)), (size_t)n);
-        if (info_out) {
-            std::memcpy(info_out, h->h_out, sizeof(lvi_fmat_info));
-            info_out->stream_us = stream_us;
-        }
+        });
         return LVI_OK;
     });
 }
@@ -542,15 +407,13 @@ int32_t lvi_fmat_find(lvi_fmat* h, const float* pts1_xy, const float* pts2_xy, i
 int32_t lvi_fmat_trace(lvi_fmat* h, int32_t* subsets, int32_t* nmodels, double* F, int32_t* score, int32_t cap, int32_t* n_out)
 {
     if (!h || cap < 0) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
-    return guarded(h->device, [&]() -> int32_t {
-        const int m = std::min(cap, h->last_nsub);
-        if (n_out) *n_out = h->last_nsub;
+    return guarded(h->io.device, [&]() -> int32_t {
+        const int m = h->io.trace_subsets(subsets, MODEL_POINTS, cap, n_out);
         if (m == 0) return LVI_OK;
-        if (subsets) std::memcpy(subsets, h->last_subsets.data(), sizeof(int) * 7 * (size_t)m);
-        if (nmodels) LVI_HIP(hipMemcpyAsync(nmodels, h->d_nm, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-        if (F) LVI_HIP(hipMemcpyAsync(F, h->d_F, sizeof(double) * 27 * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-        if (score) LVI_HIP(hipMemcpyAsync(score, h->d_score, sizeof(int) * 3 * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-        LVI_HIP(hipStreamSynchronize(h->stream));
+        if (nmodels) LVI_HIP(hipMemcpyAsync(nmodels, h->d_nm, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
+        if (F) LVI_HIP(hipMemcpyAsync(F, h->d_F, sizeof(double) * 27 * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
+        if (score) LVI_HIP(hipMemcpyAsync(score, h->d_score, sizeof(int) * 3 * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
+        LVI_HIP(hipStreamSynchronize(h->io.stream));
         return LVI_OK;
     });
 }

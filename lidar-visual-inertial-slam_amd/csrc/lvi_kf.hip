@@ -246,8 +246,6 @@ __global__ __launch_bounds__(256) void kf_match_kernel(const ulonglong2* __restr
     }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 struct Slot {
     bool valid = false;
     int n_kp = 0, n_win = 0;
@@ -340,9 +338,7 @@ int32_t lvi_kf_create(int32_t device, int32_t max_width, int32_t max_height, int
             if (v[k] < -LVI_KF_PATTERN_MAX || v[k] > LVI_KF_PATTERN_MAX) return fail(LVI_ERR_INVALID_ARG, "pattern offset beyond +-24");
         pattern[i] = (v[0] & 0xFF) | ((v[1] & 0xFF) << 8) | ((v[2] & 0xFF) << 16) | ((v[3] & 0xFF) << 24);
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (const int32_t bad = check_device(device)) return bad;
     lvi_kf* h = new lvi_kf();
     h->device = device; h->W = max_width; h->H = max_height; h->K = max_keypoints; h->Wn = max_window; h->S = max_keyframes;
     h->slots.resize(max_keyframes);

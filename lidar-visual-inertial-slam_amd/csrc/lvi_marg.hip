@@ -369,9 +369,7 @@ int32_t lvi_marg_create(int32_t device, const lvi_marg_caps* caps, lvi_marg** ou
         c.max_dense_factors < 0 || c.max_dense_factors > LVI_MARG_MAX_DENSE_FACTORS || c.max_dense_rows < 0 || c.max_dense_rows > LVI_MARG_MAX_DENSE_ROWS ||
         c.max_drop_dim < 1 || c.max_drop_dim > LVI_MARG_MAX_DROP_DIM || c.max_keep_dim < 1 || c.max_keep_dim > LVI_MARG_MAX_KEEP_DIM)
         return fail(LVI_ERR_INVALID_ARG, "a capacity is outside 1..LVI_MARG_MAX_*");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (const int32_t bad = check_device(device)) return bad;
     lvi_marg* h = new lvi_marg();
     h->device = device; h->caps = c;
     lvi_marg_params_default(&h->P);

@@ -467,8 +467,6 @@ __global__ __launch_bounds__(LOOPS_THREADS) void pgo_finish(Dev d, int which)
     d.info->iterations = iters; d.info->converged = conv; d.info->max_step = last;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- the handle
@@ -613,9 +611,7 @@ int32_t lvi_pgo_create(int32_t device, int32_t max_poses, int32_t max_loops, lvi
     *out = nullptr;
     if (max_poses < 1 || max_poses > LVI_PGO_MAX_POSES) return fail(LVI_ERR_INVALID_ARG, "max_poses must be 1..LVI_PGO_MAX_POSES");
     if (max_loops < 0 || max_loops > LVI_PGO_MAX_LOOPS) return fail(LVI_ERR_INVALID_ARG, "max_loops must be 0..LVI_PGO_MAX_LOOPS");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (const int32_t bad = check_device(device)) return bad;
     lvi_pgo* h = new lvi_pgo();
     h->device = device; h->Ncap = max_poses; h->Lcap = max_loops;
     lvi_pgo_params_default(&h->P);

@@ -1,33 +1,31 @@
 // KeyFrame::PnPRANSAC's cv::solvePnPRansac(matched_3d, matched_2d_old_norm, K = I, D, rvec, t, true, 100, 10.0 / 460.0,
 // 0.99, inliers) on the GPU (keyframe.cpp:135-176; include/lvi_pnp.h; the contract is DESIGN §16).
 //
-//   host       the sample stream: cv::RNG((uint64)-1) and getSubset with modelPoints = 5 and no checkSubset (OpenCV
-//              ptsetreg.cpp) — the draws do not depend on any model, so the whole stream is known before the first
-//              hypothesis is scored (lvi_pnp_stream.hpp)
+//   host       the sample stream: getSubset with modelPoints = 5 (lvi_ransac.hpp).  The PnP callback has no checkSubset,
+//              so the first five distinct draws are the subset and getSubset never fails
 //   pnp_hyp    one wave per hypothesis: EPnP on the subset's five points (epnp.cpp compute_pose, lvi_pnp_math.hpp) in
 //              double — the 12x12 eigenproblem by round-robin Jacobi with its entries spread over the lanes, the three
 //              beta candidates on three lanes — then every lane scores the n points against the chosen pose
-//   pnp_walk   one wave replays the sequential RANSAC walk (RANSACPointSetRegistrator::run) from the counts and writes
-//              the chosen hypothesis's status
+//   pnp_walk   one wave replays the sequential RANSAC walk (lvi_ransac.hpp) from the counts and writes the chosen
+//              hypothesis's status
 //
 // Everything scored is double with -ffp-contract=off; only sqrt and division come from the math library (both IEEE-exact
 // in f64), so for the same (R, t) bits the errors are those of the host restatement.
 #include <chrono>
 #include <cfloat>
 #include <cmath>
-#include <vector>
 
-#include "lvi_dev.hpp"
+#include "lvi_ransac.hpp"
 #include "lvi_pnp_math.hpp"
-#include "lvi_pnp_stream.hpp"
 #include "../../include/lvi_pnp.h"
 
 using namespace lvi;
 using namespace lvi_pnp_math;
+using namespace lvi_ransac;
 
 namespace {
 
-constexpr int MODEL_POINTS = lvi_pnp_stream::MODEL_POINTS;
+constexpr int MODEL_POINTS = 5;
 constexpr int LD = 13;                       // row stride of the 12x12 matrices in LDS: a column walk (stride 26 banks) hits 12 distinct bank pairs
 
 struct HypArgs {
@@ -155,37 +153,21 @@ struct WalkArgs {
     unsigned char* status;
 };
 
-// RANSACUpdateNumIters(p, ep, 5, max_iters) from the precomputed log(denom)
-__device__ __forceinline__ int update_iters(double num, double ld, int max_iters)
-{
-    if (ld == HUGE_VAL) return 0;
-    return ld >= 0 || -num >= max_iters * (-ld) ? max_iters : (int)rint(num / ld);
-}
-
 __global__ __launch_bounds__(LVI_WAVE) void pnp_walk(WalkArgs a)
 {
     __shared__ int s_best;
     const int lane = threadIdx.x;
     if (lane == 0) {
-        int iter = 0, best = -1;
+        Walk w{1, -1, -1};                                     // the direct path: one iteration
         if (a.path == LVI_PNP_PATH_DIRECT) {
-            iter = 1;
-            if (a.nsub > 0 && a.has[0]) best = 0;
+            if (a.nsub > 0 && a.has[0]) w.best_iter = 0;
         } else {
-            int max_good = 0;
-            for (int niters = a.niters0; iter < niters; iter++) {
-                if (iter >= a.nsub) break;
-                if (!a.has[iter]) continue;                    // no model: skipped, but it counts as an iteration
-                const int good = a.good[iter];
-                if (good > max(max_good, MODEL_POINTS - 1)) {
-                    best = iter; max_good = good;
-                    niters = update_iters(a.num_log, a.logtab[good], niters);
-                }
-            }
+            w = ransac_walk<MODEL_POINTS>(a.has, a.good, 1, a.nsub, a.niters0, a.num_log, a.logtab);   // has: 0 or 1 model per hypothesis
         }
+        const int best = w.best_iter;
         s_best = best;
         lvi_pnp_info* o = a.info;
-        o->path = a.path; o->iters = iter; o->n_subsets = a.nsub; o->best_iter = best;
+        o->path = a.path; o->iters = w.iter; o->n_subsets = a.nsub; o->best_iter = best;
         o->which_beta = best >= 0 ? a.wb[best] : 0;
         for (int k = 0; k < 9; k++) o->R[k] = best >= 0 ? a.Rt[12 * (size_t)best + k] : 0.;
         for (int k = 0; k < 3; k++) o->t[k] = best >= 0 ? a.Rt[12 * (size_t)best + 9 + k] : 0.;
@@ -196,38 +178,22 @@ __global__ __launch_bounds__(LVI_WAVE) void pnp_walk(WalkArgs a)
     double R[9], t[3];
     for (int k = 0; k < 9; k++) R[k] = best >= 0 ? a.Rt[12 * (size_t)best + k] : 0.;
     for (int k = 0; k < 3; k++) t[k] = best >= 0 ? a.Rt[12 * (size_t)best + 9 + k] : 0.;
-    int good = 0;
-    for (int base = 0; base < a.n; base += LVI_WAVE) {
-        const int i = base + lane;
-        bool in = false;
-        if (i < a.n) {
-            if (best >= 0)
-                in = a.path == LVI_PNP_PATH_DIRECT ? true : pnp_error(R, t, a.p3[3 * i], a.p3[3 * i + 1], a.p3[3 * i + 2], a.p2[2 * i], a.p2[2 * i + 1]) <= a.thr;
-            a.status[i] = in ? 1 : 0;
-        }
-        good += __popcll(__ballot(in));
-    }
+    const int good = status_sweep(a.n, a.status, [&](int i) {
+        if (best < 0) return false;
+        return a.path == LVI_PNP_PATH_DIRECT ? true : pnp_error(R, t, a.p3[3 * i], a.p3[3 * i + 1], a.p3[3 * i + 2], a.p2[2 * i], a.p2[2 * i + 1]) <= a.thr;
+    });
     if (lane == 0) a.info->n_inliers = good;
 }
-
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- the handle
 struct lvi_pnp {
-    int device = 0, P = 0, I = 0;
-    hipStream_t stream = nullptr;
-    char* d_in = nullptr;                  // pts3d [P][3] | pts2d [P][2] | subsets [I][5] | logtab [P + 1]
-    char* h_in = nullptr;                  // pinned mirror of d_in
-    char* d_out = nullptr;                 // info | status [P]
-    char* h_out = nullptr;
+    int P = 0, I = 0;
+    Io io;                                 // d_in: pts3d [P][3] | pts2d [P][2] | subsets [I][5] | logtab [P + 1]; d_out: info | status [P]
     double* d_Rt = nullptr;                // [I][12]
     int *d_has = nullptr, *d_good = nullptr, *d_wb = nullptr;
-    size_t off_p2 = 0, off_sub = 0, off_log = 0, in_bytes = 0, out_bytes = 0;
-    // last call
-    int last_nsub = 0;
-    std::vector<int> last_subsets;
+    size_t off_p2 = 0, off_sub = 0, off_log = 0;
 };
 
 extern "C" {
@@ -240,28 +206,16 @@ int32_t lvi_pnp_create(int32_t device, int32_t max_points, int32_t max_iters, lv
     *out = nullptr;
     if (max_points < MODEL_POINTS || max_points > LVI_PNP_MAX_POINTS) return fail(LVI_ERR_INVALID_ARG, "max_points must be 5..LVI_PNP_MAX_POINTS");
     if (max_iters < 1 || max_iters > LVI_PNP_MAX_ITERS) return fail(LVI_ERR_INVALID_ARG, "max_iters must be 1..LVI_PNP_MAX_ITERS");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
     lvi_pnp* h = new lvi_pnp();
-    h->device = device; h->P = max_points; h->I = max_iters;
+    h->P = max_points; h->I = max_iters;
     h->off_p2 = align256(sizeof(float) * 3 * (size_t)h->P);
     h->off_sub = h->off_p2 + align256(sizeof(float) * 2 * (size_t)h->P);
     h->off_log = h->off_sub + align256(sizeof(int) * MODEL_POINTS * (size_t)h->I);
-    h->in_bytes = h->off_log + align256(sizeof(double) * ((size_t)h->P + 1));
-    h->out_bytes = align256(sizeof(lvi_pnp_info)) + align256((size_t)h->P);
-    const int32_t st = guarded(h->device, [&]() -> int32_t {
-        LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        LVI_HIP(hipMalloc((void**)&h->d_in, h->in_bytes));
-        LVI_HIP(hipMalloc((void**)&h->d_out, h->out_bytes));
-        LVI_HIP(hipMalloc((void**)&h->d_Rt, sizeof(double) * 12 * (size_t)h->I));
-        LVI_HIP(hipMalloc((void**)&h->d_has, sizeof(int) * (size_t)h->I));
-        LVI_HIP(hipMalloc((void**)&h->d_good, sizeof(int) * (size_t)h->I));
-        LVI_HIP(hipMalloc((void**)&h->d_wb, sizeof(int) * (size_t)h->I));
-        LVI_HIP(hipHostMalloc((void**)&h->h_in, h->in_bytes, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_out, h->out_bytes, hipHostMallocDefault));
-        return LVI_OK;
-    });
+    const int32_t st = h->io.open(device, h->off_log + align256(sizeof(double) * ((size_t)h->P + 1)), align256(sizeof(lvi_pnp_info)) + align256((size_t)h->P),
+                                  {{(void**)&h->d_Rt, sizeof(double) * 12 * (size_t)h->I},
+                                   {(void**)&h->d_has, sizeof(int) * (size_t)h->I},
+                                   {(void**)&h->d_good, sizeof(int) * (size_t)h->I},
+                                   {(void**)&h->d_wb, sizeof(int) * (size_t)h->I}});
     if (st != LVI_OK) { lvi_pnp_destroy(h); return st; }
     *out = h;
     return LVI_OK;
@@ -270,17 +224,7 @@ int32_t lvi_pnp_create(int32_t device, int32_t max_points, int32_t max_iters, lv
 void lvi_pnp_destroy(lvi_pnp* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_out) (void)hipFree(h->d_out);
-    if (h->d_Rt) (void)hipFree(h->d_Rt);
-    if (h->d_has) (void)hipFree(h->d_has);
-    if (h->d_good) (void)hipFree(h->d_good);
-    if (h->d_wb) (void)hipFree(h->d_wb);
-    if (h->h_in) (void)hipHostFree(h->h_in);
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->io.close({h->d_Rt, h->d_has, h->d_good, h->d_wb});
     delete h;
 }
 
@@ -290,11 +234,12 @@ int32_t lvi_pnp_solve(lvi_pnp* h, const float* pts3d_xyz, const float* pts2d_xy,
     if (!h || !pts3d_xyz || !pts2d_xy || !status_out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (n < MODEL_POINTS) return fail(LVI_ERR_INVALID_ARG, "n < 5: the P3P path of solvePnPRansac is not restated");
     if (n > h->P) return fail(LVI_ERR_INVALID_ARG, "n > max_points");
-    return guarded(h->device, [&]() -> int32_t {
-        std::memcpy(h->h_in, pts3d_xyz, sizeof(float) * 3 * (size_t)n);
-        std::memcpy(h->h_in + h->off_p2, pts2d_xy, sizeof(float) * 2 * (size_t)n);
-        int* sub = reinterpret_cast<int*>(h->h_in + h->off_sub);
-        double* lt = reinterpret_cast<double*>(h->h_in + h->off_log);
+    Io& io = h->io;
+    return guarded(io.device, [&]() -> int32_t {
+        std::memcpy(io.h_in, pts3d_xyz, sizeof(float) * 3 * (size_t)n);
+        std::memcpy(io.h_in + h->off_p2, pts2d_xy, sizeof(float) * 2 * (size_t)n);
+        int* sub = reinterpret_cast<int*>(io.h_in + h->off_sub);
+        double* lt = reinterpret_cast<double*>(io.h_in + h->off_log);
         const int path = n == MODEL_POINTS ? LVI_PNP_PATH_DIRECT : LVI_PNP_PATH_RANSAC;
         const auto t0 = std::chrono::steady_clock::now();
         int nsub = 1;
@@ -302,36 +247,26 @@ int32_t lvi_pnp_solve(lvi_pnp* h, const float* pts3d_xyz, const float* pts2d_xy,
             for (int k = 0; k < MODEL_POINTS; k++) sub[k] = k;
             for (int g = 0; g <= n; g++) lt[g] = 0.;                   // the walk does not read the table on this path
         } else {
-            nsub = lvi_pnp_stream::sample_stream(n, h->I, sub);
-            lvi_pnp_stream::update_log_table(n, lt);
+            nsub = sample_stream<MODEL_POINTS>(n, h->I, 1, [](const int32_t*) { return true; }, sub);
+            for (int g = 0; g <= n; g++) lt[g] = update_log<MODEL_POINTS>(n, g);
         }
         const double stream_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        h->last_nsub = nsub;
-        h->last_subsets.assign(sub, sub + MODEL_POINTS * (size_t)nsub);
+        io.record(sub, MODEL_POINTS, nsub);
 
         const float thr_param = (float)threshold;                      // solvePnPRansac's `float reprojectionError`
         const float thr = (float)((double)thr_param * thr_param);
-        const double num_log = std::log(std::max(1. - std::min(std::max(confidence, 0.), 1.), DBL_MIN));
         // one upload: points, subsets, and the log table
-        LVI_HIP(hipMemcpyAsync(h->d_in, h->h_in, h->off_log + sizeof(double) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
-        const float* d_p3 = reinterpret_cast<const float*>(h->d_in);
-        const float* d_p2 = reinterpret_cast<const float*>(h->d_in + h->off_p2);
-        HypArgs ha{d_p3, d_p2, reinterpret_cast<const int*>(h->d_in + h->off_sub), n, thr, h->d_Rt, h->d_has, h->d_good, h->d_wb};
-        hipLaunchKernelGGL(pnp_hyp, dim3(nsub), dim3(LVI_WAVE), 0, h->stream, ha);
-        LVI_HIP(hipGetLastError());
-        lvi_pnp_info* d_info = reinterpret_cast<lvi_pnp_info*>(h->d_out);
-        unsigned char* d_status = reinterpret_cast<unsigned char*>(h->d_out + align256(sizeof(lvi_pnp_info)));
-        WalkArgs wa{d_p3, d_p2, reinterpret_cast<const double*>(h->d_in + h->off_log), h->d_Rt, h->d_has, h->d_good, h->d_wb, n, nsub, path, h->I, num_log, thr,
-                    d_info, d_status};
-        hipLaunchKernelGGL(pnp_walk, dim3(1), dim3(LVI_WAVE), 0, h->stream, wa);
-        LVI_HIP(hipGetLastError());
-        LVI_HIP(hipMemcpyAsync(h->h_out, h->d_out, align256(sizeof(lvi_pnp_info)) + (size_t)n, hipMemcpyDeviceToHost, h->stream));
-        LVI_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(status_out, h->h_out + align256(sizeof(lvi_pnp_info)), (size_t)n);
-        if (info_out) {
-            std::memcpy(info_out, h->h_out, sizeof(lvi_pnp_info));
-            info_out->stream_us = stream_us;
-        }
+        io.run(h->off_log + sizeof(double) * ((size_t)n + 1), n, stream_us, status_out, info_out, [&](lvi_pnp_info* d_info, unsigned char* d_status) {
+            const float* d_p3 = reinterpret_cast<const float*>(io.d_in);
+            const float* d_p2 = reinterpret_cast<const float*>(io.d_in + h->off_p2);
+            HypArgs ha{d_p3, d_p2, reinterpret_cast<const int*>(io.d_in + h->off_sub), n, thr, h->d_Rt, h->d_has, h->d_good, h->d_wb};
+            hipLaunchKernelGGL(pnp_hyp, dim3(nsub), dim3(LVI_WAVE), 0, io.stream, ha);
+            LVI_HIP(hipGetLastError());
+            WalkArgs wa{d_p3, d_p2, reinterpret_cast<const double*>(io.d_in + h->off_log), h->d_Rt, h->d_has, h->d_good, h->d_wb, n, nsub, path, h->I, num_log(confidence), thr,
+                        d_info, d_status};
+            hipLaunchKernelGGL(pnp_walk, dim3(1), dim3(LVI_WAVE), 0, io.stream, wa);
+            LVI_HIP(hipGetLastError());
+        });
         return LVI_OK;
     });
 }
@@ -339,15 +274,13 @@ int32_t lvi_pnp_solve(lvi_pnp* h, const float* pts3d_xyz, const float* pts2d_xy,
 int32_t lvi_pnp_trace(lvi_pnp* h, int32_t* subsets, int32_t* has_model, double* Rt, int32_t* good, int32_t cap, int32_t* n_out)
 {
     if (!h || cap < 0) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
-    return guarded(h->device, [&]() -> int32_t {
-        const int m = std::min(cap, h->last_nsub);
-        if (n_out) *n_out = h->last_nsub;
+    return guarded(h->io.device, [&]() -> int32_t {
+        const int m = h->io.trace_subsets(subsets, MODEL_POINTS, cap, n_out);
         if (m == 0) return LVI_OK;
-        if (subsets) std::memcpy(subsets, h->last_subsets.data(), sizeof(int) * MODEL_POINTS * (size_t)m);
-        if (has_model) LVI_HIP(hipMemcpyAsync(has_model, h->d_has, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-        if (Rt) LVI_HIP(hipMemcpyAsync(Rt, h->d_Rt, sizeof(double) * 12 * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-        if (good) LVI_HIP(hipMemcpyAsync(good, h->d_good, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, h->stream));
-        LVI_HIP(hipStreamSynchronize(h->stream));
+        if (has_model) LVI_HIP(hipMemcpyAsync(has_model, h->d_has, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
+        if (Rt) LVI_HIP(hipMemcpyAsync(Rt, h->d_Rt, sizeof(double) * 12 * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
+        if (good) LVI_HIP(hipMemcpyAsync(good, h->d_good, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
+        LVI_HIP(hipStreamSynchronize(h->io.stream));
         return LVI_OK;
     });
 }

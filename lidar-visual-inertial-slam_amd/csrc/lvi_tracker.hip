@@ -1372,9 +1372,7 @@ int32_t lvi_tracker_create(const lvi_tracker_params* p, int32_t device, lvi_trac
 {
     if (!p || !out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (const int32_t bad = check_tracker_params(p)) return bad;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (const int32_t bad = check_device(device)) return bad;
     lvi_tracker* t = new lvi_tracker();
     t->P = *p; t->device = device;
     { const char* e = getenv("LVI_GFTT_RADIX"); t->gftt_force_radix = e && e[0] == '1'; }
@@ -1700,9 +1698,7 @@ int32_t lvi_tbatch_create(const lvi_tracker_params* p, int32_t slots, int32_t de
     if (!p || !out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (slots < 1 || slots > LVI_TRACKER_MAX_BATCH) return fail(LVI_ERR_INVALID_ARG, "slots must be 1..LVI_TRACKER_MAX_BATCH");
     if (const int32_t bad = check_tracker_params(p)) return bad;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (const int32_t bad = check_device(device)) return bad;
     lvi_tbatch* b = new lvi_tbatch();
     b->P = *p; b->device = device; b->S = slots;
     const char* e = getenv("LVI_GFTT_RADIX");

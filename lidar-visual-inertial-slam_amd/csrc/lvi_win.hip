@@ -667,9 +667,7 @@ int32_t lvi_win_create(int32_t device, const lvi_win_caps* caps, lvi_win** out)
         c.max_eliminated < 0 || c.max_eliminated > LVI_WIN_MAX_ELIMINATED || c.max_imu < 0 || c.max_imu > LVI_WIN_MAX_IMU ||
         c.max_prior_rows < 0 || c.max_prior_rows > LVI_WIN_MAX_PRIOR_ROWS || c.max_dim < 1 || c.max_dim > LVI_WIN_MAX_DIM)
         return fail(LVI_ERR_INVALID_ARG, "a capacity is outside its range 0 or 1..LVI_WIN_MAX_*");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(LVI_ERR_NO_DEVICE, "no HIP device: the HIP path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(LVI_ERR_NO_DEVICE, "device index out of range");
+    if (const int32_t bad = check_device(device)) return bad;
     lvi_win* h = new lvi_win();
     h->device = device; h->caps = c;
     lvi_win_params_default(&h->P);

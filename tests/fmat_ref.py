@@ -53,9 +53,12 @@ def have_collinear(xy):
     return False
 
 
-def get_subset(rng, p1, p2, n, check, max_attempts):
-    """getSubset: draw 7 distinct indices (redrawing duplicates), then checkSubset; None after max_attempts rejections"""
+def get_subset(rng, p1, p2, n, check, max_attempts, attempts=None):
+    """getSubset: draw 7 distinct indices (redrawing duplicates), then checkSubset; None after max_attempts rejections.
+    attempts: a one-element list that counts the subsets drawn"""
     for _ in range(max_attempts):
+        if attempts is not None:
+            attempts[0] += 1
         idx = []
         for _i in range(MODEL_POINTS):
             k = rng.uniform(0, n)
@@ -308,7 +311,7 @@ def bits_to_f32(b):
     return struct.unpack("<f", struct.pack("<i", int(b)))[0]
 
 
-def sample_stream(p1, p2, n, path, max_iters, confidence, check=1):
+def sample_stream(p1, p2, n, path, max_iters, confidence, check=1, attempts=None):
     if path == "kernel":
         return [list(range(7))], 1
     ransac = path == "ransac"
@@ -317,7 +320,7 @@ def sample_stream(p1, p2, n, path, max_iters, confidence, check=1):
     rng = CvRng()
     subs = []
     while len(subs) < niters0:
-        s = get_subset(rng, p1, p2, n, check, RANSAC_MAX_ATTEMPTS if ransac else LMEDS_MAX_ATTEMPTS)
+        s = get_subset(rng, p1, p2, n, check, RANSAC_MAX_ATTEMPTS if ransac else LMEDS_MAX_ATTEMPTS, attempts)
         if s is None:
             break
         subs.append(s)

@@ -187,3 +187,119 @@ def test_lmeds_medians_below_fourteen_points_are_rounding_noise():
     assert not R.lmeds_rounding_decided("lmeds", 8, (1, 1), (0, 0), sc, sc)
     assert not R.lmeds_rounding_decided("lmeds", 14, (1, 1), (0, 0), sc, np.array([[5, 0, 0], [7, 8, 0]]))
     assert not R.lmeds_rounding_decided("ransac", 8, (1, 1), (0, 0), sc, np.array([[5, 0, 0], [7, 8, 0]]))
+
+
+# ---- the host half of csrc/lvi_ransac.hpp under the host sanitizers ---------------------------------------------
+DRIVER = r"""
+// stand-alone driver of the 7-point sample stream of lvi_fmat_find (csrc/lvi_ransac.hpp, no HIP)
+//   driver FILE n lmeds|ransac max_iters confidence check      FILE: n x (x1 y1 x2 y2) float
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "lvi_ransac.hpp"
+using namespace lvi_ransac;
+
+int main(int argc, char** argv)
+{
+    if (argc < 7) return 1;
+    const int n = std::atoi(argv[2]), max_iters = std::atoi(argv[4]), check = std::atoi(argv[6]);
+    const bool ransac = !std::strcmp(argv[3], "ransac");
+    const double confidence = std::atof(argv[5]);
+    std::vector<float> xy(4 * (size_t)n);
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f || std::fread(xy.data(), 4, xy.size(), f) != xy.size()) return 2;
+    std::fclose(f);
+    // as lvi_fmat_find calls it, into the room a handle of max_iters has and no more
+    std::vector<int32_t> sub(7 * (size_t)max_iters), again(sub.size());
+    int niters0 = 0;
+    const int nsub = fm_sample_stream(xy.data(), n, ransac, max_iters, confidence, check, sub.data(), &niters0);
+    // the same stream once more through a predicate that counts the subsets getSubset drew
+    long attempts = 0;
+    const int nsub2 = sample_stream<7>(n, niters0, ransac ? FM_RANSAC_MAX_ATTEMPTS : FM_LMEDS_MAX_ATTEMPTS,
+                                       [&](const int32_t* idx) { attempts++; return fm_check_subset(xy.data(), idx, check); }, again.data());
+    if (nsub2 != nsub || std::memcmp(sub.data(), again.data(), sizeof(int32_t) * 7 * (size_t)nsub)) return 3;
+    std::printf("niters0 %d\nattempts %ld\n", niters0, attempts);
+    for (int h = 0; h < nsub; h++) {
+        std::printf("sub");
+        for (int k = 0; k < 7; k++) std::printf(" %d", sub[7 * h + k]);
+        std::printf("\n");
+    }
+    const int gs[5] = {0, 1, n / 2, n - 1, n};
+    for (int g : gs) std::printf("log %d %a\n", g, update_log<7>(n, g));
+    return 0;
+}
+"""
+
+
+def _collinear40():
+    k = np.arange(40)
+    p1 = np.c_[50 + 8 * k, 100 + 2 * k].astype(np.float32)               # test_collinear_set_gives_no_model_and_the_switch's points
+    return p1, p1 + np.float32(3)
+
+
+def _stream_cases():
+    tv = lambda n, **kw: R.two_view(n, 0.3, 0.3, seed=n, **kw)[:2]
+    return [("lmeds8", tv(8), 1000, 1), ("lmeds14", tv(14), 1000, 1), ("ransac15", tv(15), 1000, 1), ("ransac150", tv(150), 1000, 1),
+            ("duplicates150", tv(150, kind="duplicates"), 1000, 1), ("collinear40", _collinear40(), 1000, 1), ("collinear40_unchecked", _collinear40(), 1000, 0),
+            ("lmeds8_max1", tv(8), 1, 1), ("lmeds8_max2", tv(8), 2, 1), ("ransac2500", tv(2500), 1000, 1)]
+
+
+@pytest.fixture(scope="module")
+def stream_drivers(pkg, tmp_path_factory):
+    d = tmp_path_factory.mktemp("fmat_stream")
+    (d / "driver.cpp").write_text(DRIVER)
+    out = {}
+    for which, flags in (("plain", []), ("san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])):
+        out[which] = str(d / which)
+        r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-ffp-contract=off", *flags, "-I" + os.path.join(pkg.PKG_DIR, "csrc"), "-o", out[which],
+                            str(d / "driver.cpp")], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+    return out
+
+
+@pytest.fixture(scope="module")
+def stream_wants():
+    """fmat_ref.sample_stream per case, computed once for both builds -> (subsets, niters0, attempts)"""
+    out = {}
+    for name, (p1, p2), max_iters, check in _stream_cases():
+        attempts = [0]
+        subs, niters0 = R.sample_stream(p1, p2, len(p1), R.choose_path(len(p1)), max_iters, 0.99, check, attempts)
+        out[name] = (subs, niters0, attempts[0])
+    return out
+
+
+@pytest.mark.parametrize("which", ["plain", "san"])
+def test_seven_point_stream_equals_the_restatement(stream_drivers, stream_wants, tmp_path, which):
+    """csrc/lvi_ransac.hpp as lvi_fmat_find calls it, run as a child process: the subsets, the count asked for and the
+    number of subsets getSubset drew are fmat_ref.sample_stream's, integer for integer; update_log<7> gives
+    fmat_ref.update_num_iters"""
+    seen = {}
+    for name, (p1, p2), max_iters, check in _stream_cases():
+        n = len(p1)
+        path = R.choose_path(n)
+        (tmp_path / "xy.bin").write_bytes(np.c_[p1, p2].astype(np.float32).tobytes())
+        r = subprocess.run([stream_drivers[which], str(tmp_path / "xy.bin"), str(n), path, str(max_iters), "0.99", str(check)], capture_output=True, text=True)
+        assert r.returncode == 0, (name, r.stdout[-300:] + r.stderr)
+        lines = [l.split() for l in r.stdout.split("\n") if l]
+        subs = [list(map(int, l[1:])) for l in lines if l[0] == "sub"]
+        niters0 = [int(l[1]) for l in lines if l[0] == "niters0"]
+        attempts = [int(l[1]) for l in lines if l[0] == "attempts"]
+        logs = {int(l[1]): float.fromhex(l[2]) for l in lines if l[0] == "log"}
+        want_subs, want_niters0, want_attempts = stream_wants[name]
+        assert subs == want_subs and niters0 == [want_niters0] and attempts == [want_attempts], name
+        seen[name] = (len(subs), niters0[0], attempts[0])
+        assert sorted(logs) == sorted({0, 1, n // 2, n - 1, n}) and logs[n] == float("inf")   # ep = 0: denom < DBL_MIN
+        assert R.update_num_iters(0.99, 0.0, 7, 1000) == 0
+        num = np.log(max(1.0 - 0.99, R.DBL_MIN))
+        for g in (0, 1, n // 2, n - 1):
+            # recomputed from the table as the device walk does
+            got = 1000 if logs[g] >= 0 or -num >= 1000 * -logs[g] else int(round(num / logs[g]))
+            assert got == R.update_num_iters(0.99, (n - g) / n, 7, 1000), (name, g)
+    # what each case is there for
+    assert seen["lmeds8"][:2] == seen["lmeds14"][:2] == (300, 300)                       # update_num_iters(0.99, 0.45, 7, I), floor 3
+    assert seen["ransac15"][:2] == seen["ransac150"][:2] == seen["ransac2500"][:2] == (1000, 1000)
+    assert seen["duplicates150"][0] == 1000 and seen["duplicates150"][2] > 1000         # checkSubset rejected subsets inside the stream
+    assert seen["collinear40"] == (0, 1000, R.RANSAC_MAX_ATTEMPTS)                      # no subset, and only after every attempt
+    assert seen["collinear40_unchecked"] == (1000, 1000, 1000)
+    assert seen["lmeds8_max1"][:2] == (1, 1) and seen["lmeds8_max2"][:2] == (2, 2)       # min(niters0, I) under LMeDS's floor of 3

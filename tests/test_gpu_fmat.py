@@ -188,6 +188,31 @@ def test_collinear_set_gives_no_model_and_the_switch(pkg, fr):
         fr.set_check_subset(1)
 
 
+@pytest.mark.parametrize("max_iters", [1, 2, 1000])
+def test_iteration_limits(pkg, hip, max_iters):
+    """handles with room for 1, 2 and 1000 hypotheses, on LMeDS (n = 8, whose floor of 3 iterations exceeds the first two)
+    and RANSAC (n = 16): only what is exact by construction — the stream, the walk replayed on the device's own counts,
+    the status on the device's own F"""
+    h = pkg.FundamentalRansac(hip, max_points=64, max_iters=max_iters)
+    try:
+        for n in (8, 16):
+            p1, p2, _, _ = R.two_view(n, 0.3, 0.3, seed=500 + n)
+            st, info = h.find(p1, p2, 1.0, with_info=True)
+            tr = h.trace()
+            path = R.choose_path(n)
+            subs, niters0 = R.sample_stream(p1, p2, n, path, max_iters, 0.99)
+            assert info["path"] == path and info["n_subsets"] == len(subs) == len(tr["subsets"])
+            np.testing.assert_array_equal(tr["subsets"], np.array(subs, np.int32).reshape(-1, 7))
+            it, bi, br, bmed = R.walk(path, n, niters0, info["n_subsets"], tr["nmodels"], tr["score"], 0.99)
+            assert (it, bi, br) == (info["iters"], info["best_iter"], info["best_root"]) and it <= niters0 <= max_iters
+            Fd = tr["F"][bi, br].ravel() if bi >= 0 else np.zeros(9)
+            np.testing.assert_array_equal(info["F"].ravel(), Fd)
+            np.testing.assert_array_equal(st, R.final_mask(path, n, Fd, bi, bmed, p1, p2, 1.0))
+            assert info["n_inliers"] == int(st.sum())
+    finally:
+        h.close()
+
+
 def test_error_paths(pkg, hip):
     h = pkg.FundamentalRansac(hip, max_points=64, max_iters=100)
     p1, p2, _, _ = R.two_view(65, seed=1)

@@ -224,7 +224,7 @@ DRIVER = r"""
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "lvi_pnp_stream.hpp"
+#include "lvi_ransac.hpp"
 #include "lvi_pnp_math.hpp"
 using namespace lvi_pnp_math;
 
@@ -267,10 +267,9 @@ int main(int argc, char** argv)
     if (argc >= 4 && !std::strcmp(argv[1], "stream")) {
         const int n = std::atoi(argv[2]), count = std::atoi(argv[3]);
         std::vector<int32_t> sub(5 * (size_t)(count > 0 ? count : 0) + 5);
-        const int got = lvi_pnp_stream::sample_stream(n, count, sub.data());
+        const int got = lvi_ransac::sample_stream<5>(n, count, 1, [](const int32_t*) { return true; }, sub.data());   // as lvi_pnp_solve calls it
         for (int h = 0; h < got; h++) std::printf("%d %d %d %d %d\n", sub[5 * h], sub[5 * h + 1], sub[5 * h + 2], sub[5 * h + 3], sub[5 * h + 4]);
-        std::vector<double> lt(n > 0 ? n + 1 : 1);
-        if (n >= 5) { lvi_pnp_stream::update_log_table(n, lt.data()); for (int g = 0; g <= n; g++) std::printf("log %a\n", lt[g]); }
+        if (n >= 5) for (int g = 0; g <= n; g++) std::printf("log %a\n", lvi_ransac::update_log<5>(n, g));
         return 0;
     }
     if (argc >= 3 && !std::strcmp(argv[1], "epnp")) {
@@ -319,7 +318,7 @@ def drivers(pkg, tmp_path_factory):
 
 @pytest.mark.parametrize("which", ["plain", "san"])
 def test_stream_header_equals_the_restatement(drivers, which):
-    """csrc/lvi_pnp_stream.hpp: the subsets and the log table the device walk reads"""
+    """csrc/lvi_ransac.hpp with modelPoints = 5: the subsets and the log table the device walk reads"""
     for n, count in ((5, 3), (6, 100), (26, 100), (150, 100), (2048, 1024), (4, 10)):
         r = subprocess.run([drivers[which], "stream", str(n), str(count)], capture_output=True, text=True)
         assert r.returncode == 0, r.stdout + r.stderr
