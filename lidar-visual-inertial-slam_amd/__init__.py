@@ -8,12 +8,13 @@ import it through ``__graft_entry__.import_package()`` (module name
 """
 import os
 
-from . import _abi, bow, config, depth, fmat, gmap, host_api, kf, loop, marg, pgo, pnp, replay, synth, tbatch, win  # noqa: F401
+from . import _abi, bow, config, depth, fmat, fmatb, gmap, host_api, kf, loop, marg, pgo, pnp, replay, synth, tbatch, win  # noqa: F401
 from ._abi import Library, LviError, PT_DTYPE, LIVOX_DTYPE  # noqa: F401
 from .lidar import LidarHotpath, default_params  # noqa: F401
 from .tracker import TrackerHotpath, default_tracker_params  # noqa: F401
 from .depth import DepthRegister  # noqa: F401
 from .fmat import FundamentalRansac  # noqa: F401
+from .fmatb import FundamentalRansacBatch  # noqa: F401
 from .gmap import GlobalMap  # noqa: F401
 from .loop import LoopIcp  # noqa: F401
 from .kf import KeyframeDescriber  # noqa: F401

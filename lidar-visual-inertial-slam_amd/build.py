@@ -16,7 +16,7 @@ def _stale():
         return True
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    deps += [os.path.join(CSRC, "..", "..", "include", h) for h in ("lvi_hotpath.h", "lvi_depth.h", "lvi_fmat.h", "lvi_gmap.h", "lvi_loop.h", "lvi_kf.h", "lvi_bow.h", "lvi_pnp.h", "lvi_tbatch.h", "lvi_pgo.h", "lvi_pgo_gps.h", "lvi_marg.h", "lvi_win.h")]
+    deps += [os.path.join(CSRC, "..", "..", "include", h) for h in ("lvi_hotpath.h", "lvi_depth.h", "lvi_fmat.h", "lvi_fmatb.h", "lvi_gmap.h", "lvi_loop.h", "lvi_kf.h", "lvi_bow.h", "lvi_pnp.h", "lvi_tbatch.h", "lvi_pgo.h", "lvi_pgo_gps.h", "lvi_marg.h", "lvi_win.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

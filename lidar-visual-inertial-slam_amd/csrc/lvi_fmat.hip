@@ -8,12 +8,16 @@
 //              from the counts / medians and writes the chosen model's status
 //
 // Everything scored is double with -ffp-contract=off: for the same F bits the errors are those of the host restatement.
+//
+// The batched handle (include/lvi_fmatb.h) runs the same two bodies for up to LVI_TRACKER_MAX_BATCH point sets
+// on one stream: fmatb_hyp once per active slot, enqueued while the host draws the next slot's stream, then fmatb_walk once
+// with one wave per slot, one download and one wait.
 #include <chrono>
 #include <cfloat>
 #include <cmath>
 
 #include "lvi_ransac.hpp"
-#include "../../include/lvi_fmat.h"
+#include "../../include/lvi_fmatb.h"   // includes lvi_fmat.h
 
 using namespace lvi;
 using namespace lvi_ransac;
@@ -144,14 +148,15 @@ __device__ int seven_point_roots(double* f1, const double* f2, double* F)
     return n;
 }
 
-__global__ __launch_bounds__(LVI_WAVE) void fmat_hyp(HypArgs a)
+// One hypothesis of one point-pair set (workgroup h of the set's launch): the body of fmat_hyp and fmatb_hyp
+__device__ __forceinline__ void hyp_body(const HypArgs& a, int h)
 {
     extern __shared__ float4 sp[];                             // the n correspondences
     __shared__ double sa[7 * 9];                               // the 7x9 system
     __shared__ double sF[27];
     __shared__ int s_piv[7], s_r, s_c, s_nm;
     __shared__ unsigned s_err[64];
-    const int h = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     for (int i = lane; i < a.n; i += LVI_WAVE) sp[i] = a.pts[i];
     __syncthreads();
     // rows (x1 x0, x1 y0, x1, y1 x0, y1 y0, y1, x0, y0, 1) of run7Point: (m2, 1)' F (m1, 1) = 0
@@ -247,6 +252,10 @@ __global__ __launch_bounds__(LVI_WAVE) void fmat_hyp(HypArgs a)
     }
 }
 
+__global__ __launch_bounds__(LVI_WAVE) void fmat_hyp(HypArgs a) { hyp_body(a, blockIdx.x); }
+// a slot of lvi_fmatb_find: the same body on the slot's regions of the handle's buffers, one launch per active slot
+__global__ __launch_bounds__(LVI_WAVE) void fmatb_hyp(HypArgs a) { hyp_body(a, blockIdx.x); }
+
 struct WalkArgs {
     const float4* pts;
     const double* logtab;   // [n + 1] log(1 - (1 - ep)^7) per goodCount, +inf = denom < DBL_MIN
@@ -260,7 +269,8 @@ struct WalkArgs {
     unsigned char* status;
 };
 
-__global__ __launch_bounds__(LVI_WAVE) void fmat_walk(WalkArgs a)
+// The walk and the status of one point-pair set by one wave: the body of fmat_walk and fmatb_walk
+__device__ __forceinline__ void walk_body(const WalkArgs& a)
 {
     __shared__ int s_best;
     __shared__ float s_thr;
@@ -307,15 +317,132 @@ __global__ __launch_bounds__(LVI_WAVE) void fmat_walk(WalkArgs a)
     if (lane == 0) a.info->n_inliers = good;
 }
 
+__global__ __launch_bounds__(LVI_WAVE) void fmat_walk(WalkArgs a) { walk_body(a); }
+
+// The scalars of a slot's WalkArgs: the record at the head of the slot's input region, uploaded with the slot's points
+struct WalkRec {
+    int n, nsub, path, niters0;
+    double num_log;
+    float thr;
+};
+
+// What the slots of a batched handle share: the two blocks, the per-hypothesis arrays of all slots and the strides that
+// lead to slot s's part of each.  The record holds no pointer: a pointer read from memory has no known address space and
+// every load through it would be a flat load; pointers built from these kernel arguments load as fmat_walk's do.
+struct WalkBatch {
+    const char* d_in;       // [S] x (WalkRec | pts | subsets | logtab)
+    char* d_out;            // [S] x (info | status)
+    const double* F;        // [S][I][27]
+    const int* nmodels;     // [S][I]
+    const int* score;       // [S][I][3]
+    size_t in_stride, off_set, off_log, out_stride, off_status;
+    int I;
+    unsigned active;        // bit s: slot s takes part in this call
+};
+
+// All slots of lvi_fmatb_find in one launch: workgroup s walks slot s; a slot that sits out returns at once
+__global__ __launch_bounds__(LVI_WAVE) void fmatb_walk(WalkBatch b)
+{
+    const size_t s = blockIdx.x;
+    if (!((b.active >> s) & 1u)) return;
+    const char* in = b.d_in + b.in_stride * s;
+    char* out = b.d_out + b.out_stride * s;
+    const WalkRec r = *reinterpret_cast<const WalkRec*>(in);
+    const WalkArgs a{reinterpret_cast<const float4*>(in + b.off_set), reinterpret_cast<const double*>(in + b.off_set + b.off_log),
+                     b.F + 27 * (size_t)b.I * s, b.nmodels + (size_t)b.I * s, b.score + 3 * (size_t)b.I * s,
+                     r.n, r.nsub, r.path, r.niters0, r.num_log, r.thr,
+                     reinterpret_cast<lvi_fmat_info*>(out), reinterpret_cast<unsigned char*>(out + b.off_status)};
+    walk_body(a);
+}
+
+// ---------------------------------------------------------------------------------------------- host: one point set
+// the input region of one point set: pts [P] float4 | subsets [I][7] | logtab [P + 1]; its output region: info | status [P]
+struct Layout {
+    size_t off_sub = 0, off_log = 0, in_bytes = 0, off_status = 0, out_bytes = 0;
+    void set(int P, int I)
+    {
+        off_sub = align256(sizeof(float4) * (size_t)P);
+        off_log = off_sub + align256(sizeof(int) * 7 * (size_t)I);
+        in_bytes = off_log + align256(sizeof(double) * ((size_t)P + 1));
+        off_status = align256(sizeof(lvi_fmat_info));
+        out_bytes = off_status + align256((size_t)P);
+    }
+};
+
+// what the host half of a call leaves in a point set's input region
+struct Staged {
+    int n, path, nsub, niters0;
+    float thr;              // (float)(threshold * threshold)
+    double num_log;
+    double stream_us;
+    size_t up;              // bytes of the region to upload: the points, then (if any) the subsets and the log table
+};
+
+// findFundamentalMat's argument defaults, the interleaved points, the path rule, the sample stream and the log table
+Staged stage_set(char* h_in, const Layout& L, int I, int check, const float* pts1_xy, const float* pts2_xy, int n, double threshold, double confidence, Trace& tr)
+{
+    if (threshold <= 0) threshold = 3;
+    if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
+    float* xy = reinterpret_cast<float*>(h_in);
+    for (int i = 0; i < n; i++) {
+        xy[4 * i] = pts1_xy[2 * i]; xy[4 * i + 1] = pts1_xy[2 * i + 1];
+        xy[4 * i + 2] = pts2_xy[2 * i]; xy[4 * i + 3] = pts2_xy[2 * i + 1];
+    }
+    int* sub = reinterpret_cast<int*>(h_in + L.off_sub);
+    double* lt = reinterpret_cast<double*>(h_in + L.off_log);
+    Staged g{};
+    g.n = n;
+    g.path = n == MODEL_POINTS ? LVI_FMAT_PATH_KERNEL : n < 15 ? LVI_FMAT_PATH_LMEDS : LVI_FMAT_PATH_RANSAC;
+    const auto t0 = std::chrono::steady_clock::now();
+    g.nsub = 1; g.niters0 = 1;
+    if (g.path == LVI_FMAT_PATH_KERNEL) {
+        for (int k = 0; k < MODEL_POINTS; k++) sub[k] = k;
+    } else {
+        g.nsub = fm_sample_stream(xy, n, g.path == LVI_FMAT_PATH_RANSAC, I, confidence, check, sub, &g.niters0);
+        if (g.path == LVI_FMAT_PATH_RANSAC) for (int k = 0; k <= n; k++) lt[k] = update_log<MODEL_POINTS>(n, k);
+    }
+    g.stream_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    tr.record(sub, MODEL_POINTS, g.nsub);
+    g.thr = (float)(threshold * threshold);
+    g.num_log = num_log(confidence);
+    g.up = g.path == LVI_FMAT_PATH_RANSAC ? L.off_log + sizeof(double) * (n + 1) : L.off_sub + sizeof(int) * 7 * (size_t)g.nsub;
+    return g;
+}
+
+// the per-hypothesis arrays of one point set
+struct HypBufs {
+    double* F = nullptr;                   // [I][27]
+    int *nm = nullptr, *score = nullptr;   // [I], [I][3]
+};
+
+HypArgs hyp_args(const Staged& g, const Layout& L, const char* d_in, const HypBufs& b)
+{
+    return HypArgs{reinterpret_cast<const float4*>(d_in), reinterpret_cast<const int*>(d_in + L.off_sub), g.n, g.path == LVI_FMAT_PATH_LMEDS ? 1 : 0, g.thr, b.F, b.nm, b.score};
+}
+
+WalkArgs walk_args(const Staged& g, const Layout& L, const char* d_in, const HypBufs& b, char* d_out)
+{
+    return WalkArgs{reinterpret_cast<const float4*>(d_in), reinterpret_cast<const double*>(d_in + L.off_log), b.F, b.nm, b.score, g.n, g.nsub, g.path, g.niters0, g.num_log, g.thr,
+                    reinterpret_cast<lvi_fmat_info*>(d_out), reinterpret_cast<unsigned char*>(d_out + L.off_status)};
+}
+
+// the device half of a trace: the first m hypotheses of one point set, one wait
+void trace_hyp(hipStream_t stream, const HypBufs& b, int m, int32_t* nmodels, double* F, int32_t* score)
+{
+    if (nmodels) LVI_HIP(hipMemcpyAsync(nmodels, b.nm, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, stream));
+    if (F) LVI_HIP(hipMemcpyAsync(F, b.F, sizeof(double) * 27 * (size_t)m, hipMemcpyDeviceToHost, stream));
+    if (score) LVI_HIP(hipMemcpyAsync(score, b.score, sizeof(int) * 3 * (size_t)m, hipMemcpyDeviceToHost, stream));
+    LVI_HIP(hipStreamSynchronize(stream));
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- the handle
 struct lvi_fmat {
     int P = 0, I = 0, check = 1;
-    Io io;                                 // d_in: pts [P] float4 | subsets [I][7] | logtab [P + 1]; d_out: info | status [P]
-    double* d_F = nullptr;                 // [I][27]
-    int *d_nm = nullptr, *d_score = nullptr;
-    size_t off_sub = 0, off_log = 0;
+    Io io;
+    Layout L;
+    HypBufs hb;
 };
 
 extern "C" {
@@ -330,12 +457,11 @@ int32_t lvi_fmat_create(int32_t device, int32_t max_points, int32_t max_iters, l
     if (max_iters < 1 || max_iters > LVI_FMAT_MAX_ITERS) return fail(LVI_ERR_INVALID_ARG, "max_iters must be 1..LVI_FMAT_MAX_ITERS");
     lvi_fmat* h = new lvi_fmat();
     h->P = max_points; h->I = max_iters;
-    h->off_sub = align256(sizeof(float4) * (size_t)h->P);
-    h->off_log = h->off_sub + align256(sizeof(int) * 7 * (size_t)h->I);
-    const int32_t st = h->io.open(device, h->off_log + align256(sizeof(double) * ((size_t)h->P + 1)), align256(sizeof(lvi_fmat_info)) + align256((size_t)h->P),
-                                  {{(void**)&h->d_F, sizeof(double) * 27 * (size_t)h->I},
-                                   {(void**)&h->d_nm, sizeof(int) * (size_t)h->I},
-                                   {(void**)&h->d_score, sizeof(int) * 3 * (size_t)h->I}});
+    h->L.set(h->P, h->I);
+    const int32_t st = h->io.open(device, h->L.in_bytes, h->L.out_bytes,
+                                  {{(void**)&h->hb.F, sizeof(double) * 27 * (size_t)h->I},
+                                   {(void**)&h->hb.nm, sizeof(int) * (size_t)h->I},
+                                   {(void**)&h->hb.score, sizeof(int) * 3 * (size_t)h->I}});
     if (st != LVI_OK) { lvi_fmat_destroy(h); return st; }
     *out = h;
     return LVI_OK;
@@ -344,7 +470,7 @@ int32_t lvi_fmat_create(int32_t device, int32_t max_points, int32_t max_iters, l
 void lvi_fmat_destroy(lvi_fmat* h)
 {
     if (!h) return;
-    h->io.close({h->d_F, h->d_nm, h->d_score});
+    h->io.close({h->hb.F, h->hb.nm, h->hb.score});
     delete h;
 }
 
@@ -363,41 +489,13 @@ int32_t lvi_fmat_find(lvi_fmat* h, const float* pts1_xy, const float* pts2_xy, i
     if (n > h->P) return fail(LVI_ERR_INVALID_ARG, "n > max_points");
     Io& io = h->io;
     return guarded(io.device, [&]() -> int32_t {
-        // findFundamentalMat's argument defaults
-        if (threshold <= 0) threshold = 3;
-        if (confidence < DBL_EPSILON || confidence > 1 - DBL_EPSILON) confidence = 0.99;
-        float* xy = reinterpret_cast<float*>(io.h_in);
-        for (int i = 0; i < n; i++) {
-            xy[4 * i] = pts1_xy[2 * i]; xy[4 * i + 1] = pts1_xy[2 * i + 1];
-            xy[4 * i + 2] = pts2_xy[2 * i]; xy[4 * i + 3] = pts2_xy[2 * i + 1];
-        }
-        int* sub = reinterpret_cast<int*>(io.h_in + h->off_sub);
-        double* lt = reinterpret_cast<double*>(io.h_in + h->off_log);
-        const int path = n == MODEL_POINTS ? LVI_FMAT_PATH_KERNEL : n < 15 ? LVI_FMAT_PATH_LMEDS : LVI_FMAT_PATH_RANSAC;
-        const auto t0 = std::chrono::steady_clock::now();
-        int nsub = 1, niters0 = 1;
-        if (path == LVI_FMAT_PATH_KERNEL) {
-            for (int k = 0; k < MODEL_POINTS; k++) sub[k] = k;
-        } else {
-            nsub = fm_sample_stream(xy, n, path == LVI_FMAT_PATH_RANSAC, h->I, confidence, h->check, sub, &niters0);
-            if (path == LVI_FMAT_PATH_RANSAC) for (int g = 0; g <= n; g++) lt[g] = update_log<MODEL_POINTS>(n, g);
-        }
-        const double stream_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        io.record(sub, MODEL_POINTS, nsub);
-
-        const float thr = (float)(threshold * threshold);
-        // one upload: the points, then (if any) the subsets and the log table
-        const size_t up = path == LVI_FMAT_PATH_RANSAC ? h->off_log + sizeof(double) * (n + 1) : h->off_sub + sizeof(int) * 7 * (size_t)nsub;
-        io.run(up, n, stream_us, status_out, info_out, [&](lvi_fmat_info* d_info, unsigned char* d_status) {
-            const float4* d_pts = reinterpret_cast<const float4*>(io.d_in);
-            if (nsub > 0) {
-                HypArgs ha{d_pts, reinterpret_cast<const int*>(io.d_in + h->off_sub), n, path == LVI_FMAT_PATH_LMEDS ? 1 : 0, thr, h->d_F, h->d_nm, h->d_score};
-                hipLaunchKernelGGL(fmat_hyp, dim3(nsub), dim3(LVI_WAVE), sizeof(float4) * (size_t)n, io.stream, ha);
+        const Staged g = stage_set(io.h_in, h->L, h->I, h->check, pts1_xy, pts2_xy, n, threshold, confidence, io);
+        io.run(g.up, n, g.stream_us, status_out, info_out, [&](lvi_fmat_info*, unsigned char*) {
+            if (g.nsub > 0) {
+                hipLaunchKernelGGL(fmat_hyp, dim3(g.nsub), dim3(LVI_WAVE), sizeof(float4) * (size_t)n, io.stream, hyp_args(g, h->L, io.d_in, h->hb));
                 LVI_HIP(hipGetLastError());
             }
-            WalkArgs wa{d_pts, reinterpret_cast<const double*>(io.d_in + h->off_log), h->d_F, h->d_nm, h->d_score, n, nsub, path, niters0, num_log(confidence), thr,
-                        d_info, d_status};
-            hipLaunchKernelGGL(fmat_walk, dim3(1), dim3(LVI_WAVE), 0, io.stream, wa);
+            hipLaunchKernelGGL(fmat_walk, dim3(1), dim3(LVI_WAVE), 0, io.stream, walk_args(g, h->L, io.d_in, h->hb, io.d_out));
             LVI_HIP(hipGetLastError());
         });
         return LVI_OK;
@@ -409,13 +507,145 @@ int32_t lvi_fmat_trace(lvi_fmat* h, int32_t* subsets, int32_t* nmodels, double* 
     if (!h || cap < 0) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
     return guarded(h->io.device, [&]() -> int32_t {
         const int m = h->io.trace_subsets(subsets, MODEL_POINTS, cap, n_out);
-        if (m == 0) return LVI_OK;
-        if (nmodels) LVI_HIP(hipMemcpyAsync(nmodels, h->d_nm, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
-        if (F) LVI_HIP(hipMemcpyAsync(F, h->d_F, sizeof(double) * 27 * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
-        if (score) LVI_HIP(hipMemcpyAsync(score, h->d_score, sizeof(int) * 3 * (size_t)m, hipMemcpyDeviceToHost, h->io.stream));
-        LVI_HIP(hipStreamSynchronize(h->io.stream));
+        if (m > 0) trace_hyp(h->io.stream, h->hb, m, nmodels, F, score);
         return LVI_OK;
     });
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- the batched handle
+// include/lvi_fmatb.h, DESIGN §25: `slots` point sets per call on one stream.  Slot s owns a region of each block:
+//   d_in / h_in    [s * in_stride]   the slot's WalkRec | the region of a single handle (Layout)
+//   d_out / h_out  [s * L.out_bytes] info | status [P]
+// and slot s's part [s * I] of each per-hypothesis array, so no slot reads what another wrote.
+struct lvi_fmatb {
+    int S = 0, P = 0, I = 0, check = 1;
+    Bufs io;
+    Layout L;
+    size_t off_set = 0, in_stride = 0;     // the slot's Layout region starts off_set bytes into the slot's input region
+    HypBufs hb;                            // [S][I]...
+    Trace tr[LVI_TRACKER_MAX_BATCH];
+    int64_t calls = 0, hyp_launches = 0, walk_launches = 0, waits = 0;
+    HypBufs slot(int s) const { return HypBufs{hb.F + 27 * (size_t)I * s, hb.nm + (size_t)I * s, hb.score + 3 * (size_t)I * s}; }
+};
+
+extern "C" {
+
+int32_t lvi_fmatb_abi_version(void) { return LVI_FMATB_ABI_VERSION; }
+
+int32_t lvi_fmatb_create(int32_t device, int32_t slots, int32_t max_points, int32_t max_iters, lvi_fmatb** out)
+{
+    if (!out) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (slots < 1 || slots > LVI_TRACKER_MAX_BATCH) return fail(LVI_ERR_INVALID_ARG, "slots must be 1..LVI_TRACKER_MAX_BATCH");
+    if (max_points < MODEL_POINTS || max_points > LVI_FMAT_MAX_POINTS) return fail(LVI_ERR_INVALID_ARG, "max_points must be 7..LVI_FMAT_MAX_POINTS");
+    if (max_iters < 1 || max_iters > LVI_FMAT_MAX_ITERS) return fail(LVI_ERR_INVALID_ARG, "max_iters must be 1..LVI_FMAT_MAX_ITERS");
+    lvi_fmatb* h = new lvi_fmatb();
+    h->S = slots; h->P = max_points; h->I = max_iters;
+    h->L.set(h->P, h->I);
+    h->off_set = align256(sizeof(WalkRec));
+    h->in_stride = h->off_set + h->L.in_bytes;
+    const size_t SI = (size_t)slots * (size_t)h->I;
+    const int32_t st = h->io.open(device, h->in_stride * (size_t)slots, h->L.out_bytes * (size_t)slots,
+                                  {{(void**)&h->hb.F, sizeof(double) * 27 * SI}, {(void**)&h->hb.nm, sizeof(int) * SI}, {(void**)&h->hb.score, sizeof(int) * 3 * SI}});
+    if (st != LVI_OK) { lvi_fmatb_destroy(h); return st; }
+    *out = h;
+    return LVI_OK;
+}
+
+void lvi_fmatb_destroy(lvi_fmatb* h)
+{
+    if (!h) return;
+    h->io.close({h->hb.F, h->hb.nm, h->hb.score});
+    delete h;
+}
+
+int32_t lvi_fmatb_set_check_subset(lvi_fmatb* h, int32_t mode)
+{
+    if (!h || (mode != 0 && mode != 1)) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
+    h->check = mode;
+    return LVI_OK;
+}
+
+int32_t lvi_fmatb_find(lvi_fmatb* h, const float* const* pts1_xy, const float* const* pts2_xy, const int32_t* n, const double* threshold, double confidence,
+                       uint8_t* const* status_out, lvi_fmat_info* info_out)
+{
+    if (!h || !pts1_xy || !pts2_xy || !n || !threshold || !status_out) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    // every slot's arguments before anything is written, staged or launched
+    unsigned active = 0;
+    for (int s = 0; s < h->S; s++) {
+        if (n[s] == -1) continue;
+        if (!pts1_xy[s] || !pts2_xy[s] || !status_out[s]) return fail(LVI_ERR_INVALID_ARG, "null argument in an active slot");
+        if (n[s] < MODEL_POINTS) return fail(LVI_ERR_INVALID_ARG, "n < 7 in a slot (-1 = the slot sits out): findFundamentalMat has no model");
+        if (n[s] > h->P) return fail(LVI_ERR_INVALID_ARG, "n > max_points in a slot");
+        active |= 1u << s;
+    }
+    Bufs& io = h->io;
+    return guarded(io.device, [&]() -> int32_t {
+        for (int s = 0; s < h->S; s++) if (!((active >> s) & 1u)) {
+            h->tr[s].clear();
+            if (info_out) std::memset(&info_out[s], 0, sizeof(lvi_fmat_info));
+        }
+        if (!active) return LVI_OK;
+        double stream_us[LVI_TRACKER_MAX_BATCH] = {};
+        // per active slot: the host's half, then the slot's upload and its hypotheses enqueued; the device scores slot s
+        // while the host draws the stream of slot s + 1
+        for (int s = 0; s < h->S; s++) {
+            if (!((active >> s) & 1u)) continue;
+            char* hs = io.h_in + h->in_stride * (size_t)s;
+            const char* ds = io.d_in + h->in_stride * (size_t)s;
+            const Staged g = stage_set(hs + h->off_set, h->L, h->I, h->check, pts1_xy[s], pts2_xy[s], n[s], threshold[s], confidence, h->tr[s]);
+            stream_us[s] = g.stream_us;
+            const WalkRec rec{g.n, g.nsub, g.path, g.niters0, g.num_log, g.thr};
+            std::memcpy(hs, &rec, sizeof(WalkRec));
+            LVI_HIP(hipMemcpyAsync(io.d_in + h->in_stride * (size_t)s, hs, h->off_set + g.up, hipMemcpyHostToDevice, io.stream));
+            if (g.nsub > 0) {
+                hipLaunchKernelGGL(fmatb_hyp, dim3(g.nsub), dim3(LVI_WAVE), sizeof(float4) * (size_t)g.n, io.stream, hyp_args(g, h->L, ds + h->off_set, h->slot(s)));
+                LVI_HIP(hipGetLastError());
+                h->hyp_launches++;
+            }
+        }
+        const WalkBatch wb{io.d_in, io.d_out, h->hb.F, h->hb.nm, h->hb.score, h->in_stride, h->off_set, h->L.off_log, h->L.out_bytes, h->L.off_status, h->I, active};
+        hipLaunchKernelGGL(fmatb_walk, dim3(h->S), dim3(LVI_WAVE), 0, io.stream, wb);
+        LVI_HIP(hipGetLastError());
+        h->walk_launches++;
+        LVI_HIP(hipMemcpyAsync(io.h_out, io.d_out, h->L.out_bytes * (size_t)h->S, hipMemcpyDeviceToHost, io.stream));
+        LVI_HIP(hipStreamSynchronize(io.stream));
+        h->waits++;
+        h->calls++;
+        for (int s = 0; s < h->S; s++) {
+            if (!((active >> s) & 1u)) continue;
+            const char* o = io.h_out + h->L.out_bytes * (size_t)s;
+            std::memcpy(status_out[s], o + h->L.off_status, (size_t)n[s]);
+            if (info_out) {
+                std::memcpy(&info_out[s], o, sizeof(lvi_fmat_info));
+                info_out[s].stream_us = stream_us[s];
+            }
+        }
+        return LVI_OK;
+    });
+}
+
+int32_t lvi_fmatb_trace(lvi_fmatb* h, int32_t slot, int32_t* subsets, int32_t* nmodels, double* F, int32_t* score, int32_t cap, int32_t* n_out)
+{
+    if (!h || cap < 0 || slot < 0 || slot >= h->S) return fail(LVI_ERR_INVALID_ARG, "bad arguments");
+    return guarded(h->io.device, [&]() -> int32_t {
+        const int m = h->tr[slot].trace_subsets(subsets, MODEL_POINTS, cap, n_out);
+        if (m > 0) trace_hyp(h->io.stream, h->slot(slot), m, nmodels, F, score);
+        return LVI_OK;
+    });
+}
+
+int32_t lvi_fmatb_counters(lvi_fmatb* h, int64_t* calls, int64_t* hyp_launches, int64_t* walk_launches, int64_t* waits)
+{
+    if (!h) return fail(LVI_ERR_INVALID_ARG, "null argument");
+    if (calls) *calls = h->calls;
+    if (hyp_launches) *hyp_launches = h->hyp_launches;
+    if (walk_launches) *walk_launches = h->walk_launches;
+    if (waits) *waits = h->waits;
+    return LVI_OK;
+}
+
+}  // extern "C"
+

@@ -6,7 +6,9 @@
 //            or pow; then the 7-point callback's checkSubset and findFundamentalMat's stream.  No HIP in this part: tests
 //            compile it with a stand-alone main under the host sanitizers.
 //   device   the sequential walk of RANSACPointSetRegistrator::run over per-candidate inlier counts, and the status sweep
-//   Io       the stream and the buffer pairs of a handle, and the tail of a call: upload, launches, download, wait
+//   Io       the stream and the buffer pairs of a handle (Bufs), the last call's sample stream (Trace), and the tail of a
+//            call: upload, launches, download, wait.  The batched RANSAC (lvi_fmatb) takes Bufs and one Trace
+//            per slot and has a tail of its own.
 //
 // The draws do not depend on any model, so the whole stream is known before the first hypothesis is scored.  The host
 // functions are static: with external linkage the position-independent library calls them through the PLT, and
@@ -180,7 +182,8 @@ __device__ __forceinline__ int status_sweep(int n, unsigned char* status, Inlier
 // ---------------------------------------------------------------------------------------------- the handle's plumbing
 struct DevBuf { void** p; size_t bytes; };
 
-struct Io {
+// the stream and the buffer pairs; a batched handle (lvi_fmatb) lays one region per slot into each block
+struct Bufs {
     int device = 0;
     hipStream_t stream = nullptr;
     char* d_in = nullptr;                  // points | subsets | logtab, laid out by the owner
@@ -188,9 +191,6 @@ struct Io {
     char* d_out = nullptr;                 // info | status
     char* h_out = nullptr;
     size_t in_bytes = 0, out_bytes = 0;
-    // last call
-    int last_nsub = 0;
-    std::vector<int32_t> last_subsets;
 
     // the device checks, then the stream, the buffer pairs and the owner's per-hypothesis arrays
     int32_t open(int dev, size_t in_b, size_t out_b, std::initializer_list<DevBuf> hyp)
@@ -220,13 +220,32 @@ struct Io {
         if (h_out) (void)hipHostFree(h_out);
         (void)hipStreamDestroy(stream);
     }
+};
+
+// the sample stream of the last call, kept on the host for the trace; a batched handle has one per slot
+struct Trace {
+    int last_nsub = 0;
+    std::vector<int32_t> last_subsets;
 
     void record(const int32_t* sub, int model_points, int nsub)
     {
         last_nsub = nsub;
         last_subsets.assign(sub, sub + model_points * (size_t)nsub);
     }
+    void clear() { last_nsub = 0; last_subsets.clear(); }
 
+    // the head of a trace: the last call's subset count to *n_out, its first min(cap, count) subsets copied; returns that minimum
+    int trace_subsets(int32_t* subsets, int model_points, int cap, int32_t* n_out) const
+    {
+        const int m = std::min(cap, last_nsub);
+        if (n_out) *n_out = last_nsub;
+        if (m > 0 && subsets) std::memcpy(subsets, last_subsets.data(), sizeof(int32_t) * model_points * (size_t)m);
+        return m;
+    }
+};
+
+// a handle of one point set per call: the buffers, the trace and the tail of a call
+struct Io : Bufs, Trace {
     // The tail of a call.  One upload of the first `up` bytes of h_in, then launch(d_info, d_status) enqueues the
     // kernels, then one download of the info record and n status bytes, and one wait.
     template <class Info, class Launch>
@@ -242,15 +261,6 @@ struct Io {
             std::memcpy(info_out, h_out, sizeof(Info));
             info_out->stream_us = stream_us;
         }
-    }
-
-    // the head of a trace: the last call's subset count to *n_out, its first min(cap, count) subsets copied; returns that minimum
-    int trace_subsets(int32_t* subsets, int model_points, int cap, int32_t* n_out) const
-    {
-        const int m = std::min(cap, last_nsub);
-        if (n_out) *n_out = last_nsub;
-        if (m > 0 && subsets) std::memcpy(subsets, last_subsets.data(), sizeof(int32_t) * model_points * (size_t)m);
-        return m;
     }
 };
 

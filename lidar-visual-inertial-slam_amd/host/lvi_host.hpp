@@ -695,11 +695,14 @@ public:
         if (xi == 1.0) P[2] = (1.0 - mx_u * mx_u - my_u * my_u) / 2.0;
         else { const double rho2_d = mx_u * mx_u + my_u * my_u; P[2] = 1.0 - xi * (rho2_d + 1.0) / (xi + std::sqrt(1.0 + (1.0 - xi * xi) * rho2_d)); }
     }
-    void rejectWithF()                                          // feature_tracker.cpp:209-242
+    // rejectWithF in two halves around the findFundamentalMat call, so that a rig can make one call for all its cameras
+    // (host/lvi_fmatb_host.hpp).  prepareRejectWithF: the < 8 return, the camera test and the two lifts (:210-228); false = no
+    // call for this camera (without a camera that counts as a skip).  applyRejectWithF: the five reduceVector (:232-236).
+    bool prepareRejectWithF(std::vector<Point2f>& un_cur_pts, std::vector<Point2f>& un_forw_pts)
     {
-        if (forw_pts.size() < 8) return;
-        if (!findFundamentalMat || !have_cam_) { rejectWithF_skipped++; return; }
-        std::vector<Point2f> un_cur_pts(cur_pts.size()), un_forw_pts(forw_pts.size());
+        if (forw_pts.size() < 8) return false;
+        if (!have_cam_) { rejectWithF_skipped++; return false; }
+        un_cur_pts.resize(cur_pts.size()); un_forw_pts.resize(forw_pts.size());
         for (size_t i = 0; i < cur_pts.size(); i++) {
             double tmp_p[3];
             liftProjective(cur_pts[i].x, cur_pts[i].y, tmp_p);
@@ -707,10 +710,24 @@ public:
             liftProjective(forw_pts[i].x, forw_pts[i].y, tmp_p);
             un_forw_pts[i] = Point2f{(float)(FOCAL_LENGTH * tmp_p[0] / tmp_p[2] + COL / 2.0), (float)(FOCAL_LENGTH * tmp_p[1] / tmp_p[2] + ROW / 2.0)};
         }
-        std::vector<uint8_t> status(cur_pts.size(), 1);
-        findFundamentalMat(un_cur_pts, un_forw_pts, F_THRESHOLD, status);
+        return true;
+    }
+    void applyRejectWithF(const std::vector<uint8_t>& status)
+    {
+        const size_t before = forw_pts.size();
         reduceVector(prev_pts, status); reduceVector(cur_pts, status); reduceVector(forw_pts, status);
         reduceVector(ids, status); reduceVector(track_cnt, status);
+        rejectWithF_removed += (int)(before - forw_pts.size());
+    }
+    int rejectWithF_removed = 0;                                // tracks findFundamentalMat's status has removed so far
+    void rejectWithF()                                          // feature_tracker.cpp:209-242
+    {
+        if (!findFundamentalMat) { if (forw_pts.size() >= 8) rejectWithF_skipped++; return; }
+        std::vector<Point2f> un_cur_pts, un_forw_pts;
+        if (!prepareRejectWithF(un_cur_pts, un_forw_pts)) return;
+        std::vector<uint8_t> status(cur_pts.size(), 1);
+        findFundamentalMat(un_cur_pts, un_forw_pts, F_THRESHOLD, status);
+        applyRejectWithF(status);
     }
 
     // ---- the host steps of readImage (feature_tracker.cpp:81-207), in the order readImage takes them
@@ -725,9 +742,15 @@ public:
     // (<= 0, or a frame that is not published: nothing to detect)
     int beginDetection()
     {
-        for (auto& n : track_cnt) n++;                                                            // :150-151
+        bumpTrackCnt();
         if (!PUB_THIS_FRAME) return 0;
         rejectWithF();                                                                            // :153
+        return maskAndQuota();
+    }
+    // beginDetection's steps before and after rejectWithF, for a rig that rejects for all cameras in one call
+    void bumpTrackCnt() { for (auto& n : track_cnt) n++; }                                        // :150-151
+    int maskAndQuota()                                                                            // :154-161, PUB frames only
+    {
         setMask();
         return MAX_CNT - (int)forw_pts.size();
     }

@@ -27,7 +27,9 @@ int32_t guarded(F&& f)
 struct lvh_rig {
     int S = 0;
     std::unique_ptr<TrackerBatchHandle> b;
+    std::unique_ptr<BatchedFundamental> bf;
     std::unique_ptr<FeatureTrackerRig> rig;
+    long hook_calls = 0;                                       // findFundamentalMat calls of the per-camera device hooks
     std::vector<std::unique_ptr<TrackerHandle>> th;
     std::vector<std::unique_ptr<FeatureTracker>> ft;
     FeatureTrackerState& cam(int i) { return rig ? rig->trackerData[(size_t)i] : *ft[(size_t)i]; }
@@ -72,10 +74,38 @@ int32_t lvh_rig_use_device_fundamental(lvh_rig* r, int32_t device)
     return guarded([&]() -> int32_t {
         for (int i = 0; i < r->S; i++) {
             auto df = std::make_shared<DeviceFundamental>(device);
-            r->cam(i).findFundamentalMat = [df](const std::vector<Point2f>& a, const std::vector<Point2f>& b, double thr, std::vector<uint8_t>& status) {
+            r->cam(i).findFundamentalMat = [df, r](const std::vector<Point2f>& a, const std::vector<Point2f>& b, double thr, std::vector<uint8_t>& status) {
+                r->hook_calls++;
                 df->find(a, b, thr, status);
             };
         }
+        return LVI_OK;
+    });
+}
+
+// rejectWithF of all cameras := ONE BatchedFundamental::find per frame (lvi_fmatb_host.hpp); the batched form only
+int32_t lvh_rig_use_batched_fundamental(lvh_rig* r, int32_t device)
+{
+    if (!r) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!r->rig) { g_err = "the batched rejectWithF needs a rig created with batched = 1"; return LVI_ERR_STATE; }
+    return guarded([&]() -> int32_t {
+        std::unique_ptr<BatchedFundamental> bf(new BatchedFundamental(device, r->S));
+        r->rig->useBatchedFundamental(bf.get());
+        r->bf = std::move(bf);
+        return LVI_OK;
+    });
+}
+
+// out[4]: rejectWithF_skipped and rejectWithF_removed summed over the cameras, the findFundamentalMat calls made (batched: the
+// handle's calls; otherwise those of the per-camera device hooks), and the cameras that prepared over all frames (batched only)
+int32_t lvh_rig_fundamental_stats(lvh_rig* r, int64_t* out)
+{
+    if (!r || !out) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    return guarded([&]() -> int32_t {
+        out[0] = out[1] = 0;
+        for (int i = 0; i < r->S; i++) { out[0] += r->cam(i).rejectWithF_skipped; out[1] += r->cam(i).rejectWithF_removed; }
+        out[2] = r->bf ? r->bf->calls() : r->hook_calls;
+        out[3] = r->bf ? r->rig->batchedSlots() : 0;
         return LVI_OK;
     });
 }

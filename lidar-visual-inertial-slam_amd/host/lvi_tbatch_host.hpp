@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "../../include/lvi_tbatch.h"
+#include "lvi_fmatb_host.hpp"
 #include "lvi_host.hpp"
 
 namespace lvi_host {
@@ -67,23 +68,48 @@ public:
             check(lvi_tbatch_run_lk(b_.get()), "lvi_tbatch_run_lk");                               // calcOpticalFlowPyrLK (:113)
         }
         // ---- 2: per camera the border test, reduceVector, rejectWithF through its hook, setMask's walk; circles and GFTT for all
+        //         (with useBatchedFundamental: rejectWithF for all cameras in ONE call between its two halves)
         std::vector<int32_t> quota((size_t)S, -1), n_kept((size_t)S, -1);
         bool any_gftt = false, any_end = false;
+        auto lkResults = [&](int i) {
+            const int32_t n_lk = n[(size_t)i];
+            if (n_lk <= 0) return;
+            FeatureTrackerState& c = trackerData[(size_t)i];
+            std::vector<uint8_t> status((size_t)n_lk);
+            std::vector<float> err((size_t)n_lk);
+            c.forw_pts.resize((size_t)n_lk);
+            int32_t m = 0;
+            check(lvi_tbatch_get_lk(b_.get(), i, &c.forw_pts[0].x, status.data(), err.data(), n_lk, &m), "lvi_tbatch_get_lk");
+            c.applyLkStatus(status);
+        };
+        if (bf_) {
+            const std::vector<Point2f>* none = nullptr;
+            std::vector<const std::vector<Point2f>*> pa((size_t)S, none), pb((size_t)S, none);
+            std::vector<double> thr((size_t)S, 0.0);
+            bool any_prepared = false;
+            un_a_.resize((size_t)S); un_b_.resize((size_t)S);
+            for (int i = 0; i < S; i++) {
+                if (!imgs[i]) continue;
+                FeatureTrackerState& c = trackerData[(size_t)i];
+                lkResults(i);
+                c.bumpTrackCnt();
+                if (c.PUB_THIS_FRAME && c.prepareRejectWithF(un_a_[(size_t)i], un_b_[(size_t)i])) {
+                    pa[(size_t)i] = &un_a_[(size_t)i]; pb[(size_t)i] = &un_b_[(size_t)i]; thr[(size_t)i] = c.F_THRESHOLD;
+                    any_prepared = true; batched_slots_++;
+                }
+            }
+            if (any_prepared) {
+                bf_->find(pa, pb, thr, f_status_);
+                for (int i = 0; i < S; i++) if (pa[(size_t)i]) trackerData[(size_t)i].applyRejectWithF(f_status_[(size_t)i]);
+            }
+        }
         for (int i = 0; i < S; i++) {
             ptr[(size_t)i] = nullptr;
-            const int32_t n_lk = n[(size_t)i];
+            if (!bf_ && imgs[i]) lkResults(i);
             n[(size_t)i] = -1;
             if (!imgs[i]) continue;
             FeatureTrackerState& c = trackerData[(size_t)i];
-            if (n_lk > 0) {
-                std::vector<uint8_t> status((size_t)n_lk);
-                std::vector<float> err((size_t)n_lk);
-                c.forw_pts.resize((size_t)n_lk);
-                int32_t m = 0;
-                check(lvi_tbatch_get_lk(b_.get(), i, &c.forw_pts[0].x, status.data(), err.data(), n_lk, &m), "lvi_tbatch_get_lk");
-                c.applyLkStatus(status);
-            }
-            const int n_max_cnt = c.beginDetection();
+            const int n_max_cnt = !bf_ ? c.beginDetection() : c.PUB_THIS_FRAME ? c.maskAndQuota() : 0;
             if (n_max_cnt > 0) {
                 ptr[(size_t)i] = c.forw_pts.empty() ? nullptr : &c.forw_pts[0].x; n[(size_t)i] = (int32_t)c.forw_pts.size();
                 quota[(size_t)i] = n_max_cnt; any_gftt = true;
@@ -127,11 +153,23 @@ public:
             if (!completed) break;
         }
     }
+    // rejectWithF of all cameras := one BatchedFundamental::find per frame (host/lvi_fmatb_host.hpp) between prepareRejectWithF and
+    // applyRejectWithF; the cameras' own findFundamentalMat hooks are then not called.  nullptr: the per-camera hooks again.
+    void useBatchedFundamental(BatchedFundamental* bf)
+    {
+        if (bf && bf->slots() != S) throw Error(LVI_ERR_INVALID_ARG, "FeatureTrackerRig::useBatchedFundamental: one slot per camera");
+        bf_ = bf;
+    }
+    long batchedSlots() const { return batched_slots_; }       // cameras that prepared, over all frames: the calls per-camera hooks would have made
 private:
     TrackerBatchHandle& b_;
     int S, ROW, COL, MIN_DIST;
     std::vector<lvi_mei_params> cams_;
     std::vector<Point2f> out_, un_;
+    BatchedFundamental* bf_ = nullptr;
+    long batched_slots_ = 0;
+    std::vector<std::vector<Point2f>> un_a_, un_b_;            // un_cur_pts, un_forw_pts per camera
+    std::vector<std::vector<uint8_t>> f_status_;
 };
 
 }  // namespace lvi_host

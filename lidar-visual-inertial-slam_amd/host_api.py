@@ -62,6 +62,7 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
     if sources:
         deps += [os.path.join(HOST_DIR, "lvi_depth_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_depth.h"),
                  os.path.join(HOST_DIR, "lvi_fmat_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmat.h"),
+                 os.path.join(HOST_DIR, "lvi_fmatb_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmatb.h"),
                  os.path.join(HOST_DIR, "lvi_gmap_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_gmap.h"),
                  os.path.join(HOST_DIR, "lvi_loop_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_loop.h"),
                  os.path.join(HOST_DIR, "lvi_kf_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_kf.h"),
@@ -237,6 +238,8 @@ class HostLibrary:
             d.lvh_rig_create.argtypes = [C.POINTER(A.TrackerParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(A.MeiParams), C.c_int32]
             d.lvh_rig_destroy.argtypes = [C.c_void_p]
             d.lvh_rig_use_device_fundamental.argtypes = [C.c_void_p, C.c_int32]
+            d.lvh_rig_use_batched_fundamental.argtypes = [C.c_void_p, C.c_int32]
+            d.lvh_rig_fundamental_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
             d.lvh_rig_read_images.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
             d.lvh_rig_update_ids.argtypes = [C.c_void_p]
             d.lvh_rig_reset_ids.restype = None
@@ -1073,6 +1076,18 @@ class TrackerRig:
     def use_device_fundamental(self, device=0):
         """every camera's rejectWithF runs the device RANSAC (include/lvi_fmat.h) through a handle of its own"""
         self._check(self.hl.dll.lvh_rig_use_device_fundamental(self._r, int(device)), "lvh_rig_use_device_fundamental")
+
+    def use_batched_fundamental(self, device=0):
+        """rejectWithF of all cameras runs as ONE call of the batched device RANSAC per frame (include/lvi_fmatb.h); the
+        batched rig only (LVI_ERR_STATE otherwise)"""
+        self._check(self.hl.dll.lvh_rig_use_batched_fundamental(self._r, int(device)), "lvh_rig_use_batched_fundamental")
+
+    def fundamental_stats(self):
+        """dict(rejectWithF_skipped, rejectWithF_removed: summed over the cameras; calls: findFundamentalMat calls made (the
+        batched handle's, or the per-camera device hooks'); prepared: cameras that prepared over all frames (batched only))"""
+        out = (C.c_int64 * 4)()
+        self._check(self.hl.dll.lvh_rig_fundamental_stats(self._r, out), "lvh_rig_fundamental_stats")
+        return dict(rejectWithF_skipped=int(out[0]), rejectWithF_removed=int(out[1]), calls=int(out[2]), prepared=int(out[3]))
 
     def reset_ids(self):
         """FeatureTracker::n_id := 0 (one counter per process)"""
