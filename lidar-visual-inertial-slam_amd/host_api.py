@@ -53,6 +53,8 @@ TBATCH_SOURCES = ("lvi_tbatch_capi.cpp",)
 MARG_SOURCES = ("lvi_marg_capi.cpp",)
 # the window solve's (include/lvi_win.h, the same restriction; it optimises the marginaliser's window arrays, so MARG_SOURCES go with it)
 WIN_SOURCES = ("lvi_win_capi.cpp",)
+# the feature manager's (include/lvi_fman.h, the same restriction; fillWindow writes into both, so MARG_SOURCES and WIN_SOURCES go with it)
+FMAN_SOURCES = ("lvi_fman_capi.cpp",)
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
@@ -70,6 +72,7 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
                  os.path.join(HOST_DIR, "lvi_bow_capi_detail.hpp"), os.path.join(HOST_DIR, "lvi_pnp_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pnp.h"),
                  os.path.join(HOST_DIR, "lvi_tbatch_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_tbatch.h"),
                  os.path.join(HOST_DIR, "lvi_win_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_win.h"),
+                 os.path.join(HOST_DIR, "lvi_fman_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fman.h"),
                  os.path.join(HOST_DIR, "lvi_pgo_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pgo.h"),
                  os.path.join(HOST_DIR, "lvi_marg_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_marg.h")]
     if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
@@ -231,6 +234,24 @@ class HostLibrary:
             d.lvh_win_set_lidar_flags.argtypes = [C.c_void_p, C.c_int32, ip]
             d.lvh_win_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(WinInfo)]
             d.lvh_win_get_window.argtypes = [C.c_void_p, dp, dp, dp, dp, C.c_int32, ip, dp]
+        self.has_fman = hasattr(d, "lvh_fman_create")     # the HIP host library only
+        if self.has_fman:
+            from .fman import FmanFrameInfo, FmanParams, FmanTriInfo
+            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+            d.lvh_fman_last_error.restype = C.c_char_p
+            d.lvh_fman_create.restype = C.c_void_p
+            d.lvh_fman_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(FmanParams)]
+            d.lvh_fman_destroy.argtypes = [C.c_void_p]
+            d.lvh_fman_handle.restype = C.c_void_p
+            d.lvh_fman_handle.argtypes = [C.c_void_p]
+            d.lvh_fman_clear_state.argtypes = [C.c_void_p]
+            d.lvh_fman_add_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip, dp, C.c_double, C.POINTER(FmanFrameInfo)]
+            d.lvh_fman_triangulate.argtypes = [C.c_void_p, dp, dp, dp, dp, C.POINTER(FmanTriInfo)]
+            d.lvh_fman_fill_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            d.lvh_fman_take_depths.argtypes = [C.c_void_p, C.c_void_p]
+            d.lvh_fman_remove_failures.argtypes = [C.c_void_p]
+            d.lvh_fman_slide_old.argtypes = [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp]
+            d.lvh_fman_slide_new.argtypes = [C.c_void_p, C.c_int32]
         self.has_rig = hasattr(d, "lvh_rig_create")      # the HIP host library only
         if self.has_rig:
             d.lvh_rig_last_error.restype = C.c_char_p
@@ -1035,6 +1056,97 @@ class VinsWindowOptimizer:
         self._check(self.hl.dll.lvh_win_get_window(self._p, pose.ctypes.data_as(dp), sb.ctypes.data_as(dp), ex.ctypes.data_as(dp), C.byref(td), n.value, None,
                                                    inv.ctypes.data_as(dp)), "lvh_win_get_window")
         return dict(pose=pose, speed_bias=sb, ex_pose=ex, td=td.value, inv_dep=inv[:n.value])
+
+
+class FeatureManager:
+    """lvi_host::FeatureManager (host/lvi_fman_host.hpp): the reference's f_manager over include/lvi_fman.h, with fillWindow /
+    takeDepths towards a VinsMarginalizer and a VinsWindowOptimizer and the two slides of estimator.cpp:1076-1099.  HIP host
+    library only.  `table` is a fman.FeatureTable view of the handle the C++ side owns (download, projections, ...)."""
+
+    def __init__(self, hostlib, abi_lib, device=0, max_features=1024, **params):
+        from .fman import FeatureTable, FmanParams, bind as fman_bind
+        if not hostlib.has_fman:
+            raise RuntimeError("this host library has no feature manager (only the one linked against liblvi_hip.so has)")
+        self.hl = hostlib
+        p = FmanParams()
+        fman_bind(abi_lib).dll.lvi_fman_params_default(C.byref(p))
+        for k, v in params.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"lvi_fman_params has no field {k}")
+            setattr(p, k, v)
+        self._p = hostlib.dll.lvh_fman_create(int(device), int(max_features), C.byref(p))
+        if not self._p:
+            raise A.LviError(-1, "lvh_fman_create", hostlib.dll.lvh_fman_last_error().decode(errors="replace"))
+        self.table = FeatureTable(abi_lib, max_features=max_features, handle=hostlib.dll.lvh_fman_handle(self._p))    # never destroyed from here
+        self.table.params = p
+
+    def close(self):
+        if self._p:
+            self.hl.dll.lvh_fman_destroy(self._p)
+            self._p = None
+            self.table._h = C.c_void_p()                 # the view's handle went with the C++ object
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, code, where):
+        if code < 0:
+            raise A.LviError(code, where, self.hl.dll.lvh_fman_last_error().decode(errors="replace"))
+        return code
+
+    def clear_state(self):
+        self._check(self.hl.dll.lvh_fman_clear_state(self._p), "lvh_fman_clear_state")
+
+    def add_frame(self, frame_count, ids, obs, td=0.0):
+        """addFeatureCheckParallax -> dict(last_track_num, parallax_num, keyframe, added, parallax_sum)"""
+        from .fman import FmanFrameInfo
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 8)
+        assert len(obs) == len(ids)
+        info = FmanFrameInfo()
+        key = self._check(self.hl.dll.lvh_fman_add_frame(self._p, int(frame_count), len(ids), ids.ctypes.data_as(ip), obs.ctypes.data_as(dp), float(td),
+                                                         C.byref(info)), "lvh_fman_add_frame")
+        out = {k: getattr(info, k) for k, _ in FmanFrameInfo._fields_}
+        assert out["keyframe"] == key
+        return out
+
+    def triangulate(self, Ps, Rs, tic, ric):
+        from .fman import FmanTriInfo
+        dp = C.POINTER(C.c_double)
+        a, b, c, d = (np.ascontiguousarray(x, np.float64) for x in (Ps, Rs, tic, ric))
+        assert a.shape == (11, 3) and b.shape == (11, 3, 3) and c.shape == (3,) and d.shape == (3, 3)
+        info = FmanTriInfo()
+        self._check(self.hl.dll.lvh_fman_triangulate(self._p, a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp), d.ctypes.data_as(dp),
+                                                     C.byref(info)), "lvh_fman_triangulate")
+        return {k: getattr(info, k) for k, _ in FmanTriInfo._fields_}
+
+    def fill_window(self, marginalizer, optimizer):
+        """fillWindow: `features` and `lidarDepthFlag` of a VinsMarginalizer / VinsWindowOptimizer pair from the table"""
+        self._check(self.hl.dll.lvh_fman_fill_window(self._p, marginalizer._p, optimizer._p), "lvh_fman_fill_window")
+
+    def take_depths(self, marginalizer):
+        """takeDepths: setDepth with the inverse depths the window solve left"""
+        self._check(self.hl.dll.lvh_fman_take_depths(self._p, marginalizer._p), "lvh_fman_take_depths")
+
+    def remove_failures(self):
+        self._check(self.hl.dll.lvh_fman_remove_failures(self._p), "lvh_fman_remove_failures")
+
+    def slide_old(self, shift_depth, back_R0=None, back_P0=None, Rs0=None, Ps0=None, ric=None, tic=None):
+        """slideWindowOld (estimator.cpp:1082-1099)"""
+        dp = C.POINTER(C.c_double)
+        if not shift_depth:
+            return self._check(self.hl.dll.lvh_fman_slide_old(self._p, 0, None, None, None, None, None, None), "lvh_fman_slide_old")
+        arrs = [np.ascontiguousarray(x, np.float64) for x in (back_R0, back_P0, Rs0, Ps0, ric, tic)]
+        assert [x.size for x in arrs] == [9, 3, 9, 3, 9, 3]
+        return self._check(self.hl.dll.lvh_fman_slide_old(self._p, 1, *[x.ctypes.data_as(dp) for x in arrs]), "lvh_fman_slide_old")
+
+    def slide_new(self, frame_count=10):
+        """slideWindowNew (estimator.cpp:1076-1080)"""
+        self._check(self.hl.dll.lvh_fman_slide_new(self._p, int(frame_count)), "lvh_fman_slide_new")
 
 
 class TrackerRig:
