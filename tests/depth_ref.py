@@ -142,6 +142,60 @@ def knn3(oracle, sphere, V):
     return idx3, sqd[:, :3]
 
 
+def brute_knn3(sphere, V):
+    """exact 3-NN by exhaustive search: f32 squared distances in FLANN's L2_Simple order (dx*dx + dy*dy) + dz*dz, NaN
+    distances dropped, ordered by the distance's bits first and the sphere index second; padded with -1 / -1.0"""
+    S = np.ascontiguousarray(sphere, np.float32).reshape(len(sphere), -1)[:, :3]
+    q = np.ascontiguousarray(V, np.float32).reshape(-1, 3)
+    idx = np.full((len(q), 3), -1, np.int32)
+    sqd = np.full((len(q), 3), -1.0, np.float32)
+    if len(S) == 0 or len(q) == 0:
+        return idx, sqd
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    j = np.arange(len(S), dtype=np.uint64)
+    step = max(1, (1 << 22) // len(S))
+    for b in range(0, len(q), step):
+        v = q[b:b + step]
+        with np.errstate(all="ignore"):
+            dx, dy, dz = (v[:, k, None] - S[None, :, k] for k in range(3))
+            d = (dx * dx + dy * dy) + dz * dz
+        key = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | j[None, :]   # d >= 0: its bits order like its value
+        key[np.isnan(d)] = none
+        if key.shape[1] < 3:
+            key = np.concatenate([key, np.full((len(v), 3 - key.shape[1]), none, np.uint64)], 1)
+        best = np.sort(np.partition(key, 2, axis=1)[:, :3], axis=1)
+        ok = best != none
+        idx[b:b + step] = np.where(ok, (best & np.uint64(0xFFFFFFFF)).astype(np.int64), -1)
+        sqd[b:b + step] = np.where(ok, (best >> np.uint64(32)).astype(np.uint32).view(np.float32), F32(-1.0))
+    return idx, sqd
+
+
+def accepted(nbr, sqd):
+    """step 6's test: three neighbours and the third below the threshold"""
+    return (nbr >= 0).all(1) & (sqd[:, 2] < DIST_SQ_THRESHOLD)
+
+
+def check_search(sphere, V, nbr, sqd, depth, full):
+    """a device search (nbr, sqd, depth) against the exhaustive one on the device's own sphere cloud [n, 4].  Full
+    search: every neighbour and distance bit.  Band: the same for every feature either side accepts; where both reject,
+    the band's third distance is not below the true one.  Every accepted feature's depth is intersect() of the device's
+    own neighbours, bit for bit; every other depth is -1.  Returns the accepted mask."""
+    V = np.ascontiguousarray(V, np.float32).reshape(-1, 3)
+    b_nbr, b_sqd = brute_knn3(sphere, V)
+    acc = accepted(nbr, sqd)
+    both = acc | accepted(b_nbr, b_sqd)
+    must = np.ones(len(V), bool) if full else both
+    bad = np.nonzero(must & ((nbr != b_nbr).any(1) | (sqd.view(np.uint32) != b_sqd.view(np.uint32)).any(1)))[0]
+    assert len(bad) == 0, (bad[:5], nbr[bad[:5]], b_nbr[bad[:5]], sqd[bad[:5]], b_sqd[bad[:5]])
+    third = lambda n, s: np.where(n[:, 2] >= 0, s[:, 2], F32(np.inf))  # noqa: E731   (no third neighbour: beyond any distance)
+    assert not (third(nbr, sqd)[~both] < third(b_nbr, b_sqd)[~both]).any()
+    want = np.full(len(V), -1.0, np.float32)
+    for i in np.nonzero(acc)[0]:
+        want[i] = intersect(sphere, nbr[i], V[i])
+    assert np.array_equal(depth.view(np.uint32), want.view(np.uint32)), np.nonzero(depth.view(np.uint32) != want.view(np.uint32))[0][:5]
+    return acc
+
+
 def intersect(sphere, nbr, V):
     """step 7 for one feature whose 3 neighbours were accepted: the published depth (> 3.0, else -1)"""
     P = [sphere[k] for k in nbr]
