@@ -206,12 +206,11 @@ int bit_width(unsigned v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- the handle
-struct lvi_bow {
+struct lvi_bow : Handle {                   // on the store's device and stream (sv)
     lvi_kf* store = nullptr;
     KfStoreView sv;
     int K = 0, max_entries = 0, size = 0;
     int n_nodes = 0, n_words = 0, max_depth = 0, accumulate = 0, sort_passes = 0;
-    Arena arena;
     int *d_child_begin = nullptr, *d_child_count = nullptr, *d_node_word = nullptr;
     double* d_node_weight = nullptr;
     ulonglong2* d_node_desc = nullptr;
@@ -230,8 +229,9 @@ struct lvi_bow {
     int staged_slot = -1;
     uint64_t staged_gen = 0;
 
-    template <class A> void layout(A& a)
+    template <class A, class B> void layout(A& a, B& pin)
     {
+        h_out = pin.template alloc<char>(sizeof(lvi_bow_result) * LVI_BOW_MAX_RESULTS + 64);
         d_child_begin = a.template alloc<int>(n_nodes);
         d_child_count = a.template alloc<int>(n_nodes);
         d_node_word = a.template alloc<int>(n_nodes);
@@ -301,17 +301,13 @@ int32_t lvi_bow_create(lvi_kf* store, const void* vocab, int64_t vocab_bytes, in
     std::string err;
     const int pst = lvi_bowvoc::parse_vocab(vocab, vocab_bytes, fv, err);
     if (pst != lvi_bowvoc::VOCAB_OK) return fail(pst, err);
-    lvi_bow* h = new lvi_bow();
-    h->store = store; h->sv = sv; h->K = sv.max_keypoints; h->max_entries = max_entries;
-    h->n_nodes = fv.n_nodes; h->n_words = fv.n_words; h->max_depth = fv.max_depth; h->accumulate = fv.accumulates() ? 1 : 0;
     const int nbits = bit_width((unsigned)fv.n_words);                           // keys are 0 .. n_words, the last one the stopped words'
-    h->sort_passes = (nbits + 7) / 8;
-    const int32_t st = guarded(sv.device, [&]() -> int32_t {
-        ArenaSizer sz;
-        h->layout(sz);
-        h->arena.init(sz.used);
-        h->layout(h->arena);
-        LVI_HIP(hipHostMalloc((void**)&h->h_out, sizeof(lvi_bow_result) * LVI_BOW_MAX_RESULTS + 64, hipHostMallocDefault));
+    return create_handle(sv.device, out, lvi_bow_destroy, [&](lvi_bow* h) {
+        h->store = store; h->sv = sv; h->K = sv.max_keypoints; h->max_entries = max_entries;
+        h->n_nodes = fv.n_nodes; h->n_words = fv.n_words; h->max_depth = fv.max_depth; h->accumulate = fv.accumulates() ? 1 : 0;
+        h->sort_passes = (nbits + 7) / 8;
+    }, [&](lvi_bow* h) -> int32_t {
+        h->open(sv.device, [&](auto& dev, auto& pin) { h->layout(dev, pin); }, 0, sv.stream);
         const size_t n = (size_t)fv.n_nodes;
         const int zero = 0;
         LVI_HIP(hipMemcpyAsync(h->d_child_begin, fv.child_begin.data(), 4 * n, hipMemcpyHostToDevice, sv.stream));
@@ -325,18 +321,12 @@ int32_t lvi_bow_create(lvi_kf* store, const void* vocab, int64_t vocab_bytes, in
         LVI_HIP(hipStreamSynchronize(sv.stream));                                // the host arrays die with this call
         return LVI_OK;
     });
-    if (st != LVI_OK) { lvi_bow_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
 }
 
 void lvi_bow_destroy(lvi_bow* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->sv.device);
-    if (h->sv.stream) (void)hipStreamSynchronize(h->sv.stream);
-    h->arena.release();
-    if (h->h_out) (void)hipHostFree(h->h_out);
+    h->close();
     delete h;
 }
 

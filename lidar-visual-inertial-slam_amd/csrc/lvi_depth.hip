@@ -280,18 +280,17 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_depth_kernel(const float* fea
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- the handle
-struct lvi_depth {
-    int device = 0, C = 0, P = 0, F = 0, skip = 0;
+struct lvi_depth : Handle {
+    int C = 0, P = 0, F = 0, skip = 0;
     double window = 5.0;
-    Ctx ctx;
-    Arena arena;
+    Ctx ctx;                               // ctx.stream is the handle's stream
     VoxelPlan vox1, vox2;
     lvi_pt *rawIn = nullptr, *vOut = nullptr, *ring = nullptr, *fused = nullptr, *cloud = nullptr, *sphere = nullptr;
     int *ringN = nullptr, *blkCnt = nullptr, *fusedN = nullptr, *cloudN = nullptr, *rowN = nullptr, *rowOff = nullptr, *nsph = nullptr, *nbr = nullptr;
     unsigned long long* range = nullptr;
     float *feat = nullptr, *depth = nullptr, *nsqd = nullptr;
     float* h_io = nullptr;                 // pinned: features in, depths out
-    int* h_cnt = nullptr;                  // pinned: [0] depth cloud size
+    int* h_cnt = nullptr;                  // pinned [16]: [0] depth cloud size
     // host state of the window
     int lidar_count = -1, used_total = 0, cloud_n = 0, fused_n_last = 0;
     std::deque<int> slots;
@@ -303,9 +302,10 @@ struct lvi_depth {
 
 namespace {
 
-template <class AR> void depth_layout(AR& ar, lvi_depth& h)
+template <class AR, class PIN> void depth_layout(AR& ar, PIN& pin, lvi_depth& h)
 {
     const size_t W = (size_t)h.C * h.P;
+    h.h_io = pin.template alloc<float>((size_t)3 * h.F); h.h_cnt = pin.template alloc<int>(16);
     h.rawIn = ar.template alloc<lvi_pt>(h.P); h.vOut = ar.template alloc<lvi_pt>(h.P);
     h.ring = ar.template alloc<lvi_pt>(W); h.ringN = ar.template alloc<int>(h.C);
     h.blkCnt = ar.template alloc<int>(div_up(h.P, FOV_BLOCK));
@@ -390,18 +390,13 @@ int32_t lvi_depth_create(int32_t device, int32_t max_clouds, int32_t max_cloud_p
     if (max_clouds < 1 || max_clouds > LVI_DEPTH_MAX_CLOUDS) return fail(LVI_ERR_INVALID_ARG, "max_clouds must be 1..LVI_DEPTH_MAX_CLOUDS");
     if (max_cloud_points < 1 || max_features < 1 || lidar_skip < 0 || !(window_s >= 0.0)) return fail(LVI_ERR_INVALID_ARG, "bad capacities");
     if ((long long)max_clouds * max_cloud_points > (1 << 25) || max_features > (1 << 20)) return fail(LVI_ERR_INVALID_ARG, "capacities above 2^25 window points are not supported");
-    if (const int32_t bad = check_device(device)) return bad;
-    lvi_depth* h = new lvi_depth();
-    h->device = device; h->C = max_clouds; h->P = max_cloud_points; h->F = max_features; h->skip = lidar_skip; h->window = window_s;
-    // float dist_sq_threshold = pow(sin(bin_res / 180.0 * M_PI) * 5.0, 2)
-    h->thr = (float)std::pow(std::sin((double)BIN_RES / 180.0 * M_PI) * 5.0, 2);
-    const int32_t st = guarded(h->device, [&]() -> int32_t {
-        LVI_HIP(hipStreamCreateWithFlags(&h->ctx.stream, hipStreamNonBlocking));
-        ArenaSizer sz; depth_layout(sz, *h);
-        h->arena.init(sz.used + (1 << 16));
-        depth_layout(h->arena, *h);
-        LVI_HIP(hipHostMalloc((void**)&h->h_io, sizeof(float) * 3 * (size_t)h->F, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_cnt, 64, hipHostMallocDefault));
+    return create_handle(device, out, lvi_depth_destroy, [&](lvi_depth* h) {
+        h->C = max_clouds; h->P = max_cloud_points; h->F = max_features; h->skip = lidar_skip; h->window = window_s;
+        // float dist_sq_threshold = pow(sin(bin_res / 180.0 * M_PI) * 5.0, 2)
+        h->thr = (float)std::pow(std::sin((double)BIN_RES / 180.0 * M_PI) * 5.0, 2);
+    }, [&](lvi_depth* h) -> int32_t {
+        h->open(device, [&](auto& dev, auto& pin) { depth_layout(dev, pin, *h); }, 1 << 16);
+        h->ctx.stream = h->stream;
         VoxSegStatic s1{h->rawIn, nullptr, h->vOut, 0.2f}, s2{h->fused, nullptr, h->cloud, 0.2f};
         h->vox1.set_static(h->ctx, &s1);
         h->vox2.set_static(h->ctx, &s2);
@@ -411,21 +406,15 @@ int32_t lvi_depth_create(int32_t device, int32_t max_clouds, int32_t max_cloud_p
         wait(h);
         return LVI_OK;
     });
-    if (st != LVI_OK) { lvi_depth_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
 }
 
 void lvi_depth_destroy(lvi_depth* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->ctx.stream) (void)hipStreamSynchronize(h->ctx.stream);
-    h->vox1.release(); h->vox2.release();
-    if (h->h_io) (void)hipHostFree(h->h_io);
-    if (h->h_cnt) (void)hipHostFree(h->h_cnt);
-    h->arena.release();
-    if (h->ctx.stream) (void)hipStreamDestroy(h->ctx.stream);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->vox1.release(); h->vox2.release();                       // before the arena goes
+    h->close();
     delete h;
 }
 

@@ -105,17 +105,25 @@ struct LaunchScope {
         LVI_HIP(hipGetLastError());                             \
     } while (0)
 
-// bump allocator over one hipMalloc (all buffers live as long as the handle)
-struct Arena {
+// bump allocation out of one block (all buffers live as long as the handle); every buffer starts 256-byte aligned
+struct Bump {
     char* base = nullptr; size_t size = 0, used = 0;
-    void init(size_t bytes) { LVI_HIP(hipMalloc((void**)&base, bytes)); size = bytes; used = 0; }
     template <class T> T* alloc(size_t n)
     {
         size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
         if (used + bytes > size) throw HipError{hipErrorOutOfMemory, "arena exhausted", __FILE__, __LINE__};
         T* p = reinterpret_cast<T*>(base + used); used += bytes; return p;
     }
+};
+// over one hipMalloc
+struct Arena : Bump {
+    void init(size_t bytes) { LVI_HIP(hipMalloc((void**)&base, bytes)); size = bytes; used = 0; }
     void release() { if (base) (void)hipFree(base); base = nullptr; }
+};
+// over one hipHostMalloc: the pinned staging buffers of a handle
+struct PinnedArena : Bump {
+    void init(size_t bytes) { LVI_HIP(hipHostMalloc((void**)&base, std::max<size_t>(bytes, 256), hipHostMallocDefault)); size = bytes; used = 0; }
+    void release() { if (base) (void)hipHostFree(base); base = nullptr; }
 };
 // sizing pass: same calls, no memory
 struct ArenaSizer {
@@ -123,8 +131,60 @@ struct ArenaSizer {
     template <class T> T* alloc(size_t n) { used += (n * sizeof(T) + 255) & ~size_t(255); return nullptr; }
 };
 
+// a device array and its pinned mirror, carved together: the size is written once
+template <class T, class A, class B> void alloc_pair(A& dev, B& pin, T*& d, T*& h, size_t n) { d = dev.template alloc<T>(n); h = pin.template alloc<T>(n); }
+
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }   // byte offsets of the parts of one buffer
+
+// What every stand-alone handle is made of: a device, one stream, one device arena and one pinned arena.
+// open() runs inside guarded(): it creates the non-blocking stream unless the handle borrows one, runs layout(dev, pin)
+// with two sizers, allocates both arenas (`slack` bytes of headroom on the device side) and runs layout again over the
+// memory, so a buffer's size is written once, where it is carved.  close() tolerates a handle whose open() stopped
+// anywhere: it waits for the stream if there is one, frees what was allocated and destroys only a stream open() created.
+struct Handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    Arena arena;
+    PinnedArena pinned;
+
+    template <class Layout> void open(int dev, Layout&& layout, size_t slack = 0, hipStream_t borrowed_stream = nullptr)
+    {
+        device = dev;
+        if (borrowed_stream) stream = borrowed_stream;
+        else { LVI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); own_stream = true; }
+        ArenaSizer sd, sp;
+        layout(sd, sp);
+        arena.init(sd.used + slack);
+        pinned.init(sp.used);
+        layout(arena, pinned);
+    }
+    void close()
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        arena.release();
+        pinned.release();
+        if (own_stream) (void)hipStreamDestroy(stream);
+        stream = nullptr; own_stream = false;
+    }
+};
+
+// The body of every *_create after its argument checks: the device check, a new H, the caller's field setup, then
+// open_fn(h) under the guard, which opens the handle on that device and does what else the handle needs before its first
+// call; a failure destroys the handle and leaves *out null.
+template <class H, class Setup, class Open>
+int32_t create_handle(int device, H** out, void (*destroy)(H*), Setup&& setup, Open&& open_fn)
+{
+    if (const int32_t bad = check_device(device)) return bad;
+    H* h = new H();
+    setup(h);
+    const int32_t st = guarded(device, [&]() -> int32_t { return open_fn(h); });
+    if (st != LVI_OK) { destroy(h); return st; }
+    *out = h;
+    return LVI_OK;
+}
 
 // Batched launches: one launch sequence serves up to LVI_MAX_BATCH independent scans (SURVEY §7.3-6 i).  Every kernel
 // of the lidar path takes the argument blocks of all scans of the batch and picks its own by blockIdx.z, so a batch of S

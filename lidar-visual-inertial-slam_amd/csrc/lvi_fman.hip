@@ -15,8 +15,10 @@
 #include "../../include/lvi_fman.h"
 #include "lvi_dev.hpp"
 #include "lvi_fman_math.hpp"
+#include "lvi_winsys.hpp"
 
 using namespace lvi;
+using lvi_winsys::finite_all;
 namespace fm = lvi_fman_math;
 
 static_assert(sizeof(lvi_fman_obs) == 72 && sizeof(lvi_fman_feature) == 824, "lvi_fman_feature layout");
@@ -307,11 +309,9 @@ __global__ __launch_bounds__(64) void fman_triangulate(lvi_fman_feature* tab, in
 
 }  // namespace
 
-struct lvi_fman {
-    int device = 0, max_features = 0;
+struct lvi_fman : Handle {
+    int max_features = 0;
     lvi_fman_params P{};
-    hipStream_t stream = nullptr;
-    Arena arena;
     lvi_fman_feature* tab[2] = {nullptr, nullptr};
     int cur = 0;
     int32_t* d_ids = nullptr; double* d_obs = nullptr; double* d_x = nullptr; Summary* d_sum = nullptr;
@@ -325,16 +325,17 @@ namespace {
 size_t rec_room(int mf) { return align256(sizeof(lvi_marg_projection) * (size_t)mf * LVI_FMAN_WINDOW); }
 size_t out_room(int mf) { return std::max(rec_room(mf) + align256(8 * (size_t)mf) + align256(4 * (size_t)mf), sizeof(lvi_fman_feature) * (size_t)mf); }
 
-template <class A> void carve(A& a, lvi_fman* h)
+template <class A, class B> void carve(A& a, B& pin, lvi_fman* h)
 {
     const size_t mf = (size_t)h->max_features;
+    h->out_bytes = out_room(h->max_features);
     h->tab[0] = a.template alloc<lvi_fman_feature>(mf);
     h->tab[1] = a.template alloc<lvi_fman_feature>(mf);
-    h->d_ids = a.template alloc<int32_t>(MAXF);
-    h->d_obs = a.template alloc<double>(8 * (size_t)MAXF);
-    h->d_x = a.template alloc<double>(mf);
-    h->d_sum = a.template alloc<Summary>(1);
-    h->d_out = a.template alloc<char>(out_room(h->max_features));
+    alloc_pair(a, pin, h->d_ids, h->h_ids, MAXF);
+    alloc_pair(a, pin, h->d_obs, h->h_obs, 8 * (size_t)MAXF);
+    alloc_pair(a, pin, h->d_x, h->h_x, mf);
+    alloc_pair(a, pin, h->d_sum, h->h_sum, 1);
+    alloc_pair(a, pin, h->d_out, h->h_out, h->out_bytes);
 }
 
 // after the call's one wait: an error met on the device leaves the host's counts as they were
@@ -358,12 +359,6 @@ int32_t run_compact(lvi_fman* h, int op, const ShiftArgs& a)
         h->cur ^= 1;
         return settle(h, "compaction");
     });
-}
-
-bool finite_all(const double* v, int n)
-{
-    for (int k = 0; k < n; k++) if (!std::isfinite(v[k])) return false;
-    return true;
 }
 
 int32_t depth_io(lvi_fman* h, int what, int32_t n, const double* x)
@@ -399,38 +394,15 @@ int32_t lvi_fman_create(int32_t device, int32_t max_features, lvi_fman** out)
     if (!out) return fail(LVI_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     if (max_features < 1 || max_features > LVI_FMAN_MAX_FEATURES) return fail(LVI_ERR_INVALID_ARG, "max_features is outside 1..LVI_FMAN_MAX_FEATURES");
-    if (const int32_t bad = check_device(device)) return bad;
-    lvi_fman* h = new lvi_fman();
-    h->device = device; h->max_features = max_features;
-    lvi_fman_params_default(&h->P);
-    const int32_t st = guarded(h->device, [&]() -> int32_t {
-        LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        ArenaSizer sz;
-        carve(sz, h);
-        h->arena.init(sz.used);
-        carve(h->arena, h);
-        h->out_bytes = out_room(max_features);
-        LVI_HIP(hipHostMalloc((void**)&h->h_ids, sizeof(int32_t) * MAXF, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_obs, sizeof(double) * 8 * MAXF, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_x, sizeof(double) * (size_t)max_features, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_sum, sizeof(Summary), hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_out, h->out_bytes, hipHostMallocDefault));
-        return LVI_OK;
-    });
-    if (st != LVI_OK) { lvi_fman_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
+    return create_handle(device, out, lvi_fman_destroy,
+        [&](lvi_fman* h) { h->max_features = max_features; lvi_fman_params_default(&h->P); },
+        [&](lvi_fman* h) -> int32_t { h->open(device, [&](auto& dev, auto& pin) { carve(dev, pin, h); }); return LVI_OK; });
 }
 
 void lvi_fman_destroy(lvi_fman* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->arena.release();
-    for (void* p : {(void*)h->h_ids, (void*)h->h_obs, (void*)h->h_x, (void*)h->h_sum, (void*)h->h_out})
-        if (p) (void)hipHostFree(p);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 

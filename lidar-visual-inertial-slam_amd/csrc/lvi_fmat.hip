@@ -413,6 +413,7 @@ Staged stage_set(char* h_in, const Layout& L, int I, int check, const float* pts
 struct HypBufs {
     double* F = nullptr;                   // [I][27]
     int *nm = nullptr, *score = nullptr;   // [I], [I][3]
+    template <class A> void carve(A& a, size_t I) { F = a.template alloc<double>(27 * I); nm = a.template alloc<int>(I); score = a.template alloc<int>(3 * I); }
 };
 
 HypArgs hyp_args(const Staged& g, const Layout& L, const char* d_in, const HypBufs& b)
@@ -455,22 +456,15 @@ int32_t lvi_fmat_create(int32_t device, int32_t max_points, int32_t max_iters, l
     *out = nullptr;
     if (max_points < MODEL_POINTS || max_points > LVI_FMAT_MAX_POINTS) return fail(LVI_ERR_INVALID_ARG, "max_points must be 7..LVI_FMAT_MAX_POINTS");
     if (max_iters < 1 || max_iters > LVI_FMAT_MAX_ITERS) return fail(LVI_ERR_INVALID_ARG, "max_iters must be 1..LVI_FMAT_MAX_ITERS");
-    lvi_fmat* h = new lvi_fmat();
-    h->P = max_points; h->I = max_iters;
-    h->L.set(h->P, h->I);
-    const int32_t st = h->io.open(device, h->L.in_bytes, h->L.out_bytes,
-                                  {{(void**)&h->hb.F, sizeof(double) * 27 * (size_t)h->I},
-                                   {(void**)&h->hb.nm, sizeof(int) * (size_t)h->I},
-                                   {(void**)&h->hb.score, sizeof(int) * 3 * (size_t)h->I}});
-    if (st != LVI_OK) { lvi_fmat_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
+    return create_handle(device, out, lvi_fmat_destroy,
+        [&](lvi_fmat* h) { h->P = max_points; h->I = max_iters; h->L.set(h->P, h->I); },
+        [&](lvi_fmat* h) -> int32_t { h->io.open(device, h->L.in_bytes, h->L.out_bytes, [&](auto& a) { h->hb.carve(a, (size_t)h->I); }); return LVI_OK; });
 }
 
 void lvi_fmat_destroy(lvi_fmat* h)
 {
     if (!h) return;
-    h->io.close({h->hb.F, h->hb.nm, h->hb.score});
+    h->io.close();
     delete h;
 }
 
@@ -541,23 +535,21 @@ int32_t lvi_fmatb_create(int32_t device, int32_t slots, int32_t max_points, int3
     if (slots < 1 || slots > LVI_TRACKER_MAX_BATCH) return fail(LVI_ERR_INVALID_ARG, "slots must be 1..LVI_TRACKER_MAX_BATCH");
     if (max_points < MODEL_POINTS || max_points > LVI_FMAT_MAX_POINTS) return fail(LVI_ERR_INVALID_ARG, "max_points must be 7..LVI_FMAT_MAX_POINTS");
     if (max_iters < 1 || max_iters > LVI_FMAT_MAX_ITERS) return fail(LVI_ERR_INVALID_ARG, "max_iters must be 1..LVI_FMAT_MAX_ITERS");
-    lvi_fmatb* h = new lvi_fmatb();
-    h->S = slots; h->P = max_points; h->I = max_iters;
-    h->L.set(h->P, h->I);
-    h->off_set = align256(sizeof(WalkRec));
-    h->in_stride = h->off_set + h->L.in_bytes;
-    const size_t SI = (size_t)slots * (size_t)h->I;
-    const int32_t st = h->io.open(device, h->in_stride * (size_t)slots, h->L.out_bytes * (size_t)slots,
-                                  {{(void**)&h->hb.F, sizeof(double) * 27 * SI}, {(void**)&h->hb.nm, sizeof(int) * SI}, {(void**)&h->hb.score, sizeof(int) * 3 * SI}});
-    if (st != LVI_OK) { lvi_fmatb_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
+    return create_handle(device, out, lvi_fmatb_destroy, [&](lvi_fmatb* h) {
+        h->S = slots; h->P = max_points; h->I = max_iters;
+        h->L.set(h->P, h->I);
+        h->off_set = align256(sizeof(WalkRec));
+        h->in_stride = h->off_set + h->L.in_bytes;
+    }, [&](lvi_fmatb* h) -> int32_t {
+        h->io.open(device, h->in_stride * (size_t)slots, h->L.out_bytes * (size_t)slots, [&](auto& a) { h->hb.carve(a, (size_t)slots * (size_t)h->I); });
+        return LVI_OK;
+    });
 }
 
 void lvi_fmatb_destroy(lvi_fmatb* h)
 {
     if (!h) return;
-    h->io.close({h->hb.F, h->hb.nm, h->hb.score});
+    h->io.close();
     delete h;
 }
 

@@ -257,10 +257,8 @@ struct Slot {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- the handle
-struct lvi_kf {
-    int device = 0, W = 0, H = 0, K = 0, Wn = 0, S = 0;
-    hipStream_t stream = nullptr;
-    Arena arena;
+struct lvi_kf : Handle {
+    int W = 0, H = 0, K = 0, Wn = 0, S = 0;
     char* d_in = nullptr;                  // window xy [Wn][2] | image (tightly packed)
     char* h_in = nullptr;                  // pinned mirror of d_in
     size_t off_img = 0, in_bytes = 0;
@@ -272,9 +270,10 @@ struct lvi_kf {
     std::vector<Slot> slots;
     int last_w = 0, last_h = 0;
 
-    template <class A> void layout(A& a)
+    template <class A, class B> void layout(A& a, B& pin)
     {
-        d_in = a.template alloc<char>(in_bytes);
+        alloc_pair(a, pin, d_in, h_in, in_bytes);
+        h_out = pin.template alloc<char>(256 + match_bytes);
         d_blur = a.template alloc<uint8_t>((size_t)W * H);
         d_score = a.template alloc<uint8_t>((size_t)W * H);
         d_row_count = a.template alloc<int>(H);
@@ -338,39 +337,26 @@ int32_t lvi_kf_create(int32_t device, int32_t max_width, int32_t max_height, int
             if (v[k] < -LVI_KF_PATTERN_MAX || v[k] > LVI_KF_PATTERN_MAX) return fail(LVI_ERR_INVALID_ARG, "pattern offset beyond +-24");
         pattern[i] = (v[0] & 0xFF) | ((v[1] & 0xFF) << 8) | ((v[2] & 0xFF) << 16) | ((v[3] & 0xFF) << 24);
     }
-    if (const int32_t bad = check_device(device)) return bad;
-    lvi_kf* h = new lvi_kf();
-    h->device = device; h->W = max_width; h->H = max_height; h->K = max_keypoints; h->Wn = max_window; h->S = max_keyframes;
-    h->slots.resize(max_keyframes);
-    h->off_img = align256(sizeof(float) * 2 * (size_t)h->Wn);
-    h->in_bytes = h->off_img + (size_t)h->W * h->H;
-    h->match_bytes = 9 * (size_t)h->Wn;
-    const int32_t st = guarded(h->device, [&]() -> int32_t {
-        LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        ArenaSizer sz;
-        h->layout(sz);
-        h->arena.init(sz.used);
-        h->layout(h->arena);
-        LVI_HIP(hipHostMalloc((void**)&h->h_in, h->in_bytes, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_out, 256 + h->match_bytes, hipHostMallocDefault));
-        LVI_HIP(hipMemcpyAsync(h->d_pattern, pattern, sizeof(pattern), hipMemcpyHostToDevice, h->stream));
-        LVI_HIP(hipStreamSynchronize(h->stream));
-        return LVI_OK;
-    });
-    if (st != LVI_OK) { lvi_kf_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
+    return create_handle(device, out, lvi_kf_destroy,
+        [&](lvi_kf* h) {
+            h->W = max_width; h->H = max_height; h->K = max_keypoints; h->Wn = max_window; h->S = max_keyframes;
+            h->slots.resize(max_keyframes);
+            h->off_img = align256(sizeof(float) * 2 * (size_t)h->Wn);
+            h->in_bytes = h->off_img + (size_t)h->W * h->H;
+            h->match_bytes = 9 * (size_t)h->Wn;
+        },
+        [&](lvi_kf* h) -> int32_t {
+            h->open(device, [&](auto& dev, auto& pin) { h->layout(dev, pin); });
+            LVI_HIP(hipMemcpyAsync(h->d_pattern, pattern, sizeof(pattern), hipMemcpyHostToDevice, h->stream));
+            LVI_HIP(hipStreamSynchronize(h->stream));
+            return LVI_OK;
+        });
 }
 
 void lvi_kf_destroy(lvi_kf* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->arena.release();
-    if (h->h_in) (void)hipHostFree(h->h_in);
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 

@@ -267,12 +267,9 @@ struct Prior { bool valid = false; int m = 0, n = 0; std::vector<int> ids, sizes
 
 }  // namespace
 
-struct lvi_marg {
-    int device = 0;
+struct lvi_marg : Handle {
     lvi_marg_caps caps{};
     lvi_marg_params P{};
-    hipStream_t stream = nullptr;
-    Arena arena;
     Dev d{};
     double *d_vals = nullptr, *d_J[2] = {nullptr, nullptr}, *d_r[2] = {nullptr, nullptr}, *d_x[2] = {nullptr, nullptr};
     ProjDev* d_proj = nullptr; PriorBlk* d_pb = nullptr; int* d_keepblk = nullptr;
@@ -297,24 +294,24 @@ int max_chunks(const lvi_marg* h)
     return div_up(h->caps.max_projections, SHARE) + div_up(h->caps.max_dense_rows + h->caps.max_keep_dim, CH_ROWS) + 1;
 }
 
-template <class A> void carve(A& a, lvi_marg* h)
+template <class A, class B> void carve(A& a, B& pin, lvi_marg* h)
 {
     const size_t Pm = (size_t)Pmax(h), mm = (size_t)h->caps.max_drop_dim, nn = (size_t)h->caps.max_keep_dim, R = (size_t)h->caps.max_dense_rows + nn;
     Dev& d = h->d;
-    h->d_vals = a.template alloc<double>((size_t)VAL * h->caps.max_blocks);
-    h->d_proj = a.template alloc<ProjDev>((size_t)h->caps.max_projections);
+    alloc_pair(a, pin, h->d_vals, h->h_vals, (size_t)VAL * h->caps.max_blocks);
+    alloc_pair(a, pin, h->d_proj, h->h_proj, (size_t)h->caps.max_projections);
     d.Jf = a.template alloc<double>((size_t)JF * h->caps.max_projections);
-    d.E = a.template alloc<double>(R * Pm);
+    alloc_pair(a, pin, d.E, h->h_E, R * Pm);
     d.part = a.template alloc<double>((size_t)max_chunks(h) * Pm * Pm);
-    d.A = a.template alloc<double>(Pm * Pm);
+    alloc_pair(a, pin, d.A, h->h_out, Pm * Pm);
     d.Wm = a.template alloc<double>(mm * mm); d.Vm = a.template alloc<double>(mm * mm); d.Minv = a.template alloc<double>(mm * mm);
     d.T = a.template alloc<double>(mm * (nn + 1)); d.Rf = a.template alloc<double>(mm * (nn + 1)); d.S = a.template alloc<double>(nn * (nn + 1));
     d.Wn = a.template alloc<double>(nn * nn); d.Vn = a.template alloc<double>(nn * nn);
     for (int k = 0; k < 2; k++) {
         h->d_J[k] = a.template alloc<double>(nn * nn); h->d_r[k] = a.template alloc<double>(nn); h->d_x[k] = a.template alloc<double>((size_t)VAL * nn);
     }
-    h->d_pb = a.template alloc<PriorBlk>(nn); h->d_keepblk = a.template alloc<int>(nn);
-    d.info = a.template alloc<DevInfo>(1);
+    alloc_pair(a, pin, h->d_pb, h->h_pb, nn); alloc_pair(a, pin, h->d_keepblk, h->h_keepblk, nn);
+    alloc_pair(a, pin, d.info, h->h_info, 1);
 }
 
 bool params_ok(const lvi_marg_params& p)
@@ -369,40 +366,15 @@ int32_t lvi_marg_create(int32_t device, const lvi_marg_caps* caps, lvi_marg** ou
         c.max_dense_factors < 0 || c.max_dense_factors > LVI_MARG_MAX_DENSE_FACTORS || c.max_dense_rows < 0 || c.max_dense_rows > LVI_MARG_MAX_DENSE_ROWS ||
         c.max_drop_dim < 1 || c.max_drop_dim > LVI_MARG_MAX_DROP_DIM || c.max_keep_dim < 1 || c.max_keep_dim > LVI_MARG_MAX_KEEP_DIM)
         return fail(LVI_ERR_INVALID_ARG, "a capacity is outside 1..LVI_MARG_MAX_*");
-    if (const int32_t bad = check_device(device)) return bad;
-    lvi_marg* h = new lvi_marg();
-    h->device = device; h->caps = c;
-    lvi_marg_params_default(&h->P);
-    const int32_t st = guarded(h->device, [&]() -> int32_t {
-        LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        ArenaSizer sz;
-        carve(sz, h);
-        h->arena.init(sz.used);
-        carve(h->arena, h);
-        const size_t Pm = (size_t)Pmax(h), nn = (size_t)c.max_keep_dim;
-        LVI_HIP(hipHostMalloc((void**)&h->h_vals, sizeof(double) * VAL * c.max_blocks, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_E, sizeof(double) * std::max<size_t>(1, (size_t)c.max_dense_rows) * Pm, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_proj, sizeof(ProjDev) * c.max_projections, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_pb, sizeof(PriorBlk) * nn, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_keepblk, sizeof(int) * nn, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_info, 256, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_out, sizeof(double) * Pm * Pm, hipHostMallocDefault));
-        return LVI_OK;
-    });
-    if (st != LVI_OK) { lvi_marg_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
+    return create_handle(device, out, lvi_marg_destroy,
+        [&](lvi_marg* h) { h->caps = c; lvi_marg_params_default(&h->P); },
+        [&](lvi_marg* h) -> int32_t { h->open(device, [&](auto& dev, auto& pin) { carve(dev, pin, h); }); return LVI_OK; });
 }
 
 void lvi_marg_destroy(lvi_marg* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->arena.release();
-    for (void* p : {(void*)h->h_vals, (void*)h->h_E, (void*)h->h_proj, (void*)h->h_pb, (void*)h->h_keepblk, (void*)h->h_info, (void*)h->h_out})
-        if (p) (void)hipHostFree(p);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 

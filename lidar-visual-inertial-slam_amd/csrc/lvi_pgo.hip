@@ -470,12 +470,10 @@ __global__ __launch_bounds__(LOOPS_THREADS) void pgo_finish(Dev d, int which)
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- the handle
-struct lvi_pgo {
-    int device = 0, Ncap = 0, Lcap = 0;
+struct lvi_pgo : Handle {
+    int Ncap = 0, Lcap = 0;
     int N = 0, L = 0, n_up = 0, l_up = 0;          // keys / loops added, and how many of them the device already holds
     lvi_pgo_params P{};
-    hipStream_t stream = nullptr;
-    Arena arena;
     Dev d{};
     // pinned host staging
     Pose *h_X = nullptr, *h_Zc = nullptr, *h_Zl = nullptr, *h_out = nullptr;
@@ -490,13 +488,13 @@ struct lvi_pgo {
 
 namespace {
 
-template <class A> void carve(A& a, lvi_pgo* h)
+template <class A, class B> void carve(A& a, B& pin, lvi_pgo* h)
 {
     const size_t N = (size_t)h->Ncap, L = (size_t)std::max(h->Lcap, 1), M = 6 * (size_t)h->Lcap + 6, n6 = 6 * L;
     Dev& d = h->d;
-    d.X = a.template alloc<Pose>(N);
-    h->d_Zc = a.template alloc<Pose>(N); h->d_Zl = a.template alloc<Pose>(L);
-    h->d_lidx = a.template alloc<int2>(L); h->d_lsw = a.template alloc<double>(L);
+    alloc_pair(a, pin, d.X, h->h_X, N); h->h_out = pin.template alloc<Pose>(N);
+    alloc_pair(a, pin, h->d_Zc, h->h_Zc, N); alloc_pair(a, pin, h->d_Zl, h->h_Zl, L);
+    alloc_pair(a, pin, h->d_lidx, h->h_lidx, L); alloc_pair(a, pin, h->d_lsw, h->h_lsw, L);
     d.JAc = a.template alloc<double>(36 * N); d.JBc = a.template alloc<double>(36 * N); d.rc = a.template alloc<double>(6 * N);
     d.JAl = a.template alloc<double>(36 * L); d.JBl = a.template alloc<double>(36 * L); d.rl = a.template alloc<double>(6 * L);
     d.e2 = a.template alloc<double>(N + L + N);
@@ -504,10 +502,10 @@ template <class A> void carve(A& a, lvi_pgo* h)
     d.Bm = a.template alloc<double>(6 * N * M);
     d.S = a.template alloc<double>(n6 * n6); d.w = a.template alloc<double>(n6 * 6);
     d.delta0 = a.template alloc<double>(6); d.step = a.template alloc<double>(LVI_PGO_MAX_ITERS);
-    d.info = a.template alloc<lvi_pgo_info>(1);
-    h->d_gkey = a.template alloc<int>(N); h->d_goff = a.template alloc<int>(N + 1);
-    h->d_gz = a.template alloc<double>(3 * N); h->d_gsw = a.template alloc<double>(3 * N);
-    d.JG = a.template alloc<double>(18 * N); d.rg = a.template alloc<double>(3 * N); d.cov = a.template alloc<double>(36);
+    alloc_pair(a, pin, d.info, h->h_info, 1);
+    alloc_pair(a, pin, h->d_gkey, h->h_gkey, N); alloc_pair(a, pin, h->d_goff, h->h_goff, N + 1);
+    alloc_pair(a, pin, h->d_gz, h->h_gz, 3 * N); alloc_pair(a, pin, h->d_gsw, h->h_gsw, 3 * N);
+    d.JG = a.template alloc<double>(18 * N); d.rg = a.template alloc<double>(3 * N); alloc_pair(a, pin, d.cov, h->h_cov, 36);
 }
 
 // what add_pose / add_loop staged since the last flush goes to the device (stream order: ahead of whatever reads it)
@@ -611,46 +609,15 @@ int32_t lvi_pgo_create(int32_t device, int32_t max_poses, int32_t max_loops, lvi
     *out = nullptr;
     if (max_poses < 1 || max_poses > LVI_PGO_MAX_POSES) return fail(LVI_ERR_INVALID_ARG, "max_poses must be 1..LVI_PGO_MAX_POSES");
     if (max_loops < 0 || max_loops > LVI_PGO_MAX_LOOPS) return fail(LVI_ERR_INVALID_ARG, "max_loops must be 0..LVI_PGO_MAX_LOOPS");
-    if (const int32_t bad = check_device(device)) return bad;
-    lvi_pgo* h = new lvi_pgo();
-    h->device = device; h->Ncap = max_poses; h->Lcap = max_loops;
-    lvi_pgo_params_default(&h->P);
-    const int32_t st = guarded(h->device, [&]() -> int32_t {
-        LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        ArenaSizer sz;
-        carve(sz, h);
-        h->arena.init(sz.used);
-        carve(h->arena, h);
-        const size_t N = (size_t)h->Ncap, L = (size_t)std::max(h->Lcap, 1);
-        LVI_HIP(hipHostMalloc((void**)&h->h_X, sizeof(Pose) * N, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_Zc, sizeof(Pose) * N, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_out, sizeof(Pose) * N, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_Zl, sizeof(Pose) * L, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_lidx, sizeof(int2) * L, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_lsw, sizeof(double) * L, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_info, align256(sizeof(lvi_pgo_info)), hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_gkey, sizeof(int) * N, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_goff, sizeof(int) * (N + 1), hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_gz, sizeof(double) * 3 * N, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_gsw, sizeof(double) * 3 * N, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_cov, align256(sizeof(double) * 36), hipHostMallocDefault));
-        return LVI_OK;
-    });
-    if (st != LVI_OK) { lvi_pgo_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
+    return create_handle(device, out, lvi_pgo_destroy,
+        [&](lvi_pgo* h) { h->Ncap = max_poses; h->Lcap = max_loops; lvi_pgo_params_default(&h->P); },
+        [&](lvi_pgo* h) -> int32_t { h->open(device, [&](auto& dev, auto& pin) { carve(dev, pin, h); }); return LVI_OK; });
 }
 
 void lvi_pgo_destroy(lvi_pgo* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->arena.release();
-    for (void* p : {(void*)h->h_X, (void*)h->h_Zc, (void*)h->h_out, (void*)h->h_Zl, (void*)h->h_lidx, (void*)h->h_lsw, (void*)h->h_info,
-                    (void*)h->h_gkey, (void*)h->h_goff, (void*)h->h_gz, (void*)h->h_gsw, (void*)h->h_cov})
-        if (p) (void)hipHostFree(p);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 

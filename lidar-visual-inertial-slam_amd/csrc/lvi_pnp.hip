@@ -206,25 +206,24 @@ int32_t lvi_pnp_create(int32_t device, int32_t max_points, int32_t max_iters, lv
     *out = nullptr;
     if (max_points < MODEL_POINTS || max_points > LVI_PNP_MAX_POINTS) return fail(LVI_ERR_INVALID_ARG, "max_points must be 5..LVI_PNP_MAX_POINTS");
     if (max_iters < 1 || max_iters > LVI_PNP_MAX_ITERS) return fail(LVI_ERR_INVALID_ARG, "max_iters must be 1..LVI_PNP_MAX_ITERS");
-    lvi_pnp* h = new lvi_pnp();
-    h->P = max_points; h->I = max_iters;
-    h->off_p2 = align256(sizeof(float) * 3 * (size_t)h->P);
-    h->off_sub = h->off_p2 + align256(sizeof(float) * 2 * (size_t)h->P);
-    h->off_log = h->off_sub + align256(sizeof(int) * MODEL_POINTS * (size_t)h->I);
-    const int32_t st = h->io.open(device, h->off_log + align256(sizeof(double) * ((size_t)h->P + 1)), align256(sizeof(lvi_pnp_info)) + align256((size_t)h->P),
-                                  {{(void**)&h->d_Rt, sizeof(double) * 12 * (size_t)h->I},
-                                   {(void**)&h->d_has, sizeof(int) * (size_t)h->I},
-                                   {(void**)&h->d_good, sizeof(int) * (size_t)h->I},
-                                   {(void**)&h->d_wb, sizeof(int) * (size_t)h->I}});
-    if (st != LVI_OK) { lvi_pnp_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
+    return create_handle(device, out, lvi_pnp_destroy, [&](lvi_pnp* h) {
+        h->P = max_points; h->I = max_iters;
+        h->off_p2 = align256(sizeof(float) * 3 * (size_t)h->P);
+        h->off_sub = h->off_p2 + align256(sizeof(float) * 2 * (size_t)h->P);
+        h->off_log = h->off_sub + align256(sizeof(int) * MODEL_POINTS * (size_t)h->I);
+    }, [&](lvi_pnp* h) -> int32_t {
+        h->io.open(device, h->off_log + align256(sizeof(double) * ((size_t)h->P + 1)), align256(sizeof(lvi_pnp_info)) + align256((size_t)h->P), [&](auto& a) {
+            const size_t I = (size_t)h->I;
+            h->d_Rt = a.template alloc<double>(12 * I); h->d_has = a.template alloc<int>(I); h->d_good = a.template alloc<int>(I); h->d_wb = a.template alloc<int>(I);
+        });
+        return LVI_OK;
+    });
 }
 
 void lvi_pnp_destroy(lvi_pnp* h)
 {
     if (!h) return;
-    h->io.close({h->d_Rt, h->d_has, h->d_good, h->d_wb});
+    h->io.close();
     delete h;
 }
 

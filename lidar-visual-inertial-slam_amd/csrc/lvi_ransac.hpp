@@ -6,7 +6,7 @@
 //            or pow; then the 7-point callback's checkSubset and findFundamentalMat's stream.  No HIP in this part: tests
 //            compile it with a stand-alone main under the host sanitizers.
 //   device   the sequential walk of RANSACPointSetRegistrator::run over per-candidate inlier counts, and the status sweep
-//   Io       the stream and the buffer pairs of a handle (Bufs), the last call's sample stream (Trace), and the tail of a
+//   Io       the handle core (lvi_dev.hpp) and the buffer pairs of a handle (Bufs), the last call's sample stream (Trace), and the tail of a
 //            call: upload, launches, download, wait.  The batched RANSAC (lvi_fmatb) takes Bufs and one Trace
 //            per slot and has a tail of its own.
 //
@@ -124,8 +124,6 @@ static inline int fm_sample_stream(const float* xy, int n, bool ransac, int max_
 }  // namespace lvi_ransac
 
 #ifdef __HIPCC__
-#include <initializer_list>
-
 #include "lvi_dev.hpp"
 
 namespace lvi_ransac {
@@ -180,45 +178,21 @@ __device__ __forceinline__ int status_sweep(int n, unsigned char* status, Inlier
 }
 
 // ---------------------------------------------------------------------------------------------- the handle's plumbing
-struct DevBuf { void** p; size_t bytes; };
-
-// the stream and the buffer pairs; a batched handle (lvi_fmatb) lays one region per slot into each block
-struct Bufs {
-    int device = 0;
-    hipStream_t stream = nullptr;
+// the handle core and the buffer pairs; a batched handle (lvi_fmatb) lays one region per slot into each block
+struct Bufs : lvi::Handle {
     char* d_in = nullptr;                  // points | subsets | logtab, laid out by the owner
     char* h_in = nullptr;                  // pinned mirror of d_in
     char* d_out = nullptr;                 // info | status
     char* h_out = nullptr;
-    size_t in_bytes = 0, out_bytes = 0;
 
-    // the device checks, then the stream, the buffer pairs and the owner's per-hypothesis arrays
-    int32_t open(int dev, size_t in_b, size_t out_b, std::initializer_list<DevBuf> hyp)
+    // under the guard of create: the buffer pairs, then hyp(dev) carves the owner's per-hypothesis arrays
+    template <class Hyp> void open(int dev, size_t in_bytes, size_t out_bytes, Hyp&& hyp)
     {
-        if (const int32_t bad = lvi::check_device(dev)) return bad;
-        device = dev; in_bytes = in_b; out_bytes = out_b;
-        return lvi::guarded(device, [&]() -> int32_t {
-            LVI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            LVI_HIP(hipMalloc((void**)&d_in, in_bytes));
-            LVI_HIP(hipMalloc((void**)&d_out, out_bytes));
-            for (const DevBuf& b : hyp) LVI_HIP(hipMalloc(b.p, b.bytes));
-            LVI_HIP(hipHostMalloc((void**)&h_in, in_bytes, hipHostMallocDefault));
-            LVI_HIP(hipHostMalloc((void**)&h_out, out_bytes, hipHostMallocDefault));
-            return LVI_OK;
+        lvi::Handle::open(dev, [&](auto& a, auto& pin) {
+            lvi::alloc_pair(a, pin, d_in, h_in, in_bytes);
+            lvi::alloc_pair(a, pin, d_out, h_out, out_bytes);
+            hyp(a);
         });
-    }
-
-    void close(std::initializer_list<void*> hyp)
-    {
-        if (!stream) return;                                   // open failed before its first allocation
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(stream);
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-        for (void* p : hyp) if (p) (void)hipFree(p);
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        (void)hipStreamDestroy(stream);
     }
 };
 

@@ -432,12 +432,9 @@ struct HostPrior {
 
 }  // namespace
 
-struct lvi_win {
-    int device = 0;
+struct lvi_win : Handle {
     lvi_win_caps caps{};
     lvi_win_params P{};
-    hipStream_t stream = nullptr;
-    Arena arena;
     Dev d{};
     ProjDev* d_proj = nullptr; ImuDev* d_imu = nullptr; PriorBlk* d_pb = nullptr; BlkDev* d_blk = nullptr; int *d_fptr = nullptr, *d_ffac = nullptr;
     double *d_pJ = nullptr, *d_pr = nullptr, *d_px0 = nullptr;
@@ -459,15 +456,15 @@ int P1max(const lvi_win* h) { return h->caps.max_dim + 1; }
 int dense_rows_max(const lvi_win* h) { return IMU_ROWS * h->caps.max_imu + h->caps.max_prior_rows; }
 int max_chunks(const lvi_win* h) { return div_up(h->caps.max_projections, SHARE) + div_up(dense_rows_max(h), CH_ROWS) + 1; }
 
-template <class A> void carve(A& a, lvi_win* h)
+template <class A, class B> void carve(A& a, B& pin, lvi_win* h)
 {
     const lvi_win_caps& c = h->caps;
     const size_t Pm = (size_t)P1max(h), nb = (size_t)c.max_blocks, np = (size_t)c.max_projections, ne = std::max(1, c.max_eliminated), ni = std::max(1, c.max_imu),
                  n0 = std::max(1, c.max_prior_rows), R = std::max(1, dense_rows_max(h));
     Dev& d = h->d;
-    d.x = a.template alloc<double>(VAL * nb); d.xc = a.template alloc<double>(VAL * nb);
-    h->d_proj = a.template alloc<ProjDev>(np); h->d_imu = a.template alloc<ImuDev>(ni); h->d_pb = a.template alloc<PriorBlk>(n0); h->d_blk = a.template alloc<BlkDev>(nb);
-    h->d_fptr = a.template alloc<int>(ne + 1); h->d_ffac = a.template alloc<int>(np);
+    alloc_pair(a, pin, d.x, h->h_x, VAL * nb); d.xc = a.template alloc<double>(VAL * nb);
+    alloc_pair(a, pin, h->d_proj, h->h_proj, np); alloc_pair(a, pin, h->d_imu, h->h_imu, ni); alloc_pair(a, pin, h->d_pb, h->h_pb, n0);
+    alloc_pair(a, pin, h->d_blk, h->h_blk, nb); alloc_pair(a, pin, h->d_fptr, h->h_fptr, ne + 1); alloc_pair(a, pin, h->d_ffac, h->h_ffac, np);
     d.Jf = a.template alloc<double>(JF * np); d.E = a.template alloc<double>(R * Pm); d.fc = a.template alloc<double>(np + ni + n0);
     d.part = a.template alloc<double>((size_t)max_chunks(h) * Pm * Pm); d.A = a.template alloc<double>(Pm * Pm);
     d.W = a.template alloc<double>(ne * Pm); d.h = a.template alloc<double>(ne);
@@ -477,7 +474,7 @@ template <class A> void carve(A& a, lvi_win* h)
     d.uf = a.template alloc<double>(ne);
     d.S = a.template alloc<double>(Pm * Pm);
     h->d_pJ = a.template alloc<double>(n0 * n0); h->d_pr = a.template alloc<double>(n0); h->d_px0 = a.template alloc<double>(VAL * n0);
-    d.gi = a.template alloc<GradInfo>(1); d.si = a.template alloc<StepInfo>(1);
+    alloc_pair(a, pin, d.gi, h->h_gi, 1); alloc_pair(a, pin, d.si, h->h_si, 1);
 }
 
 bool params_ok(const lvi_win_params& p)
@@ -667,42 +664,15 @@ int32_t lvi_win_create(int32_t device, const lvi_win_caps* caps, lvi_win** out)
         c.max_eliminated < 0 || c.max_eliminated > LVI_WIN_MAX_ELIMINATED || c.max_imu < 0 || c.max_imu > LVI_WIN_MAX_IMU ||
         c.max_prior_rows < 0 || c.max_prior_rows > LVI_WIN_MAX_PRIOR_ROWS || c.max_dim < 1 || c.max_dim > LVI_WIN_MAX_DIM)
         return fail(LVI_ERR_INVALID_ARG, "a capacity is outside its range 0 or 1..LVI_WIN_MAX_*");
-    if (const int32_t bad = check_device(device)) return bad;
-    lvi_win* h = new lvi_win();
-    h->device = device; h->caps = c;
-    lvi_win_params_default(&h->P);
-    const int32_t st = guarded(h->device, [&]() -> int32_t {
-        LVI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        ArenaSizer sz;
-        carve(sz, h);
-        h->arena.init(sz.used);
-        carve(h->arena, h);
-        const size_t nb = (size_t)c.max_blocks, np = (size_t)c.max_projections;
-        LVI_HIP(hipHostMalloc((void**)&h->h_x, sizeof(double) * VAL * nb, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_proj, sizeof(ProjDev) * np, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_imu, sizeof(ImuDev) * std::max(1, c.max_imu), hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_pb, sizeof(PriorBlk) * std::max(1, c.max_prior_rows), hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_blk, sizeof(BlkDev) * nb, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_fptr, sizeof(int) * (c.max_eliminated + 1), hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_ffac, sizeof(int) * np, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_gi, 256, hipHostMallocDefault));
-        LVI_HIP(hipHostMalloc((void**)&h->h_si, 256, hipHostMallocDefault));
-        return LVI_OK;
-    });
-    if (st != LVI_OK) { lvi_win_destroy(h); return st; }
-    *out = h;
-    return LVI_OK;
+    return create_handle(device, out, lvi_win_destroy,
+        [&](lvi_win* h) { h->caps = c; lvi_win_params_default(&h->P); },
+        [&](lvi_win* h) -> int32_t { h->open(device, [&](auto& dev, auto& pin) { carve(dev, pin, h); }); return LVI_OK; });
 }
 
 void lvi_win_destroy(lvi_win* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->arena.release();
-    for (void* p : {(void*)h->h_x, (void*)h->h_proj, (void*)h->h_imu, (void*)h->h_pb, (void*)h->h_blk, (void*)h->h_fptr, (void*)h->h_ffac, (void*)h->h_gi, (void*)h->h_si})
-        if (p) (void)hipHostFree(p);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->close();
     delete h;
 }
 
