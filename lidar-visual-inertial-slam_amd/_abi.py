@@ -216,6 +216,32 @@ class Library:
         return code
 
 
+class Owned:
+    """The one lifetime of a wrapper that owns a C or C++ object.  A subclass says where its library lives (`_lib`: "lib"
+    for a Library, "hl" for a HostLibrary), which attribute holds the pointer (`_ptr`), which function frees it
+    (`_destroy`) and, over the host library, which lvh_X_last_error `_check` reads (`_last_error`).  An instance with
+    `_own = False`, or with a `close` of its own, is a view of an object the C++ side owns and never destroys it."""
+    _lib, _ptr, _destroy, _last_error, _own = "lib", "_h", None, None, True
+
+    def close(self):
+        p = getattr(self, self._ptr, None)
+        if p:
+            if self._own:
+                getattr(getattr(self, self._lib).dll, self._destroy)(p)
+            setattr(self, self._ptr, C.c_void_p() if isinstance(p, C.c_void_p) else None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, code, where):
+        if code < 0:
+            raise LviError(code, where, getattr(getattr(self, self._lib).dll, self._last_error)().decode(errors="replace"))
+        return code
+
+
 def as_pts(a):
     """any (n,4) float array or PT_DTYPE array -> contiguous PT_DTYPE array"""
     a = np.asarray(a)

@@ -69,9 +69,10 @@ def read_vocab(src):
     return {n: int(head[n]) for n in HEADER_DTYPE.names}, nodes, words
 
 
-class BowDatabase:
+class BowDatabase(A.Owned):
     """BriefDatabase of the reference's LoopDetector on the GPU of `store` (a kf.KeyframeDescriber, which must outlive it).
     vocab = the file's bytes or its path."""
+    _destroy = "lvi_bow_destroy"
 
     def __init__(self, lib, store, vocab, max_entries=4096):
         self.lib = bind(lib)
@@ -84,17 +85,6 @@ class BowDatabase:
         lib.check(lib.dll.lvi_bow_create(store._h, C.c_void_p(buf.ctypes.data) if buf.size else None, buf.size, int(max_entries), C.byref(self._h)),
                   "lvi_bow_create")
         self.max_entries = int(max_entries)
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_bow_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return int(self.lib.dll.lvi_bow_size(self._h))

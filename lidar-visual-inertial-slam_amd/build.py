@@ -11,13 +11,15 @@ SOURCES = ["lvi_sort.hip", "lvi_voxel.hip", "lvi_scan.hip", "lvi_icp.hip", "lvi_
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
 
+def hip_dependencies():
+    """what liblvi_hip.so is rebuilt for: every csrc/*.hip and *.hpp and every include/*.h"""
+    inc = os.path.normpath(os.path.join(CSRC, "..", "..", "include"))
+    return (sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp")))
+            + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")))
+
+
 def _stale():
-    if not os.path.exists(OUT):
-        return True
-    t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    deps += [os.path.join(CSRC, "..", "..", "include", h) for h in ("lvi_hotpath.h", "lvi_depth.h", "lvi_fmat.h", "lvi_fmatb.h", "lvi_gmap.h", "lvi_loop.h", "lvi_kf.h", "lvi_bow.h", "lvi_pnp.h", "lvi_tbatch.h", "lvi_pgo.h", "lvi_pgo_gps.h", "lvi_marg.h", "lvi_win.h", "lvi_fman.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in hip_dependencies())
 
 
 def build_hip(force=False, verbose=False):
@@ -53,8 +55,8 @@ def build_hip(force=False, verbose=False):
 
 def build_host(verbose=False):
     """host/liblvi_host_hip.so: the C++ host mirror (host/lvi_host.hpp) flattened to C, linked against liblvi_hip.so"""
-    from .host_api import BOW_SOURCES, DEPTH_SOURCES, FMAT_SOURCES, GMAP_SOURCES, HOST_HIP_LIB, KF_SOURCES, LOOP_SOURCES, MARG_SOURCES, PGO_SOURCES, PNP_SOURCES, TBATCH_SOURCES, WIN_SOURCES, FMAN_SOURCES, build_host_library
-    sources = DEPTH_SOURCES + FMAT_SOURCES + GMAP_SOURCES + LOOP_SOURCES + KF_SOURCES + BOW_SOURCES + PNP_SOURCES + PGO_SOURCES + TBATCH_SOURCES + MARG_SOURCES + WIN_SOURCES + FMAN_SOURCES
+    from .host_api import HOST_HIP_LIB, build_host_library, component_sources
+    sources = component_sources()
     if verbose:
         print("g++ -shared host/lvi_seq_capi.cpp", *("host/" + f for f in sources), "-llvi_hip ->", HOST_HIP_LIB, flush=True)
     return build_host_library(HOST_HIP_LIB, CSRC, "lvi_hip", sources=sources)

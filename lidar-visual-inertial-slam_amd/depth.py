@@ -44,9 +44,10 @@ def _pose(pose6):
     return (C.c_float * 6)(*[float(v) for v in np.asarray(pose6, np.float32).reshape(6)])
 
 
-class DepthRegister:
+class DepthRegister(A.Owned):
     """DepthRegister + the node's lidar window.  pose6 = (x, y, z, roll, pitch, yaw) of the body in the world frame, or
     None when no transform is available."""
+    _destroy = "lvi_depth_destroy"
 
     def __init__(self, lib, device=0, max_clouds=64, max_cloud_points=131072, max_features=150, lidar_skip=3, window_s=5.0):
         self.lib = bind(lib)
@@ -56,17 +57,6 @@ class DepthRegister:
         self._h = C.c_void_p()
         lib.check(lib.dll.lvi_depth_create(int(device), int(max_clouds), int(max_cloud_points), int(max_features), int(lidar_skip),
                                            float(window_s), C.byref(self._h)), "lvi_depth_create")
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_depth_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def lidar_callback(self, cloud, pose6, stamp):
         """one incoming cloud (sensor frame); returns True when it entered the window"""

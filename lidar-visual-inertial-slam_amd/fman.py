@@ -8,6 +8,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _abi as A
 from .marg import PROJECTION_DTYPE
 
 _P = C.POINTER
@@ -89,8 +90,9 @@ def _arr(a, shape):
     return a
 
 
-class FeatureTable:
+class FeatureTable(A.Owned):
     """f_manager: the feature list of one estimator, resident on the device in the reference's list order"""
+    _destroy = "lvi_fman_destroy"
     feature_dtype = FEATURE_DTYPE
     record_dtype = PROJECTION_DTYPE
 
@@ -105,17 +107,6 @@ class FeatureTable:
         lib.dll.lvi_fman_params_default(C.byref(self.params))
         if params:
             self.set_params(**params)
-
-    def close(self):
-        if self._h and self._own:
-            self.lib.dll.lvi_fman_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _call(self, name, *args):
         return self.lib.check(getattr(self.lib.dll, name)(self._h, *args), name)

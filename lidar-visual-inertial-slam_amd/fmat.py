@@ -43,9 +43,10 @@ def _info_dict(info):
                 F=np.array(info.F[:], np.float64).reshape(3, 3), stream_us=info.stream_us)
 
 
-class FundamentalRansac:
+class FundamentalRansac(A.Owned):
     """cv::findFundamentalMat(pts1, pts2, FM_RANSAC, threshold, confidence, max_iters, mask) on the GPU.  One handle
     serves calls of up to max_points correspondences."""
+    _destroy = "lvi_fmat_destroy"
 
     def __init__(self, lib, device=0, max_points=2048, max_iters=1000):
         self.lib = bind(lib)
@@ -53,17 +54,6 @@ class FundamentalRansac:
         self.max_iters = int(max_iters)
         self._h = C.c_void_p()
         lib.check(lib.dll.lvi_fmat_create(int(device), self.max_points, self.max_iters, C.byref(self._h)), "lvi_fmat_create")
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_fmat_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_check_subset(self, mode):
         """1 (default): getSubset rejects subsets with collinear points in either set; 0: it does not"""

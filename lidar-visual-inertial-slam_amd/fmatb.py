@@ -32,9 +32,10 @@ def bind(lib):
     return lib.bind(FMATB_SIGNATURES)
 
 
-class FundamentalRansacBatch:
+class FundamentalRansacBatch(A.Owned):
     """`slots` FundamentalRansac handles behind one call: the sample stream of slot s + 1 is drawn on the host while the
     device scores slot s, then one launch walks all slots and one wait ends the call."""
+    _destroy = "lvi_fmatb_destroy"
 
     def __init__(self, lib, slots, max_points=2048, max_iters=1000, device=0):
         self.lib = bind(lib)
@@ -43,17 +44,6 @@ class FundamentalRansacBatch:
         self.max_iters = int(max_iters)
         self._h = C.c_void_p()
         lib.check(lib.dll.lvi_fmatb_create(int(device), self.slots, self.max_points, self.max_iters, C.byref(self._h)), "lvi_fmatb_create")
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_fmatb_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_check_subset(self, mode):
         """FundamentalRansac.set_check_subset for all slots"""

@@ -1,24 +1,11 @@
 // C entry points over the loop detector of the host mirror (lvi_bow_host.hpp): LoopDetector::loadVocabulary and
 // addKeyFrame, for replay harnesses that are not C++.  include/lvi_bow.h is exported by liblvi_hip.so only, so this file
 // is linked into host/liblvi_host_hip.so alone (build.py), never into a host library built against the CPU oracle.
-#include <string>
-
 #include "lvi_bow_capi_detail.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
 using lvi_host_capi::Detector;
-
-namespace {
-thread_local std::string g_err;
-
-template <class F>
-int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 extern "C" {
 
@@ -39,7 +26,7 @@ lvi_bow* lvh_bow_db_handle(void* d) { return d ? static_cast<Detector*>(d)->ld.d
 
 int32_t lvh_bow_load_vocabulary(void* d, const char* path)
 {
-    if (!d || !path) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!d || !path) return fail("null argument");
     return guarded([&]() -> int32_t { static_cast<Detector*>(d)->ld.loadVocabulary(path); return LVI_OK; });
 }
 
@@ -51,10 +38,8 @@ int32_t lvh_bow_add_keyframe(void* d, int32_t slot, int32_t index, int32_t flag_
                              const float* point_2d_norm, const double* point_id, int32_t n_kp, const float* keypoints, const float* keypoints_norm,
                              int32_t* out, lvi_bow_result* ret)
 {
-    if (!d || n < 0 || n_kp < 0 || (n > 0 && (!point_3d || !point_2d_uv || !point_2d_norm || !point_id)) || (n_kp > 0 && (!keypoints || !keypoints_norm))) {
-        g_err = "bad arguments";
-        return LVI_ERR_INVALID_ARG;
-    }
+    if (!d || n < 0 || n_kp < 0 || (n > 0 && (!point_3d || !point_2d_uv || !point_2d_norm || !point_id)) || (n_kp > 0 && (!keypoints || !keypoints_norm)))
+        return fail("bad arguments");
     return guarded([&]() -> int32_t {
         Detector* D = static_cast<Detector*>(d);
         KeyFrame kf;
@@ -81,7 +66,7 @@ int32_t lvh_bow_add_keyframe(void* d, int32_t slot, int32_t index, int32_t flag_
 // the compacted vectors of the last hit's findConnectionFront: cur, old [n][2], id [n] (any may be NULL); returns n
 int32_t lvh_bow_connection(void* d, float* cur, float* old_xy, double* id)
 {
-    if (!d) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!d) return fail("null argument");
     const Connection& c = static_cast<Detector*>(d)->last.connection;
     const size_t n = c.matched_2d_cur.size();
     if (cur) for (size_t i = 0; i < n; i++) { cur[2 * i] = c.matched_2d_cur[i].x; cur[2 * i + 1] = c.matched_2d_cur[i].y; }

@@ -3,23 +3,13 @@
 // liblvi_hip.so only, so this file is linked into host/liblvi_host_hip.so alone (build.py), never into a host library
 // built against the CPU oracle; lvi_seq_capi.cpp stays free of it.
 #include <memory>
-#include <string>
 
 #include "lvi_depth_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
 
 extern "C" void* lvh_trk_node(struct lvh_trk* t);     // lvi_seq_capi.cpp
-
-namespace {
-thread_local std::string g_err;
-template <class F> int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 struct lvh_depth {
     std::unique_ptr<DepthRegister> reg;
@@ -45,7 +35,7 @@ lvi_depth* lvh_depth_handle(lvh_depth* d) { return d ? d->reg->get() : nullptr; 
 // FeatureTrackerNode::get_depth := the register (channel 5 of every message lvh_trk_image assembles from now on)
 int32_t lvh_depth_install(lvh_depth* d, struct lvh_trk* t)
 {
-    if (!d || !t) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!d || !t) return fail("null argument");
     d->reg->install(*static_cast<FeatureTrackerNode*>(lvh_trk_node(t)));
     return LVI_OK;
 }
@@ -53,7 +43,7 @@ int32_t lvh_depth_install(lvh_depth* d, struct lvh_trk* t)
 // lidar_callback: pose6 = (x, y, z, roll, pitch, yaw) or NULL (no TF)
 int32_t lvh_depth_lidar(lvh_depth* d, const lvi_pt* pts, int32_t n, const float* pose6, double stamp, int32_t* used)
 {
-    if (!d || n < 0 || (n > 0 && !pts)) { g_err = "bad arguments"; return LVI_ERR_INVALID_ARG; }
+    if (!d || n < 0 || (n > 0 && !pts)) return fail("bad arguments");
     return guarded([&]() -> int32_t {
         BodyPose p{};
         if (pose6) for (int k = 0; k < 6; k++) p.v[k] = pose6[k];
@@ -66,7 +56,7 @@ int32_t lvh_depth_lidar(lvh_depth* d, const lvi_pt* pts, int32_t n, const float*
 // the pose get_depth's TF lookup returns for the next image (NULL: the lookup fails)
 int32_t lvh_depth_set_image_pose(lvh_depth* d, const float* pose6)
 {
-    if (!d) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!d) return fail("null argument");
     BodyPose p{};
     if (pose6) for (int k = 0; k < 6; k++) p.v[k] = pose6[k];
     d->reg->set_image_pose(pose6 ? &p : nullptr);

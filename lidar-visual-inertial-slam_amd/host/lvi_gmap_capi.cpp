@@ -3,24 +3,14 @@
 // liblvi_hip.so only, so this file is linked into host/liblvi_host_hip.so alone (build.py).
 #include <cstring>
 #include <memory>
-#include <string>
 
 #include "lvi_gmap_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
 
 extern "C" void* lvh_seq_node(struct lvh_seq* s);     // lvi_seq_capi.cpp
 extern "C" lvi_lidar* lvh_seq_handle(struct lvh_seq* s);
-
-namespace {
-thread_local std::string g_err;
-template <class F> int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 struct lvh_gmap {
     std::unique_ptr<GlobalMapper> m;
@@ -45,18 +35,18 @@ void lvh_gmap_destroy(lvh_gmap* g) { delete g; }
 
 int32_t lvh_gmap_reserve(lvh_gmap* g, int32_t max_points)
 {
-    if (!g) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g) return fail("null argument");
     return guarded([&]() -> int32_t { g->m->reserve(max_points); return LVI_OK; });
 }
 
 // steps 2-6: the fuse order of the key clouds; *n = its length whatever capacity is
 int32_t lvh_gmap_keys(lvh_gmap* g, int32_t* keys, int32_t capacity, int32_t* n)
 {
-    if (!g || !n) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || !n) return fail("null argument");
     return guarded([&]() -> int32_t {
         const std::vector<int32_t> k = g->m->globalMapKeys();
         *n = (int32_t)k.size();
-        if (keys) { if (capacity < *n) { g_err = "capacity too small"; return LVI_ERR_CAPACITY; } std::memcpy(keys, k.data(), sizeof(int32_t) * k.size()); }
+        if (keys) { if (capacity < *n) return fail("capacity too small", LVI_ERR_CAPACITY); std::memcpy(keys, k.data(), sizeof(int32_t) * k.size()); }
         return LVI_OK;
     });
 }
@@ -64,7 +54,7 @@ int32_t lvh_gmap_keys(lvh_gmap* g, int32_t* keys, int32_t capacity, int32_t* n)
 // publishGlobalMap: 1 = published (info = n_fused, n_out, overflow, filtered), 0 = no key poses
 int32_t lvh_gmap_publish(lvh_gmap* g, int32_t info[4])
 {
-    if (!g || !info) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || !info) return fail("null argument");
     return guarded([&]() -> int32_t {
         lvi_gmap_info r{};
         if (!g->m->publishGlobalMap(g->last, &r)) { g->last.clear(); return 0; }
@@ -76,16 +66,16 @@ int32_t lvh_gmap_publish(lvh_gmap* g, int32_t info[4])
 // the last published cloud; *n = its size whatever capacity is
 int32_t lvh_gmap_cloud(lvh_gmap* g, lvi_pt* out, int32_t capacity, int32_t* n)
 {
-    if (!g || !n) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || !n) return fail("null argument");
     *n = (int32_t)g->last.size();
-    if (out) { if (capacity < *n) { g_err = "capacity too small"; return LVI_ERR_CAPACITY; } std::memcpy(out, g->last.data(), sizeof(lvi_pt) * g->last.size()); }
+    if (out) { if (capacity < *n) return fail("capacity too small", LVI_ERR_CAPACITY); std::memcpy(out, g->last.data(), sizeof(lvi_pt) * g->last.size()); }
     return LVI_OK;
 }
 
 // the save_map service: 1 = success (the GlobalMap write), 0 = failure
 int32_t lvh_gmap_save(lvh_gmap* g, const char* dir, float resolution)
 {
-    if (!g || !dir) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || !dir) return fail("null argument");
     return guarded([&]() -> int32_t { return g->m->saveMap(dir, resolution) ? 1 : 0; });
 }
 

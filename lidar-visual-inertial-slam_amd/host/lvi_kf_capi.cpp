@@ -2,29 +2,19 @@
 // half of findConnection, for replay harnesses that are not C++.  include/lvi_kf.h is exported by liblvi_hip.so only, so
 // this file is linked into host/liblvi_host_hip.so alone (build.py), never into a host library built against the CPU oracle.
 #include <map>
-#include <string>
 
 #include "lvi_kf_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
 
 namespace {
-thread_local std::string g_err;
-
 struct Matcher {
     KeyFrameDescriber kd;
     std::map<int, KeyFrame> frames;          // by slot
     Connection last;
     template <class... A> explicit Matcher(A... a) : kd(a...) {}
 };
-
-template <class F>
-int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
 }  // namespace
 
 extern "C" {
@@ -47,7 +37,7 @@ lvi_kf* lvh_kf_handle(void* m) { return m ? static_cast<Matcher*>(m)->kd.get() :
 int32_t lvh_kf_add(void* m, int32_t slot, const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t n, const float* point_3d,
                    const float* point_2d_uv, const float* point_2d_norm, const double* point_id, const lvi_mei_params* cam, int32_t* info)
 {
-    if (!m || n < 0 || (n > 0 && (!point_3d || !point_2d_uv || !point_2d_norm || !point_id))) { g_err = "bad arguments"; return LVI_ERR_INVALID_ARG; }
+    if (!m || n < 0 || (n > 0 && (!point_3d || !point_2d_uv || !point_2d_norm || !point_id))) return fail("bad arguments");
     return guarded([&]() -> int32_t {
         Matcher* M = static_cast<Matcher*>(m);
         std::vector<Point3f> p3(n);
@@ -68,11 +58,11 @@ int32_t lvh_kf_add(void* m, int32_t slot, const uint8_t* img, int32_t w, int32_t
 
 int32_t lvh_kf_remove(void* m, int32_t slot)
 {
-    if (!m) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!m) return fail("null argument");
     return guarded([&]() -> int32_t {
         Matcher* M = static_cast<Matcher*>(m);
         auto it = M->frames.find(slot);
-        if (it == M->frames.end()) { g_err = "no keyframe in this slot"; return LVI_ERR_INVALID_ARG; }
+        if (it == M->frames.end()) return fail("no keyframe in this slot");
         M->kd.release(it->second);
         M->frames.erase(it);
         return LVI_OK;
@@ -83,11 +73,11 @@ int32_t lvh_kf_remove(void* m, int32_t slot)
 // length of the compacted vectors, kept for lvh_kf_connection
 int32_t lvh_kf_connect(void* m, int32_t cur_slot, int32_t old_slot, int32_t* n_out)
 {
-    if (!m) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!m) return fail("null argument");
     return guarded([&]() -> int32_t {
         Matcher* M = static_cast<Matcher*>(m);
         auto c = M->frames.find(cur_slot), o = M->frames.find(old_slot);
-        if (c == M->frames.end() || o == M->frames.end()) { g_err = "no keyframe in this slot"; return LVI_ERR_INVALID_ARG; }
+        if (c == M->frames.end() || o == M->frames.end()) return fail("no keyframe in this slot");
         const bool pass = M->kd.findConnectionFront(c->second, o->second, M->last);
         if (n_out) *n_out = (int32_t)M->last.matched_2d_cur.size();
         return pass ? 1 : 0;
@@ -98,7 +88,7 @@ int32_t lvh_kf_connect(void* m, int32_t cur_slot, int32_t old_slot, int32_t* n_o
 // = searchByBRIEFDes's (one per window point of cur).  Any pointer may be NULL.
 int32_t lvh_kf_connection(void* m, float* cur, float* old_xy, float* cur_norm, float* old_norm, float* p3, double* id, uint8_t* status, int32_t cap_status)
 {
-    if (!m) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!m) return fail("null argument");
     const Connection& c = static_cast<Matcher*>(m)->last;
     const size_t n = c.matched_2d_cur.size();
     auto copy2 = [n](float* dst, const std::vector<Point2f>& v) { if (dst) for (size_t i = 0; i < n; i++) { dst[2 * i] = v[i].x; dst[2 * i + 1] = v[i].y; } };

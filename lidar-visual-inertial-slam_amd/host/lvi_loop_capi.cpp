@@ -3,24 +3,14 @@
 // liblvi_hip.so only, so this file is linked into host/liblvi_host_hip.so alone (build.py).
 #include <cstring>
 #include <memory>
-#include <string>
 
 #include "lvi_loop_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
 
 extern "C" void* lvh_seq_node(struct lvh_seq* s);     // lvi_seq_capi.cpp
 extern "C" lvi_lidar* lvh_seq_handle(struct lvh_seq* s);
-
-namespace {
-thread_local std::string g_err;
-template <class F> int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 struct lvh_loop {
     std::unique_ptr<LoopCloser> m;
@@ -47,21 +37,21 @@ void lvh_loop_destroy(lvh_loop* g) { delete g; }
 
 int32_t lvh_loop_reserve(lvh_loop* g, int32_t max_source_points, int32_t max_target_points)
 {
-    if (!g) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g) return fail("null argument");
     return guarded([&]() -> int32_t { g->m->reserve(max_source_points, max_target_points); return LVI_OK; });
 }
 
 // loopInfoHandler: a message of n doubles
 int32_t lvh_loop_info_msg(lvh_loop* g, const double* data, int32_t n)
 {
-    if (!g || (n > 0 && !data)) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || (n > 0 && !data)) return fail("null argument");
     return guarded([&]() -> int32_t { g->m->loopInfoHandler(data, (size_t)n); return (int32_t)g->m->loopInfoVec.size(); });
 }
 
 // which: 0 = detectLoopClosureDistance, 1 = detectLoopClosureExternal, on fresh pose copies.  1 = found (keys[0] = cur, keys[1] = pre)
 int32_t lvh_loop_detect(lvh_loop* g, int32_t which, double time_laser_info_cur, int32_t keys[2])
 {
-    if (!g || !keys) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || !keys) return fail("null argument");
     return guarded([&]() -> int32_t {
         g->m->copyKeyPoses();
         if (g->m->copy_cloudKeyPoses3D.empty()) return 0;
@@ -75,12 +65,12 @@ int32_t lvh_loop_detect(lvh_loop* g, int32_t which, double time_laser_info_cur, 
 // startLoop / finishLoop: 1 = a job was enqueued / a constraint was pushed
 int32_t lvh_loop_start(lvh_loop* g, double time_laser_info_cur)
 {
-    if (!g) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g) return fail("null argument");
     return guarded([&]() -> int32_t { return g->m->startLoop(time_laser_info_cur) ? 1 : 0; });
 }
 int32_t lvh_loop_finish(lvh_loop* g, lvi_loop_info* info)
 {
-    if (!g) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g) return fail("null argument");
     return guarded([&]() -> int32_t {
         const bool ok = g->m->finishLoop();
         if (info) *info = g->m->lastInfo;
@@ -92,7 +82,7 @@ int32_t lvh_loop_finish(lvh_loop* g, lvi_loop_info* info)
 int32_t lvh_loop_queue_size(lvh_loop* g) { return g ? (int32_t)g->m->loopQueue.size() : 0; }
 int32_t lvh_loop_pop(lvh_loop* g, int32_t keys[2], double between[16], float* noise)
 {
-    if (!g || !keys || !between || !noise) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || !keys || !between || !noise) return fail("null argument");
     if (g->m->loopQueue.empty()) return 0;
     const LoopConstraint c = g->m->loopQueue.front();
     g->m->loopQueue.pop_front();
@@ -104,10 +94,10 @@ int32_t lvh_loop_pop(lvh_loop* g, int32_t keys[2], double between[16], float* no
 // loopIndexContainer as (cur, pre) pairs; *n = its size whatever capacity (in pairs) is
 int32_t lvh_loop_closed(lvh_loop* g, int32_t* pairs, int32_t capacity, int32_t* n)
 {
-    if (!g || !n) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || !n) return fail("null argument");
     *n = (int32_t)g->m->loopIndexContainer.size();
     if (pairs) {
-        if (capacity < *n) { g_err = "capacity too small"; return LVI_ERR_CAPACITY; }
+        if (capacity < *n) return fail("capacity too small", LVI_ERR_CAPACITY);
         int i = 0;
         for (const auto& kv : g->m->loopIndexContainer) { pairs[2 * i] = kv.first; pairs[2 * i + 1] = kv.second; i++; }
     }
@@ -117,11 +107,11 @@ int32_t lvh_loop_closed(lvh_loop* g, int32_t* pairs, int32_t capacity, int32_t* 
 // the publishers' clouds of the last finished job (LVI_LOOP_TARGET = pubHistoryKeyFrames, LVI_LOOP_ALIGNED = pubIcpKeyFrames)
 int32_t lvh_loop_cloud(lvh_loop* g, int32_t what, lvi_pt* out, int32_t capacity, int32_t* n)
 {
-    if (!g || !n) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!g || !n) return fail("null argument");
     return guarded([&]() -> int32_t {
         *n = what == LVI_LOOP_TARGET ? g->m->lastInfo.n_target : g->m->lastInfo.n_source;
         if (out) {
-            if (capacity < *n) { g_err = "capacity too small"; return LVI_ERR_CAPACITY; }
+            if (capacity < *n) return fail("capacity too small", LVI_ERR_CAPACITY);
             std::vector<lvi_pt> pts;
             g->m->fetch(what, pts);
             std::memcpy(out, pts.data(), sizeof(lvi_pt) * pts.size());

@@ -2,21 +2,11 @@
 // that are not C++.  include/lvi_marg.h is exported by liblvi_hip.so only, so this file is linked into
 // host/liblvi_host_hip.so alone (build.py), never into a host library built against the CPU oracle.
 #include <cstring>
-#include <string>
 
 #include "lvi_marg_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
-
-namespace {
-thread_local std::string g_err;
-template <class F> int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 extern "C" {
 
@@ -36,7 +26,7 @@ lvi_marg* lvh_marg_handle(void* p) { return p ? static_cast<VinsMarginalizer*>(p
 // vector2double: para_Pose [11][7], para_SpeedBias [11][9], para_Ex_Pose [7], para_Td
 int32_t lvh_marg_set_window(void* p, const double* pose, const double* speed_bias, const double* ex_pose, double td)
 {
-    if (!p || !pose || !speed_bias || !ex_pose) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p || !pose || !speed_bias || !ex_pose) return fail("null argument");
     VinsMarginalizer* v = static_cast<VinsMarginalizer*>(p);
     std::memcpy(v->paraPose, pose, sizeof(v->paraPose));
     std::memcpy(v->paraSpeedBias, speed_bias, sizeof(v->paraSpeedBias));
@@ -49,7 +39,7 @@ int32_t lvh_marg_set_window(void* p, const double* pose, const double* speed_bia
 // observations in turn, 7 doubles each (point [3], velocity [2], cur_td, uv.y)
 int32_t lvh_marg_set_features(void* p, int32_t count, const int32_t* start_frame, const int32_t* n_obs, const double* inv_dep, const double* obs)
 {
-    if (!p || (count > 0 && (!start_frame || !n_obs || !inv_dep || !obs)) || count < 0) { g_err = "bad argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p || (count > 0 && (!start_frame || !n_obs || !inv_dep || !obs)) || count < 0) return fail("bad argument");
     VinsMarginalizer* v = static_cast<VinsMarginalizer*>(p);
     v->features.clear();
     size_t at = 0;
@@ -72,7 +62,7 @@ int32_t lvh_marg_set_features(void* p, int32_t count, const int32_t* start_frame
 // NULL: no factor
 int32_t lvh_marg_set_imu(void* p, double sum_dt, const double* residual, const double* jacobians)
 {
-    if (!p || (residual && !jacobians)) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p || (residual && !jacobians)) return fail("null argument");
     VinsMarginalizer* v = static_cast<VinsMarginalizer*>(p);
     v->hasImu = residual != nullptr; v->imuSumDt = sum_dt;
     if (residual) { std::memcpy(v->imuResidual, residual, sizeof(v->imuResidual)); std::memcpy(v->imuJacobians, jacobians, sizeof(v->imuJacobians)); }
@@ -83,7 +73,7 @@ int32_t lvh_marg_set_imu(void* p, double sum_dt, const double* residual, const d
 // result is the prior.  Returns its status (LVI_OK or soft) or an error.
 int32_t lvh_marg_run(void* p, int32_t flag, int32_t* ran, lvi_marg_info* info)
 {
-    if (!p || (flag != 0 && flag != 1)) { g_err = "bad argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p || (flag != 0 && flag != 1)) return fail("bad argument");
     VinsMarginalizer* v = static_cast<VinsMarginalizer*>(p);
     return guarded([&]() -> int32_t {
         const bool r = v->run(flag == 0 ? VinsMarginalizer::MARGIN_OLD : VinsMarginalizer::MARGIN_SECOND_NEW);

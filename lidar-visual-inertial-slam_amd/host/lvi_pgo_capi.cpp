@@ -2,23 +2,13 @@
 // usePoseGraph hook, for replay harnesses that are not C++.  include/lvi_pgo.h is exported by liblvi_hip.so only, so this
 // file is linked into host/liblvi_host_hip.so alone (build.py), never into a host library built against the CPU oracle.
 #include <cstring>
-#include <string>
 
 #include "lvi_pgo_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
 
 extern "C" void* lvh_seq_node(struct lvh_seq* s);     // lvi_seq_capi.cpp
-
-namespace {
-thread_local std::string g_err;
-template <class F> int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 extern "C" {
 
@@ -43,7 +33,7 @@ lvi_pgo* lvh_pgo_handle(void* p) { return p ? static_cast<PoseGraphBackend*>(p)-
 // MapOptimizationNode::usePoseGraph on the node of lvh_seq_create; pg = NULL removes the hook.  The back end must outlive its use.
 int32_t lvh_seq_use_pose_graph(lvh_seq* s, void* pg)
 {
-    if (!s) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!s) return fail("null argument");
     return guarded([&]() -> int32_t {
         static_cast<MapOptimizationNode*>(lvh_seq_node(s))->usePoseGraph(static_cast<PoseGraphBackend*>(pg));
         return LVI_OK;
@@ -53,7 +43,7 @@ int32_t lvh_seq_use_pose_graph(lvh_seq* s, void* pg)
 // one entry of loopIndexQueue / loopPoseQueue / loopNoiseQueue (what lvh_loop_pop hands out); returns the queue's length
 int32_t lvh_pgo_push_loop(void* p, int32_t key_cur, int32_t key_pre, const double between[16], float noise)
 {
-    if (!p || !between) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p || !between) return fail("null argument");
     PoseGraphBackend* b = static_cast<PoseGraphBackend*>(p);
     LoopConstraint c;
     c.keyCur = key_cur; c.keyPre = key_pre; c.noise = noise;
@@ -66,7 +56,7 @@ int32_t lvh_pgo_push_loop(void* p, int32_t key_cur, int32_t key_pre, const doubl
 // addOdomFactor's poseTo) may be NULL
 int32_t lvh_pgo_last(void* p, lvi_pgo_info* info, float pose_to[6], int32_t counters[4])
 {
-    if (!p) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p) return fail("null argument");
     const PoseGraphBackend* b = static_cast<PoseGraphBackend*>(p);
     if (info) *info = b->lastInfo;
     if (pose_to) std::memcpy(pose_to, b->lastPoseTo, sizeof(b->lastPoseTo));
@@ -77,7 +67,7 @@ int32_t lvh_pgo_last(void* p, lvi_pgo_info* info, float pose_to[6], int32_t coun
 // MapOptimizationNode::useGps with the settings of utility.h:178-183
 int32_t lvh_seq_use_gps(lvh_seq* s, int32_t use_gps_elevation, float gps_cov_threshold, float pose_cov_threshold)
 {
-    if (!s) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!s) return fail("null argument");
     return guarded([&]() -> int32_t {
         GpsSettings g;
         g.useGpsElevation = use_gps_elevation != 0; g.gpsCovThreshold = gps_cov_threshold; g.poseCovThreshold = pose_cov_threshold;
@@ -89,7 +79,7 @@ int32_t lvh_seq_use_gps(lvh_seq* s, int32_t use_gps_elevation, float gps_cov_thr
 // gpsHandler (:334-337): the stamp, pose.pose.position and pose.covariance[0], [7], [14] of one message; returns the queue's length
 int32_t lvh_seq_gps_push(lvh_seq* s, double stamp, const double xyz[3], const double cov_xyz[3])
 {
-    if (!s || !xyz || !cov_xyz) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!s || !xyz || !cov_xyz) return fail("null argument");
     MapOptimizationNode* n = static_cast<MapOptimizationNode*>(lvh_seq_node(s));
     n->gpsHandler(stamp, xyz, cov_xyz);
     return (int32_t)n->gpsGate.gpsQueue.size();
@@ -98,7 +88,7 @@ int32_t lvh_seq_gps_push(lvh_seq* s, double stamp, const double xyz[3], const do
 // poseCovariance (:1591; row-major 6x6, may be NULL) and counters [3]: GPS factors added, messages still queued, GPS in use
 int32_t lvh_seq_gps_last(lvh_seq* s, double cov[36], int32_t counters[3])
 {
-    if (!s) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!s) return fail("null argument");
     const MapOptimizationNode* n = static_cast<MapOptimizationNode*>(lvh_seq_node(s));
     if (cov) std::memcpy(cov, n->poseCovariance, sizeof(n->poseCovariance));
     if (counters) { counters[0] = n->gpsFactorsAdded; counters[1] = (int32_t)n->gpsGate.gpsQueue.size(); counters[2] = n->gpsInUse() ? 1 : 0; }
@@ -108,7 +98,7 @@ int32_t lvh_seq_gps_last(lvh_seq* s, double cov[36], int32_t counters[3])
 // MapOptimizationNode::posesCorrected / aLoopIsClosed
 int32_t lvh_seq_poses_corrected(lvh_seq* s)
 {
-    if (!s) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!s) return fail("null argument");
     return static_cast<MapOptimizationNode*>(lvh_seq_node(s))->posesCorrected;
 }
 

@@ -1,25 +1,13 @@
 // C entry points over the loop confirmation of the host mirror (lvi_pnp_host.hpp): PnPRansac and the LoopDetector's
 // usePnP hook, for replay harnesses that are not C++.  include/lvi_pnp.h is exported by liblvi_hip.so only, so this file
 // is linked into host/liblvi_host_hip.so alone (build.py), never into a host library built against the CPU oracle.
-#include <string>
 
 #include "lvi_bow_capi_detail.hpp"
 #include "lvi_pnp_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
 using lvi_host_capi::Detector;
-
-namespace {
-thread_local std::string g_err;
-
-template <class F>
-int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 extern "C" {
 
@@ -38,7 +26,7 @@ lvi_pnp* lvh_pnp_handle(void* p) { return p ? static_cast<PnPRansac*>(p)->get() 
 // PnPRansac::status: matched_2d_old_norm [n][2], matched_3d [n][3] -> status [n]
 int32_t lvh_pnp_status(void* p, const float* matched_2d_old_norm, const float* matched_3d, int32_t n, uint8_t* status)
 {
-    if (!p || n < 0 || (n > 0 && (!matched_2d_old_norm || !matched_3d || !status))) { g_err = "bad arguments"; return LVI_ERR_INVALID_ARG; }
+    if (!p || n < 0 || (n > 0 && (!matched_2d_old_norm || !matched_3d || !status))) return fail("bad arguments");
     return guarded([&]() -> int32_t {
         std::vector<Point2f> a(n);
         std::vector<Point3f> b(n);
@@ -55,7 +43,7 @@ int32_t lvh_pnp_status(void* p, const float* matched_2d_old_norm, const float* m
 // LoopDetector::usePnP on the detector of lvh_bow_create; pnp = NULL removes the hook.  The PnPRansac must outlive its use.
 int32_t lvh_bow_use_pnp(void* d, void* pnp)
 {
-    if (!d) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!d) return fail("null argument");
     static_cast<Detector*>(d)->ld.usePnP(static_cast<PnPRansac*>(pnp));
     return LVI_OK;
 }
@@ -64,7 +52,7 @@ int32_t lvh_bow_use_pnp(void* d, void* pnp)
 // status [n] (any may be NULL); returns n, 0 when PnPRANSAC did not run
 int32_t lvh_bow_pnp_connection(void* d, float* matched_3d, float* matched_2d_old_norm, uint8_t* status)
 {
-    if (!d) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!d) return fail("null argument");
     const Connection& c = static_cast<Detector*>(d)->last.connection;
     const size_t n = c.pnp_status.size();
     if (matched_3d) for (size_t i = 0; i < n; i++) { matched_3d[3 * i] = c.front_3d[i].x; matched_3d[3 * i + 1] = c.front_3d[i].y; matched_3d[3 * i + 2] = c.front_3d[i].z; }

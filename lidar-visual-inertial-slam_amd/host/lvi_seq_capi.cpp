@@ -7,18 +7,9 @@
 #include <memory>
 
 #include "lvi_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
-
-namespace {
-thread_local std::string g_err;
-template <class F> int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 struct lvh_seq {
     std::unique_ptr<LidarHandle> h;
@@ -127,24 +118,24 @@ int32_t lvh_seq_scan_device(lvh_seq* s, const void* d_pts, int32_t n_raw, double
 // a keyframe of an earlier session; the node's pose becomes the seeded one
 int32_t lvh_seq_seed_keyframe(lvh_seq* s, const lvi_pt* corner, int32_t nc, const lvi_pt* surf, int32_t ns, const float pose[6], double time)
 {
-    if (!s || !pose || (nc > 0 && !corner) || (ns > 0 && !surf)) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!s || !pose || (nc > 0 && !corner) || (ns > 0 && !surf)) return fail("null argument");
     return guarded([&]() -> int32_t { return s->mo->seedKeyFrame(corner, nc, surf, ns, pose, time); });
 }
 // key indices of the last extractCloud, in fuse order
 int32_t lvh_seq_keys(lvh_seq* s, int32_t* keys, int32_t capacity, int32_t* n)
 {
-    if (!s || !n) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!s || !n) return fail("null argument");
     *n = (int32_t)s->mo->lastKeys.size();
-    if (keys) { if (capacity < *n) { g_err = "capacity too small"; return LVI_ERR_CAPACITY; } std::memcpy(keys, s->mo->lastKeys.data(), sizeof(int32_t) * (size_t)*n); }
+    if (keys) { if (capacity < *n) return fail("capacity too small", LVI_ERR_CAPACITY); std::memcpy(keys, s->mo->lastKeys.data(), sizeof(int32_t) * (size_t)*n); }
     return LVI_OK;
 }
 // cloudKeyPoses6D: [n][8] = x y z roll pitch yaw time index
 int32_t lvh_seq_keyposes(lvh_seq* s, double* rows, int32_t capacity, int32_t* n)
 {
-    if (!s || !n) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!s || !n) return fail("null argument");
     *n = (int32_t)s->mo->cloudKeyPoses6D.size();
     if (rows) {
-        if (capacity < *n) { g_err = "capacity too small"; return LVI_ERR_CAPACITY; }
+        if (capacity < *n) return fail("capacity too small", LVI_ERR_CAPACITY);
         for (int i = 0; i < *n; i++) {
             const PointTypePose& p = s->mo->cloudKeyPoses6D[i];
             const double r[8] = {p.x, p.y, p.z, p.roll, p.pitch, p.yaw, p.time, p.intensity};
@@ -208,10 +199,10 @@ void* lvh_trk_node(lvh_trk* t) { return t ? t->node.get() : nullptr; }
 // cur_pts / ids / track_cnt of the tracker after the last callback: [n][4] = x, y, id, track_cnt
 int32_t lvh_trk_points(lvh_trk* t, float* rows, int32_t capacity, int32_t* n)
 {
-    if (!t || !n) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!t || !n) return fail("null argument");
     *n = (int32_t)t->ft->cur_pts.size();
     if (rows) {
-        if (capacity < *n) { g_err = "capacity too small"; return LVI_ERR_CAPACITY; }
+        if (capacity < *n) return fail("capacity too small", LVI_ERR_CAPACITY);
         for (int i = 0; i < *n; i++) { rows[4 * i] = t->ft->cur_pts[i].x; rows[4 * i + 1] = t->ft->cur_pts[i].y; rows[4 * i + 2] = (float)t->ft->ids[i]; rows[4 * i + 3] = (float)t->ft->track_cnt[i]; }
     }
     return LVI_OK;

@@ -6,23 +6,12 @@
 // lvi_tracker per camera, called one after another as feature_tracker_node.cpp:136-166 does — the yardstick the rig is held to.
 #include <cstring>
 #include <memory>
-#include <string>
 
 #include "lvi_fmat_host.hpp"
 #include "lvi_tbatch_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
-
-namespace {
-thread_local std::string g_err;
-template <class F>
-int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 struct lvh_rig {
     int S = 0;
@@ -70,7 +59,7 @@ void lvh_rig_destroy(lvh_rig* r) { delete r; }
 // every camera's findFundamentalMat := a DeviceFundamental of its own (lvi_fmat_host.hpp)
 int32_t lvh_rig_use_device_fundamental(lvh_rig* r, int32_t device)
 {
-    if (!r) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!r) return fail("null argument");
     return guarded([&]() -> int32_t {
         for (int i = 0; i < r->S; i++) {
             auto df = std::make_shared<DeviceFundamental>(device);
@@ -86,8 +75,8 @@ int32_t lvh_rig_use_device_fundamental(lvh_rig* r, int32_t device)
 // rejectWithF of all cameras := ONE BatchedFundamental::find per frame (lvi_fmatb_host.hpp); the batched form only
 int32_t lvh_rig_use_batched_fundamental(lvh_rig* r, int32_t device)
 {
-    if (!r) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
-    if (!r->rig) { g_err = "the batched rejectWithF needs a rig created with batched = 1"; return LVI_ERR_STATE; }
+    if (!r) return fail("null argument");
+    if (!r->rig) return fail("the batched rejectWithF needs a rig created with batched = 1", LVI_ERR_STATE);
     return guarded([&]() -> int32_t {
         std::unique_ptr<BatchedFundamental> bf(new BatchedFundamental(device, r->S));
         r->rig->useBatchedFundamental(bf.get());
@@ -100,7 +89,7 @@ int32_t lvh_rig_use_batched_fundamental(lvh_rig* r, int32_t device)
 // handle's calls; otherwise those of the per-camera device hooks), and the cameras that prepared over all frames (batched only)
 int32_t lvh_rig_fundamental_stats(lvh_rig* r, int64_t* out)
 {
-    if (!r || !out) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!r || !out) return fail("null argument");
     return guarded([&]() -> int32_t {
         out[0] = out[1] = 0;
         for (int i = 0; i < r->S; i++) { out[0] += r->cam(i).rejectWithF_skipped; out[1] += r->cam(i).rejectWithF_removed; }
@@ -113,7 +102,7 @@ int32_t lvh_rig_fundamental_stats(lvh_rig* r, int64_t* out)
 // imgs[slots] (row x col, tightly packed; NULL = no image for that camera), times[slots], pub_this_frame[slots]
 int32_t lvh_rig_read_images(lvh_rig* r, const uint8_t* const* imgs, const double* times, const int32_t* pub_this_frame)
 {
-    if (!r || !imgs || !times || !pub_this_frame) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!r || !imgs || !times || !pub_this_frame) return fail("null argument");
     return guarded([&]() -> int32_t {
         if (r->rig) {
             bool pub[LVI_TRACKER_MAX_BATCH];
@@ -133,7 +122,7 @@ int32_t lvh_rig_read_images(lvh_rig* r, const uint8_t* const* imgs, const double
 // the node's updateID loop over the cameras (feature_tracker_node.cpp:157-166)
 int32_t lvh_rig_update_ids(lvh_rig* r)
 {
-    if (!r) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!r) return fail("null argument");
     for (unsigned int i = 0;; i++) {
         bool completed = false;
         for (int j = 0; j < r->S; j++) completed |= r->cam(j).updateID(i);
@@ -147,11 +136,11 @@ void lvh_rig_reset_ids(void) { FeatureTrackerState::n_id() = 0; }
 // one camera's lists after the last frame: xy_un_vel [n][6] = cur_pts, cur_un_pts, pts_velocity; id_cnt [n][2] = ids, track_cnt
 int32_t lvh_rig_camera(lvh_rig* r, int32_t cam, float* xy_un_vel, int32_t* id_cnt, int32_t capacity, int32_t* n)
 {
-    if (!r || !n || cam < 0 || cam >= r->S) { g_err = "bad argument"; return LVI_ERR_INVALID_ARG; }
+    if (!r || !n || cam < 0 || cam >= r->S) return fail("bad argument");
     const FeatureTrackerState& c = r->cam(cam);
     *n = (int32_t)c.cur_pts.size();
     if (!xy_un_vel && !id_cnt) return LVI_OK;
-    if (capacity < *n) { g_err = "capacity too small"; return LVI_ERR_CAPACITY; }
+    if (capacity < *n) return fail("capacity too small", LVI_ERR_CAPACITY);
     for (int i = 0; i < *n; i++) {
         const size_t k = (size_t)i;
         if (xy_un_vel) {

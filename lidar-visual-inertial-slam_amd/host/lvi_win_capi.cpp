@@ -2,21 +2,11 @@
 // harnesses that are not C++.  include/lvi_win.h is exported by liblvi_hip.so only, so this file is linked into
 // host/liblvi_host_hip.so alone (build.py), never into a host library built against the CPU oracle.
 #include <cstring>
-#include <string>
 
 #include "lvi_win_host.hpp"
+#include "lvi_capi_util.hpp"
 
 using namespace lvi_host;
-
-namespace {
-thread_local std::string g_err;
-template <class F> int32_t guarded(F&& f)
-{
-    try { return f(); }
-    catch (const Error& e) { g_err = e.what(); return e.code; }
-    catch (const std::exception& e) { g_err = e.what(); return LVI_ERR_HIP; }
-}
-}  // namespace
 
 extern "C" {
 
@@ -42,7 +32,7 @@ lvi_win* lvh_win_handle(void* p) { return p ? static_cast<VinsWindowOptimizer*>(
 // pre_integrations[j], j = 1..WINDOW_SIZE; rec NULL: no factor for that interval.  The ids of the record are ignored.
 int32_t lvh_win_set_imu(void* p, int32_t j, const lvi_win_imu* rec)
 {
-    if (!p || j < 1 || j > VinsWindowOptimizer::WINDOW_SIZE) { g_err = "bad argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p || j < 1 || j > VinsWindowOptimizer::WINDOW_SIZE) return fail("bad argument");
     VinsWindowOptimizer* v = static_cast<VinsWindowOptimizer*>(p);
     v->hasImu[j - 1] = rec != nullptr;
     if (rec) v->preIntegrations[j - 1] = *rec;
@@ -52,7 +42,7 @@ int32_t lvh_win_set_imu(void* p, int32_t j, const lvi_win_imu* rec)
 // lidar_depth_flag per feature of the marginaliser's feature list
 int32_t lvh_win_set_lidar_flags(void* p, int32_t count, const int32_t* flags)
 {
-    if (!p || count < 0 || (count > 0 && !flags)) { g_err = "bad argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p || count < 0 || (count > 0 && !flags)) return fail("bad argument");
     VinsWindowOptimizer* v = static_cast<VinsWindowOptimizer*>(p);
     v->lidarDepthFlag.assign((size_t)count, 0);
     for (int k = 0; k < count; k++) v->lidarDepthFlag[k] = flags[k] != 0;
@@ -62,7 +52,7 @@ int32_t lvh_win_set_lidar_flags(void* p, int32_t count, const int32_t* flags)
 // estimator.cpp:696-811; flag 0 MARGIN_OLD, 1 MARGIN_SECOND_NEW (the time budget).  Returns the solve's status or an error.
 int32_t lvh_win_optimize(void* p, int32_t flag, lvi_win_info* info)
 {
-    if (!p || (flag != 0 && flag != 1)) { g_err = "bad argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p || (flag != 0 && flag != 1)) return fail("bad argument");
     VinsWindowOptimizer* v = static_cast<VinsWindowOptimizer*>(p);
     return guarded([&]() -> int32_t {
         const int32_t st = v->optimize(flag == 0 ? VinsMarginalizer::MARGIN_OLD : VinsMarginalizer::MARGIN_SECOND_NEW);
@@ -75,7 +65,7 @@ int32_t lvh_win_optimize(void* p, int32_t flag, lvi_win_info* info)
 // feature of the list (cap entries at most; *count: the list's length)
 int32_t lvh_win_get_window(void* p, double* pose, double* speed_bias, double* ex_pose, double* td, int32_t cap, int32_t* count, double* inv_dep)
 {
-    if (!p) { g_err = "null argument"; return LVI_ERR_INVALID_ARG; }
+    if (!p) return fail("null argument");
     const VinsMarginalizer& w = static_cast<VinsWindowOptimizer*>(p)->win;
     if (pose) std::memcpy(pose, w.paraPose, sizeof(w.paraPose));
     if (speed_bias) std::memcpy(speed_bias, w.paraSpeedBias, sizeof(w.paraSpeedBias));
@@ -84,7 +74,7 @@ int32_t lvh_win_get_window(void* p, double* pose, double* speed_bias, double* ex
     const int n = (int)w.features.size();
     if (count) *count = n;
     if (inv_dep) {
-        if (cap < n) { g_err = "the array is shorter than the feature list"; return LVI_ERR_CAPACITY; }
+        if (cap < n) return fail("the array is shorter than the feature list", LVI_ERR_CAPACITY);
         for (int k = 0; k < n; k++) inv_dep[k] = w.features[k].inv_dep;
     }
     return LVI_OK;

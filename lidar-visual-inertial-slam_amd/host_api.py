@@ -8,10 +8,16 @@ import ctypes as C
 import os
 import subprocess
 from shutil import which
+from typing import NamedTuple
 
 import numpy as np
 
 from . import _abi as A
+from .fman import FmanFrameInfo, FmanParams, FmanTriInfo
+from .loop import LoopInfo
+from .marg import MargInfo, MargParams
+from .pgo import PgoInfo
+from .win import WinInfo, WinParams
 
 HOST_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host")
 HOST_HIP_LIB = os.path.join(HOST_DIR, "liblvi_host_hip.so")
@@ -31,52 +37,197 @@ class SeqResult(C.Structure):
 FUNDAMENTAL_FN = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_double, C.POINTER(C.c_uint8), C.c_void_p)
 
 
-# the depth register's flattening (include/lvi_depth.h is exported by liblvi_hip.so only): linked into the HIP host library alone
-DEPTH_SOURCES = ("lvi_depth_capi.cpp",)
-# the device RANSAC's (include/lvi_fmat.h, the same restriction)
-FMAT_SOURCES = ("lvi_fmat_capi.cpp",)
-# the global mapper's (include/lvi_gmap.h, the same restriction)
-GMAP_SOURCES = ("lvi_gmap_capi.cpp",)
-# the loop closer's (include/lvi_loop.h, the same restriction)
-LOOP_SOURCES = ("lvi_loop_capi.cpp",)
-# the keyframe describer's (include/lvi_kf.h, the same restriction)
-KF_SOURCES = ("lvi_kf_capi.cpp",)
-# the loop detector's (include/lvi_bow.h, the same restriction)
-BOW_SOURCES = ("lvi_bow_capi.cpp",)
-# the loop confirmation's (include/lvi_pnp.h, the same restriction; it hooks into the loop detector, so BOW_SOURCES go with it)
-PNP_SOURCES = ("lvi_pnp_capi.cpp",)
-# the pose-graph back end's (include/lvi_pgo.h, the same restriction; it reads the loop closer's constraints, so LOOP_SOURCES go with it)
-PGO_SOURCES = ("lvi_pgo_capi.cpp",)
-# the camera rig's (include/lvi_tbatch.h, the same restriction; its cameras may take the device RANSAC, so FMAT_SOURCES go with it)
-TBATCH_SOURCES = ("lvi_tbatch_capi.cpp",)
-# the window marginalisation's (include/lvi_marg.h, the same restriction)
-MARG_SOURCES = ("lvi_marg_capi.cpp",)
-# the window solve's (include/lvi_win.h, the same restriction; it optimises the marginaliser's window arrays, so MARG_SOURCES go with it)
-WIN_SOURCES = ("lvi_win_capi.cpp",)
-# the feature manager's (include/lvi_fman.h, the same restriction; fillWindow writes into both, so MARG_SOURCES and WIN_SOURCES go with it)
-FMAN_SOURCES = ("lvi_fman_capi.cpp",)
+_P, _vp, _cp, _i32, _i64, _f32, _f64 = C.POINTER, C.c_void_p, C.c_char_p, C.c_int32, C.c_int64, C.c_float, C.c_double
+_ip, _fp, _dp = _P(_i32), _P(_f32), _P(_f64)
+_scan = [_vp, _vp, _i32, _f64, _i32, _f32, _f32, _f32, _P(SeqResult)]
+
+# name -> (restype, argtypes) of host/lvi_seq_capi.cpp: in every host library, whatever it is linked against
+CORE_SIGNATURES = {
+    "lvh_last_error": (_cp, []),
+    "lvh_seq_params_default": (None, [_P(SeqParams)]),
+    "lvh_seq_create": (_vp, [_P(A.LidarParams), _i32, _P(SeqParams)]),
+    "lvh_seq_destroy": (None, [_vp]),
+    "lvh_seq_handle": (_vp, [_vp]),
+    "lvh_seq_scan": (_i32, _scan),
+    "lvh_seq_scan_device": (_i32, _scan),
+    "lvh_seq_seed_keyframe": (_i32, [_vp, _vp, _i32, _vp, _i32, _fp, _f64]),
+    "lvh_seq_keys": (_i32, [_vp, _vp, _i32, _ip]),
+    "lvh_seq_keyposes": (_i32, [_vp, _vp, _i32, _ip]),
+    "lvh_trk_create": (_vp, [_P(A.TrackerParams), _i32, _i32, _i32, _i32, _i32, _P(A.MeiParams)]),
+    "lvh_trk_destroy": (None, [_vp]),
+    "lvh_trk_set_fundamental_hook": (None, [_vp, FUNDAMENTAL_FN, _vp]),
+    "lvh_trk_image": (_i32, [_vp, _vp, _f64, _ip, _ip, _vp, _vp, _i32, _ip]),
+    "lvh_trk_points": (_i32, [_vp, _vp, _i32, _ip]),
+}
+# exported for the other translation units of the library only (they reach the node objects through these)
+INTERNAL_EXPORTS = ("lvh_seq_node", "lvh_trk_node")
+
+
+class Component(NamedTuple):
+    """one optional part of the host mirror: include/lvi_X.h is exported by liblvi_hip.so only, so host/lvi_X_capi.cpp is
+    linked into the HIP host library alone, never into one built against the CPU oracle"""
+    sources: tuple          # under host/
+    needs: tuple            # components whose sources go with it
+    flag: str               # the HostLibrary attribute it sets ...
+    probe: str              # ... when the library exports this
+    last_error: str
+    signatures: dict        # name -> (restype, argtypes), every export of `sources`
+
+
+def _component(name, signatures, needs=(), flag=None, probe=None, err=None):
+    last_error = f"lvh_{err or name}_last_error"
+    return Component((f"lvi_{name}_capi.cpp",), tuple(needs), flag or "has_" + name, probe or f"lvh_{name}_create", last_error,
+                     {last_error: (_cp, []), **signatures})
+
+
+COMPONENTS = {
+    "depth": _component("depth", {
+        "lvh_depth_create": (_vp, [_i32, _i32, _i32, _i32, _i32, _f64]),
+        "lvh_depth_destroy": (None, [_vp]),
+        "lvh_depth_handle": (_vp, [_vp]),
+        "lvh_depth_install": (_i32, [_vp, _vp]),
+        "lvh_depth_lidar": (_i32, [_vp, _vp, _i32, _fp, _f64, _ip]),
+        "lvh_depth_set_image_pose": (_i32, [_vp, _fp]),
+    }),
+    # the device RANSAC behind a TrackerNode's rejectWithF
+    "fmat": _component("fmat", {
+        "lvh_trk_use_device_fundamental": (_i32, [_vp, _i32]),
+    }, probe="lvh_trk_use_device_fundamental"),
+    "gmap": _component("gmap", {
+        "lvh_gmap_create": (_vp, [_vp, _f32, _f32, _f32]),
+        "lvh_gmap_destroy": (None, [_vp]),
+        "lvh_gmap_reserve": (_i32, [_vp, _i32]),
+        "lvh_gmap_keys": (_i32, [_vp, _vp, _i32, _ip]),
+        "lvh_gmap_publish": (_i32, [_vp, _ip]),
+        "lvh_gmap_cloud": (_i32, [_vp, _vp, _i32, _ip]),
+        "lvh_gmap_save": (_i32, [_vp, _cp, _f32]),
+    }),
+    "loop": _component("loop", {
+        "lvh_loop_create": (_vp, [_vp, _f32, _f32, _i32, _f32, _f32, _i32]),
+        "lvh_loop_destroy": (None, [_vp]),
+        "lvh_loop_reserve": (_i32, [_vp, _i32, _i32]),
+        "lvh_loop_info_msg": (_i32, [_vp, _dp, _i32]),
+        "lvh_loop_detect": (_i32, [_vp, _i32, _f64, _ip]),
+        "lvh_loop_start": (_i32, [_vp, _f64]),
+        "lvh_loop_finish": (_i32, [_vp, _P(LoopInfo)]),
+        "lvh_loop_queue_size": (_i32, [_vp]),
+        "lvh_loop_pop": (_i32, [_vp, _ip, _dp, _fp]),
+        "lvh_loop_closed": (_i32, [_vp, _vp, _i32, _ip]),
+        "lvh_loop_cloud": (_i32, [_vp, _i32, _vp, _i32, _ip]),
+    }),
+    "kf": _component("kf", {
+        "lvh_kf_create": (_vp, [_i32] * 6 + [_ip] * 4),
+        "lvh_kf_destroy": (None, [_vp]),
+        "lvh_kf_handle": (_vp, [_vp]),
+        "lvh_kf_add": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _P(A.MeiParams), _ip]),
+        "lvh_kf_remove": (_i32, [_vp, _i32]),
+        "lvh_kf_connect": (_i32, [_vp, _i32, _i32, _ip]),
+        "lvh_kf_connection": (_i32, [_vp] * 8 + [_i32]),
+    }),
+    "bow": _component("bow", {
+        "lvh_bow_create": (_vp, [_i32] * 6 + [_ip] * 4 + [_i32]),
+        "lvh_bow_destroy": (None, [_vp]),
+        "lvh_bow_kf_handle": (_vp, [_vp]),
+        "lvh_bow_db_handle": (_vp, [_vp]),
+        "lvh_bow_load_vocabulary": (_i32, [_vp, _cp]),
+        "lvh_bow_add_keyframe": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _ip, _vp]),
+        "lvh_bow_connection": (_i32, [_vp, _vp, _vp, _vp]),
+    }),
+    # it hooks into the loop detector
+    "pnp": _component("pnp", {
+        "lvh_pnp_create": (_vp, [_i32, _i32, _i32]),
+        "lvh_pnp_destroy": (None, [_vp]),
+        "lvh_pnp_handle": (_vp, [_vp]),
+        "lvh_pnp_status": (_i32, [_vp, _vp, _vp, _i32, _vp]),
+        "lvh_bow_use_pnp": (_i32, [_vp, _vp]),
+        "lvh_bow_pnp_connection": (_i32, [_vp, _vp, _vp, _vp]),
+    }, needs=("bow",)),
+    # it reads the loop closer's constraints
+    "pgo": _component("pgo", {
+        "lvh_pgo_create": (_vp, [_i32, _i32, _i32, _i32, _i32, _f64]),
+        "lvh_pgo_destroy": (None, [_vp]),
+        "lvh_pgo_handle": (_vp, [_vp]),
+        "lvh_seq_use_pose_graph": (_i32, [_vp, _vp]),
+        "lvh_pgo_push_loop": (_i32, [_vp, _i32, _i32, _dp, _f32]),
+        "lvh_pgo_last": (_i32, [_vp, _P(PgoInfo), _fp, _ip]),
+        "lvh_seq_poses_corrected": (_i32, [_vp]),
+        "lvh_seq_use_gps": (_i32, [_vp, _i32, _f32, _f32]),
+        "lvh_seq_gps_push": (_i32, [_vp, _f64, _dp, _dp]),
+        "lvh_seq_gps_last": (_i32, [_vp, _dp, _ip]),
+    }, needs=("loop",)),
+    # the camera rig; its cameras may take the device RANSAC
+    "tbatch": _component("tbatch", {
+        "lvh_rig_create": (_vp, [_P(A.TrackerParams), _i32, _i32, _i32, _i32, _i32, _P(A.MeiParams), _i32]),
+        "lvh_rig_destroy": (None, [_vp]),
+        "lvh_rig_use_device_fundamental": (_i32, [_vp, _i32]),
+        "lvh_rig_use_batched_fundamental": (_i32, [_vp, _i32]),
+        "lvh_rig_fundamental_stats": (_i32, [_vp, _P(_i64)]),
+        "lvh_rig_read_images": (_i32, [_vp, _P(_vp), _dp, _ip]),
+        "lvh_rig_update_ids": (_i32, [_vp]),
+        "lvh_rig_reset_ids": (None, []),
+        "lvh_rig_camera": (_i32, [_vp, _i32, _vp, _vp, _i32, _ip]),
+    }, needs=("fmat",), flag="has_rig", probe="lvh_rig_create", err="rig"),
+    "marg": _component("marg", {
+        "lvh_marg_create": (_vp, [_i32, _i32, _i32, _P(MargParams)]),
+        "lvh_marg_destroy": (None, [_vp]),
+        "lvh_marg_handle": (_vp, [_vp]),
+        "lvh_marg_set_window": (_i32, [_vp, _dp, _dp, _dp, _f64]),
+        "lvh_marg_set_features": (_i32, [_vp, _i32, _ip, _ip, _dp, _dp]),
+        "lvh_marg_set_imu": (_i32, [_vp, _f64, _dp, _dp]),
+        "lvh_marg_run": (_i32, [_vp, _i32, _ip, _P(MargInfo)]),
+    }),
+    # it optimises the marginaliser's window arrays
+    "win": _component("win", {
+        "lvh_win_create": (_vp, [_vp, _i32, _i32, _i32, _i32, _f64, _P(WinParams)]),
+        "lvh_win_destroy": (None, [_vp]),
+        "lvh_win_handle": (_vp, [_vp]),
+        "lvh_win_set_imu": (_i32, [_vp, _i32, _vp]),
+        "lvh_win_set_lidar_flags": (_i32, [_vp, _i32, _ip]),
+        "lvh_win_optimize": (_i32, [_vp, _i32, _P(WinInfo)]),
+        "lvh_win_get_window": (_i32, [_vp, _dp, _dp, _dp, _dp, _i32, _ip, _dp]),
+    }, needs=("marg",)),
+    # fillWindow writes into both
+    "fman": _component("fman", {
+        "lvh_fman_create": (_vp, [_i32, _i32, _P(FmanParams)]),
+        "lvh_fman_destroy": (None, [_vp]),
+        "lvh_fman_handle": (_vp, [_vp]),
+        "lvh_fman_clear_state": (_i32, [_vp]),
+        "lvh_fman_add_frame": (_i32, [_vp, _i32, _i32, _ip, _dp, _f64, _P(FmanFrameInfo)]),
+        "lvh_fman_triangulate": (_i32, [_vp, _dp, _dp, _dp, _dp, _P(FmanTriInfo)]),
+        "lvh_fman_fill_window": (_i32, [_vp, _vp, _vp]),
+        "lvh_fman_take_depths": (_i32, [_vp, _vp]),
+        "lvh_fman_remove_failures": (_i32, [_vp]),
+        "lvh_fman_slide_old": (_i32, [_vp, _i32, _dp, _dp, _dp, _dp, _dp, _dp]),
+        "lvh_fman_slide_new": (_i32, [_vp, _i32]),
+    }, needs=("marg", "win")),
+}
+
+
+def component_sources(names=None):
+    """the source files of the named components and of everything they need, each once, in table order (None: all)"""
+    want, todo = set(), list(COMPONENTS if names is None else names)
+    while todo:
+        name = todo.pop()
+        if name not in want:
+            want.add(name)
+            todo += COMPONENTS[name].needs
+    return tuple(f for name, c in COMPONENTS.items() if name in want for f in c.sources)
+
+
+def host_dependencies(sources=()):
+    """what a host library of these sources is rebuilt for: its .cpp files, every host/*.hpp and every include/*.h (no
+    host file includes anything else of the project's)"""
+    inc = os.path.normpath(os.path.join(HOST_DIR, "..", "..", "include"))
+    return ([os.path.join(HOST_DIR, f) for f in ("lvi_seq_capi.cpp", *sources)]
+            + sorted(os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR) if f.endswith(".hpp"))
+            + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")))
 
 
 def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
     """g++ -shared of host/lvi_seq_capi.cpp (+ the named host/ sources) against lib<link_name>.so in link_dir (rpath set)"""
-    srcs = [os.path.join(HOST_DIR, "lvi_seq_capi.cpp")] + [os.path.join(HOST_DIR, f) for f in sources]
-    deps = srcs + [os.path.join(HOST_DIR, "lvi_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_hotpath.h")]
-    if sources:
-        deps += [os.path.join(HOST_DIR, "lvi_depth_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_depth.h"),
-                 os.path.join(HOST_DIR, "lvi_fmat_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmat.h"),
-                 os.path.join(HOST_DIR, "lvi_fmatb_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fmatb.h"),
-                 os.path.join(HOST_DIR, "lvi_gmap_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_gmap.h"),
-                 os.path.join(HOST_DIR, "lvi_loop_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_loop.h"),
-                 os.path.join(HOST_DIR, "lvi_kf_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_kf.h"),
-                 os.path.join(HOST_DIR, "lvi_bow_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_bow.h"),
-                 os.path.join(HOST_DIR, "lvi_bow_capi_detail.hpp"), os.path.join(HOST_DIR, "lvi_pnp_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pnp.h"),
-                 os.path.join(HOST_DIR, "lvi_tbatch_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_tbatch.h"),
-                 os.path.join(HOST_DIR, "lvi_win_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_win.h"),
-                 os.path.join(HOST_DIR, "lvi_fman_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_fman.h"),
-                 os.path.join(HOST_DIR, "lvi_pgo_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_pgo.h"),
-                 os.path.join(HOST_DIR, "lvi_marg_host.hpp"), os.path.join(HOST_DIR, "..", "..", "include", "lvi_marg.h")]
-    if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in deps):
+    if os.path.exists(out_path) and all(os.path.getmtime(d) <= os.path.getmtime(out_path) for d in host_dependencies(sources)):
         return out_path
+    srcs = [os.path.join(HOST_DIR, f) for f in ("lvi_seq_capi.cpp", *sources)]
     cxx = which("g++") or "g++"
     cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", out_path, *srcs, "-L" + link_dir, "-l" + link_name,
            "-Wl,-rpath," + link_dir, *extra]
@@ -87,193 +238,28 @@ def build_host_library(out_path, link_dir, link_name, extra=(), sources=()):
 
 
 class HostLibrary:
+    bind = A.Library.bind
+
     def __init__(self, path):
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path} not found — build it first (python -c 'import __graft_entry__ as g; g.build()')")
         self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-        d = self.dll
-        d.lvh_last_error.restype = C.c_char_p
-        d.lvh_seq_params_default.argtypes = [C.POINTER(SeqParams)]
-        d.lvh_seq_create.restype = C.c_void_p
-        d.lvh_seq_create.argtypes = [C.POINTER(A.LidarParams), C.c_int32, C.POINTER(SeqParams)]
-        d.lvh_seq_destroy.argtypes = [C.c_void_p]
-        d.lvh_seq_handle.restype = C.c_void_p
-        d.lvh_seq_handle.argtypes = [C.c_void_p]
-        scan_args = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_float, C.c_float, C.c_float, C.POINTER(SeqResult)]
-        d.lvh_seq_scan.argtypes = scan_args
-        d.lvh_seq_scan_device.argtypes = scan_args
-        d.lvh_seq_seed_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_double]
-        d.lvh_seq_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        d.lvh_seq_keyposes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        d.lvh_trk_create.restype = C.c_void_p
-        d.lvh_trk_create.argtypes = [C.POINTER(A.TrackerParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(A.MeiParams)]
-        d.lvh_trk_destroy.argtypes = [C.c_void_p]
-        d.lvh_trk_set_fundamental_hook.argtypes = [C.c_void_p, FUNDAMENTAL_FN, C.c_void_p]
-        d.lvh_trk_image.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int32,
-                                    C.POINTER(C.c_int32)]
-        d.lvh_trk_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        self.has_depth = hasattr(d, "lvh_depth_create")      # the HIP host library only
-        if self.has_depth:
-            d.lvh_depth_last_error.restype = C.c_char_p
-            d.lvh_depth_create.restype = C.c_void_p
-            d.lvh_depth_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double]
-            d.lvh_depth_destroy.argtypes = [C.c_void_p]
-            d.lvh_depth_handle.restype = C.c_void_p
-            d.lvh_depth_handle.argtypes = [C.c_void_p]
-            d.lvh_depth_install.argtypes = [C.c_void_p, C.c_void_p]
-            d.lvh_depth_lidar.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_double, C.POINTER(C.c_int32)]
-            d.lvh_depth_set_image_pose.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        self.has_gmap = hasattr(d, "lvh_gmap_create")      # the HIP host library only
-        if self.has_gmap:
-            d.lvh_gmap_last_error.restype = C.c_char_p
-            d.lvh_gmap_create.restype = C.c_void_p
-            d.lvh_gmap_create.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
-            d.lvh_gmap_destroy.argtypes = [C.c_void_p]
-            d.lvh_gmap_reserve.argtypes = [C.c_void_p, C.c_int32]
-            d.lvh_gmap_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-            d.lvh_gmap_publish.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-            d.lvh_gmap_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-            d.lvh_gmap_save.argtypes = [C.c_void_p, C.c_char_p, C.c_float]
-        self.has_loop = hasattr(d, "lvh_loop_create")      # the HIP host library only
-        if self.has_loop:
-            from .loop import LoopInfo
-            d.lvh_loop_last_error.restype = C.c_char_p
-            d.lvh_loop_create.restype = C.c_void_p
-            d.lvh_loop_create.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_int32]
-            d.lvh_loop_destroy.argtypes = [C.c_void_p]
-            d.lvh_loop_reserve.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-            d.lvh_loop_info_msg.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
-            d.lvh_loop_detect.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_int32)]
-            d.lvh_loop_start.argtypes = [C.c_void_p, C.c_double]
-            d.lvh_loop_finish.argtypes = [C.c_void_p, C.POINTER(LoopInfo)]
-            d.lvh_loop_queue_size.argtypes = [C.c_void_p]
-            d.lvh_loop_pop.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float)]
-            d.lvh_loop_closed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-            d.lvh_loop_cloud.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        self.has_kf = hasattr(d, "lvh_kf_create")      # the HIP host library only
-        if self.has_kf:
-            ip = C.POINTER(C.c_int32)
-            d.lvh_kf_last_error.restype = C.c_char_p
-            d.lvh_kf_create.restype = C.c_void_p
-            d.lvh_kf_create.argtypes = [C.c_int32] * 6 + [ip] * 4
-            d.lvh_kf_destroy.argtypes = [C.c_void_p]
-            d.lvh_kf_handle.restype = C.c_void_p
-            d.lvh_kf_handle.argtypes = [C.c_void_p]
-            d.lvh_kf_add.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.POINTER(A.MeiParams), ip]
-            d.lvh_kf_remove.argtypes = [C.c_void_p, C.c_int32]
-            d.lvh_kf_connect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip]
-            d.lvh_kf_connection.argtypes = [C.c_void_p] * 8 + [C.c_int32]
-        self.has_bow = hasattr(d, "lvh_bow_create")      # the HIP host library only
-        if self.has_bow:
-            ip = C.POINTER(C.c_int32)
-            d.lvh_bow_last_error.restype = C.c_char_p
-            d.lvh_bow_create.restype = C.c_void_p
-            d.lvh_bow_create.argtypes = [C.c_int32] * 6 + [ip] * 4 + [C.c_int32]
-            d.lvh_bow_destroy.argtypes = [C.c_void_p]
-            d.lvh_bow_kf_handle.restype = C.c_void_p
-            d.lvh_bow_kf_handle.argtypes = [C.c_void_p]
-            d.lvh_bow_db_handle.restype = C.c_void_p
-            d.lvh_bow_db_handle.argtypes = [C.c_void_p]
-            d.lvh_bow_load_vocabulary.argtypes = [C.c_void_p, C.c_char_p]
-            d.lvh_bow_add_keyframe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_int32, C.c_void_p, C.c_void_p, ip, C.c_void_p]
-            d.lvh_bow_connection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.has_pnp = hasattr(d, "lvh_pnp_create")      # the HIP host library only
-        if self.has_pnp:
-            d.lvh_pnp_last_error.restype = C.c_char_p
-            d.lvh_pnp_create.restype = C.c_void_p
-            d.lvh_pnp_create.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-            d.lvh_pnp_destroy.argtypes = [C.c_void_p]
-            d.lvh_pnp_handle.restype = C.c_void_p
-            d.lvh_pnp_handle.argtypes = [C.c_void_p]
-            d.lvh_pnp_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-            d.lvh_bow_use_pnp.argtypes = [C.c_void_p, C.c_void_p]
-            d.lvh_bow_pnp_connection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.has_pgo = hasattr(d, "lvh_pgo_create")      # the HIP host library only
-        if self.has_pgo:
-            from .pgo import PgoInfo
-            d.lvh_pgo_last_error.restype = C.c_char_p
-            d.lvh_pgo_create.restype = C.c_void_p
-            d.lvh_pgo_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double]
-            d.lvh_pgo_destroy.argtypes = [C.c_void_p]
-            d.lvh_pgo_handle.restype = C.c_void_p
-            d.lvh_pgo_handle.argtypes = [C.c_void_p]
-            d.lvh_seq_use_pose_graph.argtypes = [C.c_void_p, C.c_void_p]
-            d.lvh_pgo_push_loop.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_float]
-            d.lvh_pgo_last.argtypes = [C.c_void_p, C.POINTER(PgoInfo), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-            d.lvh_seq_poses_corrected.argtypes = [C.c_void_p]
-            d.lvh_seq_use_gps.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float]
-            d.lvh_seq_gps_push.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-            d.lvh_seq_gps_last.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-        self.has_marg = hasattr(d, "lvh_marg_create")      # the HIP host library only
-        if self.has_marg:
-            from .marg import MargInfo, MargParams
-            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-            d.lvh_marg_last_error.restype = C.c_char_p
-            d.lvh_marg_create.restype = C.c_void_p
-            d.lvh_marg_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(MargParams)]
-            d.lvh_marg_destroy.argtypes = [C.c_void_p]
-            d.lvh_marg_handle.restype = C.c_void_p
-            d.lvh_marg_handle.argtypes = [C.c_void_p]
-            d.lvh_marg_set_window.argtypes = [C.c_void_p, dp, dp, dp, C.c_double]
-            d.lvh_marg_set_features.argtypes = [C.c_void_p, C.c_int32, ip, ip, dp, dp]
-            d.lvh_marg_set_imu.argtypes = [C.c_void_p, C.c_double, dp, dp]
-            d.lvh_marg_run.argtypes = [C.c_void_p, C.c_int32, ip, C.POINTER(MargInfo)]
-        self.has_win = hasattr(d, "lvh_win_create")       # the HIP host library only
-        if self.has_win:
-            from .win import WinImu, WinInfo, WinParams
-            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-            d.lvh_win_last_error.restype = C.c_char_p
-            d.lvh_win_create.restype = C.c_void_p
-            d.lvh_win_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(WinParams)]
-            d.lvh_win_destroy.argtypes = [C.c_void_p]
-            d.lvh_win_handle.restype = C.c_void_p
-            d.lvh_win_handle.argtypes = [C.c_void_p]
-            d.lvh_win_set_imu.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-            d.lvh_win_set_lidar_flags.argtypes = [C.c_void_p, C.c_int32, ip]
-            d.lvh_win_optimize.argtypes = [C.c_void_p, C.c_int32, C.POINTER(WinInfo)]
-            d.lvh_win_get_window.argtypes = [C.c_void_p, dp, dp, dp, dp, C.c_int32, ip, dp]
-        self.has_fman = hasattr(d, "lvh_fman_create")     # the HIP host library only
-        if self.has_fman:
-            from .fman import FmanFrameInfo, FmanParams, FmanTriInfo
-            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-            d.lvh_fman_last_error.restype = C.c_char_p
-            d.lvh_fman_create.restype = C.c_void_p
-            d.lvh_fman_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(FmanParams)]
-            d.lvh_fman_destroy.argtypes = [C.c_void_p]
-            d.lvh_fman_handle.restype = C.c_void_p
-            d.lvh_fman_handle.argtypes = [C.c_void_p]
-            d.lvh_fman_clear_state.argtypes = [C.c_void_p]
-            d.lvh_fman_add_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip, dp, C.c_double, C.POINTER(FmanFrameInfo)]
-            d.lvh_fman_triangulate.argtypes = [C.c_void_p, dp, dp, dp, dp, C.POINTER(FmanTriInfo)]
-            d.lvh_fman_fill_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-            d.lvh_fman_take_depths.argtypes = [C.c_void_p, C.c_void_p]
-            d.lvh_fman_remove_failures.argtypes = [C.c_void_p]
-            d.lvh_fman_slide_old.argtypes = [C.c_void_p, C.c_int32, dp, dp, dp, dp, dp, dp]
-            d.lvh_fman_slide_new.argtypes = [C.c_void_p, C.c_int32]
-        self.has_rig = hasattr(d, "lvh_rig_create")      # the HIP host library only
-        if self.has_rig:
-            d.lvh_rig_last_error.restype = C.c_char_p
-            d.lvh_rig_create.restype = C.c_void_p
-            d.lvh_rig_create.argtypes = [C.POINTER(A.TrackerParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(A.MeiParams), C.c_int32]
-            d.lvh_rig_destroy.argtypes = [C.c_void_p]
-            d.lvh_rig_use_device_fundamental.argtypes = [C.c_void_p, C.c_int32]
-            d.lvh_rig_use_batched_fundamental.argtypes = [C.c_void_p, C.c_int32]
-            d.lvh_rig_fundamental_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-            d.lvh_rig_read_images.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-            d.lvh_rig_update_ids.argtypes = [C.c_void_p]
-            d.lvh_rig_reset_ids.restype = None
-            d.lvh_rig_camera.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        self.has_fmat = hasattr(d, "lvh_trk_use_device_fundamental")      # the HIP host library only
-        if self.has_fmat:
-            d.lvh_fmat_last_error.restype = C.c_char_p
-            d.lvh_trk_use_device_fundamental.argtypes = [C.c_void_p, C.c_int32]
+        self._bound = set()
+        self.bind(CORE_SIGNATURES)
+        for c in COMPONENTS.values():                    # has_depth ... has_fman: the HIP host library only
+            present = hasattr(self.dll, c.probe)
+            if present:
+                self.bind(c.signatures)
+            setattr(self, c.flag, present)
 
     def check(self, code, where):
         if code < 0:
             raise A.LviError(code, where, self.dll.lvh_last_error().decode(errors="replace"))
         return code
+
+
+class _HostOwned(A.Owned):
+    _lib = "hl"
 
 
 class _BorrowedHandle:
@@ -289,9 +275,10 @@ class _BorrowedHandle:
         return getattr(self._obj, k)
 
 
-class SequentialMapper:
+class SequentialMapper(_HostOwned):
     """MapOptimizationNode of host/lvi_host.hpp (updateInitialGuess, extractNearby, extractCloud, scan matching, saveFrame,
     key-pose push; mapOptimization.cpp:298-333, 806-999, 1315-1412, 1529-1603) fed scan by scan"""
+    _ptr, _destroy, _last_error = "_s", "lvh_seq_destroy", "lvh_last_error"
 
     def __init__(self, hostlib, abi_lib, lidar_params, device=0, **seq):
         from .lidar import LidarHotpath
@@ -307,17 +294,6 @@ class SequentialMapper:
         if not self._s:
             raise A.LviError(-3, "lvh_seq_create", hostlib.dll.lvh_last_error().decode(errors="replace"))
         self.handle = _BorrowedHandle(LidarHotpath, abi_lib, hostlib.dll.lvh_seq_handle(self._s), lidar_params)
-
-    def close(self):
-        if self._s:
-            self.hl.dll.lvh_seq_destroy(self._s)
-            self._s = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _res(r):
@@ -397,8 +373,9 @@ class SequentialMapper:
         return out[:n.value].copy()
 
 
-class TrackerNode:
+class TrackerNode(_HostOwned):
     """FeatureTrackerNode of host/lvi_host.hpp: img_callback of feature_tracker_node.cpp:37-231 without ROS"""
+    _ptr, _destroy, _last_error = "_t", "lvh_trk_destroy", "lvh_last_error"
     OUTCOMES = ("first_image", "restart", "not_published", "first_publish_suppressed", "published")
 
     def __init__(self, hostlib, tracker_params, row, col, freq, equalize=False, cam=None, device=0):
@@ -410,11 +387,6 @@ class TrackerNode:
             raise A.LviError(-3, "lvh_trk_create", hostlib.dll.lvh_last_error().decode(errors="replace"))
         self.cap = int(tracker_params.max_features)
         self._hook = None
-
-    def close(self):
-        if self._t:
-            self.hl.dll.lvh_trk_destroy(self._t)
-            self._t = None
 
     def set_fundamental_hook(self, fn):
         """fn(un_cur [n,2], un_forw [n,2], f_threshold) -> status [n] (uint8): the node's cv::findFundamentalMat"""
@@ -461,10 +433,11 @@ class TrackerNode:
         return rows[:n.value].copy()
 
 
-class NodeDepthRegister:
+class NodeDepthRegister(_HostOwned):
     """lvi_host::DepthRegister (host/lvi_depth_host.hpp) installed as the get_depth of a TrackerNode: the node's
     lidar_callback (feature_tracker_node.cpp:273-377) and the depth channel of its messages.  pose6 = (x, y, z, roll,
     pitch, yaw) of the body in the world frame, or None for a failed TF lookup.  HIP host library only."""
+    _ptr, _destroy, _last_error = "_d", "lvh_depth_destroy", "lvh_depth_last_error"
 
     def __init__(self, hostlib, node, abi_lib, device=0, max_clouds=64, max_cloud_points=131072, max_features=150, lidar_skip=3, window_s=5.0):
         from .depth import DepthRegister, bind as depth_bind
@@ -483,19 +456,9 @@ class NodeDepthRegister:
         self.register._h = C.c_void_p(hostlib.dll.lvh_depth_handle(self._d))
         self.register.close = lambda: None
 
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_depth_last_error().decode(errors="replace"))
-        return code
-
     @staticmethod
     def _pose(pose6):
         return None if pose6 is None else (C.c_float * 6)(*[float(v) for v in np.asarray(pose6, np.float32).reshape(6)])
-
-    def close(self):
-        if self._d:
-            self.hl.dll.lvh_depth_destroy(self._d)
-            self._d = None
 
     def lidar_callback(self, cloud, pose6, stamp):
         pts = A.as_pts(cloud)
@@ -508,9 +471,10 @@ class NodeDepthRegister:
         self._check(self.hl.dll.lvh_depth_set_image_pose(self._d, self._pose(pose6)), "lvh_depth_set_image_pose")
 
 
-class GlobalMapper:
+class GlobalMapper(_HostOwned):
     """lvi_host::GlobalMapper (host/lvi_gmap_host.hpp) over a SequentialMapper's node: publishGlobalMap
     (mapOptimization.cpp:460-510) and the save_map service (:179-236).  HIP host library only."""
+    _ptr, _destroy, _last_error = "_g", "lvh_gmap_destroy", "lvh_gmap_last_error"
 
     def __init__(self, hostlib, mapper, search_radius=1000.0, pose_density=1.0, leaf_size=0.05):
         if not hostlib.has_gmap:
@@ -519,22 +483,6 @@ class GlobalMapper:
         self._g = hostlib.dll.lvh_gmap_create(mapper._s, float(search_radius), float(pose_density), float(leaf_size))
         if not self._g:
             raise A.LviError(-1, "lvh_gmap_create", hostlib.dll.lvh_gmap_last_error().decode(errors="replace"))
-
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_gmap_last_error().decode(errors="replace"))
-        return code
-
-    def close(self):
-        if self._g:
-            self.hl.dll.lvh_gmap_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reserve(self, max_points):
         self._check(self.hl.dll.lvh_gmap_reserve(self._g, int(max_points)), "lvh_gmap_reserve")
@@ -563,9 +511,10 @@ class GlobalMapper:
         return bool(self._check(self.hl.dll.lvh_gmap_save(self._g, os.fsencode(str(directory)), float(resolution)), "lvh_gmap_save"))
 
 
-class LoopCloser:
+class LoopCloser(_HostOwned):
     """lvi_host::LoopCloser (host/lvi_loop_host.hpp) over a SequentialMapper's node: the loop-closure thread of
     mapOptimization.cpp (:523-741) up to the constraint queue.  HIP host library only."""
+    _ptr, _destroy, _last_error = "_g", "lvh_loop_destroy", "lvh_loop_last_error"
 
     def __init__(self, hostlib, mapper, search_radius=15.0, search_time_diff=30.0, search_num=25, fitness_score=0.3, surf_leaf=0.4,
                  incremental_cloud=1, **_ignored):
@@ -576,22 +525,6 @@ class LoopCloser:
                                               float(surf_leaf), int(incremental_cloud))
         if not self._g:
             raise A.LviError(-1, "lvh_loop_create", hostlib.dll.lvh_loop_last_error().decode(errors="replace"))
-
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_loop_last_error().decode(errors="replace"))
-        return code
-
-    def close(self):
-        if self._g:
-            self.hl.dll.lvh_loop_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reserve(self, max_source_points, max_target_points):
         self._check(self.hl.dll.lvh_loop_reserve(self._g, int(max_source_points), int(max_target_points)), "lvh_loop_reserve")
@@ -660,9 +593,10 @@ class LoopCloser:
         return out[:n.value].copy()
 
 
-class KeyFrameMatcher:
+class KeyFrameMatcher(_HostOwned):
     """lvi_host::KeyFrameDescriber (host/lvi_kf_host.hpp) with the host halves of its keyframes: the online KeyFrame
     constructor (keyframe.cpp:14-73) and findConnection up to PnPRANSAC (:179-200).  HIP host library only."""
+    _ptr, _destroy, _last_error = "_m", "lvh_kf_destroy", "lvh_kf_last_error"
 
     def __init__(self, hostlib, pattern, device=0, max_width=1024, max_height=576, max_keypoints=8192, max_window=1024, max_keyframes=16):
         if not hostlib.has_kf:
@@ -676,22 +610,6 @@ class KeyFrameMatcher:
                                             *[p.ctypes.data_as(C.POINTER(C.c_int32)) for p in pat])
         if not self._m:
             raise A.LviError(-1, "lvh_kf_create", hostlib.dll.lvh_kf_last_error().decode(errors="replace"))
-
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_kf_last_error().decode(errors="replace"))
-        return code
-
-    def close(self):
-        if self._m:
-            self.hl.dll.lvh_kf_destroy(self._m)
-            self._m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def add(self, slot, img, point_3d, point_2d_uv, point_2d_norm, point_id, cam=None):
         """the online KeyFrame constructor into `slot` -> dict(n_keypoints_found, n_keypoints_stored)"""
@@ -725,11 +643,12 @@ class KeyFrameMatcher:
                         matched_2d_old_norm=v2[3][:m].copy(), matched_3d=p3[:m].copy(), matched_id=ids[:m].copy(), status=st)
 
 
-class LoopDetector:
+class LoopDetector(_HostOwned):
     """lvi_host::LoopDetector (host/lvi_bow_host.hpp) with a keyframe store of its own: LoopDetector::loadVocabulary and
     addKeyFrame of pose_graph/src/loop_detector.cpp (:6-40, 56-154) over the device database of include/lvi_bow.h.  HIP
     host library only.  `store` is a kf.KeyframeDescriber view of the store the C++ side owns: fill a slot through it
     (describe or put), then hand the keyframe's host half to addKeyFrame."""
+    _ptr, _destroy, _last_error = "_d", "lvh_bow_destroy", "lvh_bow_last_error"
 
     def __init__(self, hostlib, abi_lib, pattern, max_entries=4096, device=0, max_width=1024, max_height=576, max_keypoints=8192, max_window=1024,
                  max_keyframes=16):
@@ -751,22 +670,6 @@ class LoopDetector:
         self.store.max_keypoints, self.store.max_window, self.store.max_keyframes = int(max_keypoints), int(max_window), int(max_keyframes)
         self.store._h = C.c_void_p(hostlib.dll.lvh_bow_kf_handle(self._d))
         self.store.close = lambda: None
-
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_bow_last_error().decode(errors="replace"))
-        return code
-
-    def close(self):
-        if self._d:
-            self.hl.dll.lvh_bow_destroy(self._d)
-            self._d = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def loadVocabulary(self, path):
         """the vocabulary file in the VINSLoop layout (pose_graph_node.cpp:300-304); it is not shipped with the project"""
@@ -819,9 +722,10 @@ class LoopDetector:
         return cur[:n].copy(), old[:n].copy(), ids[:n].copy()
 
 
-class HostPnPRansac:
+class HostPnPRansac(_HostOwned):
     """lvi_host::PnPRansac (host/lvi_pnp_host.hpp): KeyFrame::PnPRANSAC (keyframe.cpp:135-176) with the reference's
     arguments (100 iterations, 10.0 / 460.0, 0.99).  HIP host library only.  Install it with LoopDetector.usePnP."""
+    _ptr, _destroy, _last_error = "_p", "lvh_pnp_destroy", "lvh_pnp_last_error"
 
     def __init__(self, hostlib, device=0, max_points=2048, max_iters=100):
         if not hostlib.has_pnp:
@@ -830,17 +734,6 @@ class HostPnPRansac:
         self._p = hostlib.dll.lvh_pnp_create(int(device), int(max_points), int(max_iters))
         if not self._p:
             raise A.LviError(-1, "lvh_pnp_create", hostlib.dll.lvh_pnp_last_error().decode(errors="replace"))
-
-    def close(self):
-        if self._p:
-            self.hl.dll.lvh_pnp_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def status(self, matched_2d_old_norm, matched_3d):
         """the status vector of keyframe.cpp:167-174"""
@@ -855,10 +748,11 @@ class HostPnPRansac:
         return st[:len(p2)].copy()
 
 
-class PoseGraphBackend:
+class PoseGraphBackend(_HostOwned):
     """lvi_host::PoseGraphBackend (host/lvi_pgo_host.hpp): mapOptimization's factor graph over include/lvi_pgo.h and
     include/lvi_pgo_gps.h (graph.add_gps, graph.gps_count, graph.marginal_covariance).  HIP host library only.  Install it with SequentialMapper.usePoseGraph and feed it what
     LoopCloser.pop() returns.  `graph` is a pgo.PoseGraph view of the handle the C++ side owns."""
+    _ptr, _destroy, _last_error = "_p", "lvh_pgo_destroy", "lvh_pgo_last_error"
 
     def __init__(self, hostlib, abi_lib, device=0, max_poses=4096, max_loops=64, full_logmap=-1, max_iters=0, conv_eps=0.0):
         from .pgo import PgoParams, PoseGraph, bind as pgo_bind
@@ -874,17 +768,6 @@ class PoseGraphBackend:
         self.graph._h = C.c_void_p(hostlib.dll.lvh_pgo_handle(self._p))
         self.graph.params = PgoParams()
         self.graph.close = lambda: None
-
-    def close(self):
-        if self._p:
-            self.hl.dll.lvh_pgo_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def push_loop(self, constraint):
         """a dict of LoopCloser.pop(): key_cur, key_pre, between [4, 4], noise; returns the queue's length"""
@@ -916,10 +799,11 @@ class PoseGraphBackend:
                     chi2_before=info.chi2_before, chi2_after=info.chi2_after, max_step=info.max_step, pose_to=np.array(pose[:], np.float32))
 
 
-class VinsMarginalizer:
+class VinsMarginalizer(_HostOwned):
     """lvi_host::VinsMarginalizer (host/lvi_marg_host.hpp): the MARGIN_OLD and MARGIN_SECOND_NEW branches of
     Estimator::optimization (estimator.cpp:813-976) over include/lvi_marg.h, the prior resident on the device.  HIP host
     library only.  `marg` is a marg.Marginalizer view of the handle the C++ side owns (layout, prior, debug_system)."""
+    _ptr, _destroy, _last_error = "_p", "lvh_marg_destroy", "lvh_marg_last_error"
     MARGIN_OLD, MARGIN_SECOND_NEW = 0, 1
     WINDOW_SIZE = 10
 
@@ -941,21 +825,8 @@ class VinsMarginalizer:
         self.marg.params = p
 
     def close(self):
-        if self._p:
-            self.hl.dll.lvh_marg_destroy(self._p)
-            self._p = None
-            self.marg._h = C.c_void_p()                  # the view's handle went with the C++ object
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_marg_last_error().decode(errors="replace"))
-        return code
+        super().close()
+        self.marg._h = C.c_void_p()                  # the view's handle went with the C++ object
 
     def set_window(self, pose, speed_bias, ex_pose, td):
         """vector2double: para_Pose [11, 7], para_SpeedBias [11, 9], para_Ex_Pose [7], para_Td"""
@@ -991,10 +862,11 @@ class VinsMarginalizer:
         return dict(ran=bool(ran.value), status=st, **{k: getattr(info, k) for k, _ in MargInfo._fields_})
 
 
-class VinsWindowOptimizer:
+class VinsWindowOptimizer(_HostOwned):
     """lvi_host::VinsWindowOptimizer (host/lvi_win_host.hpp): the first half of Estimator::optimization (estimator.cpp:696-811)
     over include/lvi_win.h, on the window arrays of a VinsMarginalizer and with its resident prior: `optimize(flag)` then
     `marginalizer.run(flag)` is the tail of Estimator::optimization with no prior on the bus.  HIP host library only."""
+    _ptr, _destroy, _last_error = "_p", "lvh_win_destroy", "lvh_win_last_error"
 
     def __init__(self, hostlib, abi_lib, marginalizer, device=0, max_features=150, estimate_extrinsic=0, num_iterations=8, solver_time=0.0, **params):
         from .win import WinParams, bind as win_bind
@@ -1011,22 +883,6 @@ class VinsWindowOptimizer:
                                              C.byref(p))
         if not self._p:
             raise A.LviError(-1, "lvh_win_create", hostlib.dll.lvh_win_last_error().decode(errors="replace"))
-
-    def close(self):
-        if self._p:
-            self.hl.dll.lvh_win_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_win_last_error().decode(errors="replace"))
-        return code
 
     def set_imu(self, j, record=None):
         """pre_integrations[j], j = 1..WINDOW_SIZE: a one-element win.IMU_DTYPE array (its ids are ignored), or None for no factor"""
@@ -1058,10 +914,11 @@ class VinsWindowOptimizer:
         return dict(pose=pose, speed_bias=sb, ex_pose=ex, td=td.value, inv_dep=inv[:n.value])
 
 
-class FeatureManager:
+class FeatureManager(_HostOwned):
     """lvi_host::FeatureManager (host/lvi_fman_host.hpp): the reference's f_manager over include/lvi_fman.h, with fillWindow /
     takeDepths towards a VinsMarginalizer and a VinsWindowOptimizer and the two slides of estimator.cpp:1076-1099.  HIP host
     library only.  `table` is a fman.FeatureTable view of the handle the C++ side owns (download, projections, ...)."""
+    _ptr, _destroy, _last_error = "_p", "lvh_fman_destroy", "lvh_fman_last_error"
 
     def __init__(self, hostlib, abi_lib, device=0, max_features=1024, **params):
         from .fman import FeatureTable, FmanParams, bind as fman_bind
@@ -1081,21 +938,8 @@ class FeatureManager:
         self.table.params = p
 
     def close(self):
-        if self._p:
-            self.hl.dll.lvh_fman_destroy(self._p)
-            self._p = None
-            self.table._h = C.c_void_p()                 # the view's handle went with the C++ object
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_fman_last_error().decode(errors="replace"))
-        return code
+        super().close()
+        self.table._h = C.c_void_p()                  # the view's handle went with the C++ object
 
     def clear_state(self):
         self._check(self.hl.dll.lvh_fman_clear_state(self._p), "lvh_fman_clear_state")
@@ -1149,11 +993,12 @@ class FeatureManager:
         self._check(self.hl.dll.lvh_fman_slide_new(self._p, int(frame_count)), "lvh_fman_slide_new")
 
 
-class TrackerRig:
+class TrackerRig(_HostOwned):
     """FeatureTrackerRig of host/lvi_tbatch_host.hpp: FeatureTracker::readImage for S cameras over one batch tracker handle
     (include/lvi_tbatch.h), and the node's updateID loop (feature_tracker_node.cpp:136-166).  The reference compiles
     NUM_OF_CAM = 1: a capability of the library, not a restated behaviour.  ``batched=False`` is the yardstick: one
     FeatureTracker over one lvi_tracker per camera, called one after another.  HIP host library only."""
+    _ptr, _destroy, _last_error = "_r", "lvh_rig_destroy", "lvh_rig_last_error"
 
     def __init__(self, hostlib, tracker_params, slots, row, col, equalize=False, cams=None, device=0, batched=True):
         if not hostlib.has_rig:
@@ -1169,21 +1014,6 @@ class TrackerRig:
         if not self._r:
             raise A.LviError(-3, "lvh_rig_create", hostlib.dll.lvh_rig_last_error().decode(errors="replace"))
         self.cap = int(tracker_params.max_features)
-
-    def close(self):
-        if self._r:
-            self.hl.dll.lvh_rig_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, code, where):
-        if code < 0:
-            raise A.LviError(code, where, self.hl.dll.lvh_rig_last_error().decode(errors="replace"))
 
     def use_device_fundamental(self, device=0):
         """every camera's rejectWithF runs the device RANSAC (include/lvi_fmat.h) through a handle of its own"""

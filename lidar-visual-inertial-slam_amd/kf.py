@@ -47,9 +47,10 @@ def mei_params(cam):
     return A.MeiParams(*[float(cam[k]) for k in ("xi", "k1", "k2", "p1", "p2", "gamma1", "gamma2", "u0", "v0")])
 
 
-class KeyframeDescriber:
+class KeyframeDescriber(A.Owned):
     """The keyframe store of a pose graph on one GPU.  pattern = (x1, y1, x2, y2) of config.load_brief_pattern.  A slot
     holds one keyframe: FAST keypoints (pixel, normalised, descriptors) and window points (pixel, descriptors)."""
+    _destroy = "lvi_kf_destroy"
 
     def __init__(self, lib, pattern, device=0, max_width=1024, max_height=576, max_keypoints=8192, max_window=1024, max_keyframes=16):
         self.lib = bind(lib)
@@ -61,17 +62,6 @@ class KeyframeDescriber:
         self._h = C.c_void_p()
         lib.check(lib.dll.lvi_kf_create(int(device), self.max_width, self.max_height, self.max_keypoints, self.max_window, self.max_keyframes,
                                         *[p.ctypes.data_as(_P(_i32)) for p in pat], C.byref(self._h)), "lvi_kf_create")
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_kf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def describe(self, slot, img, window_xy=None, cam=None):
         """the KeyFrame constructor's image work into `slot`; img = a 2-D uint8 array (a view with a row stride is read in

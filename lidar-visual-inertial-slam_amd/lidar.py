@@ -22,24 +22,15 @@ def default_params(lib, **overrides):
     return p
 
 
-class LidarHotpath:
+class LidarHotpath(A.Owned):
+    _destroy = "lvi_lidar_destroy"
+
     def __init__(self, lib, params=None, device=0, **overrides):
         self.lib = lib
         self.params = params if params is not None else default_params(lib, **overrides)
         self._h = C.c_void_p()
         lib.check(lib.dll.lvi_lidar_create(C.byref(self.params), int(device), C.byref(self._h)), "lvi_lidar_create")
         self._cap_scan = int(self.params.N_SCAN) * int(self.params.Horizon_SCAN)
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_lidar_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- helpers ----------------------------------------------------------
     def _new_scan_info(self, cap=None):

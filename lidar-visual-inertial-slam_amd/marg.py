@@ -7,6 +7,8 @@ import ctypes as C
 
 import numpy as np
 
+from . import _abi as A
+
 _P = C.POINTER
 _vp, _i32, _f64 = C.c_void_p, C.c_int32, C.c_double
 
@@ -79,8 +81,9 @@ def _info(i):
     return {k: getattr(i, k) for k, _ in MargInfo._fields_}
 
 
-class Marginalizer:
+class Marginalizer(A.Owned):
     """one sliding window's MarginalizationInfo; the prior it computes stays on the device for the next call"""
+    _destroy = "lvi_marg_destroy"
     record_dtype = PROJECTION_DTYPE
 
     def __init__(self, lib, device=0, max_blocks=256, max_projections=2048, max_dense_factors=2, max_dense_rows=32, max_drop_dim=256, max_keep_dim=128,
@@ -95,17 +98,6 @@ class Marginalizer:
         lib.dll.lvi_marg_params_default(C.byref(self.params))
         if params:
             self.set_params(**params)
-
-    def close(self):
-        if self._h and self._own:
-            self.lib.dll.lvi_marg_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_params(self, **kw):
         """loss_type, max_sweeps, loss_a, sqrt_info, tr_over_row, half_row, eps"""

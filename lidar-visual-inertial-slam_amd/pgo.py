@@ -61,9 +61,10 @@ def _pose6(p):
     return (C.c_float * 6)(*[float(v) for v in np.asarray(p, np.float32).reshape(6)])
 
 
-class PoseGraph:
+class PoseGraph(A.Owned):
     """the keyframe pose graph: a prior on key 0, one odometry edge per later key, up to max_loops loop edges.  Poses
     are (roll, pitch, yaw, x, y, z)."""
+    _destroy = "lvi_pgo_destroy"
 
     def __init__(self, lib, device=0, max_poses=4096, max_loops=MAX_LOOPS, **params):
         self.lib = bind(lib)
@@ -74,17 +75,6 @@ class PoseGraph:
         lib.dll.lvi_pgo_params_default(C.byref(self.params))
         if params:
             self.set_params(**params)
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_pgo_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_params(self, **kw):
         """full_logmap (1 / 0), max_iters, conv_eps"""

@@ -46,9 +46,10 @@ def _info_dict(info):
                 t=np.array(info.t[:], np.float64), stream_us=info.stream_us)
 
 
-class PnPRansac:
+class PnPRansac(A.Owned):
     """the inlier status of cv::solvePnPRansac(pts3d, pts2d, I, [], ..., max_iters, threshold, confidence, inliers) on the
     GPU.  One handle serves calls of up to max_points correspondences."""
+    _destroy = "lvi_pnp_destroy"
 
     def __init__(self, lib, device=0, max_points=MAX_POINTS, max_iters=100):
         self.lib = bind(lib)
@@ -56,17 +57,6 @@ class PnPRansac:
         self.max_iters = int(max_iters)
         self._h = C.c_void_p()
         lib.check(lib.dll.lvi_pnp_create(int(device), self.max_points, self.max_iters, C.byref(self._h)), "lvi_pnp_create")
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_pnp_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def solve(self, pts3d, pts2d, threshold=REPROJECTION_ERROR, confidence=0.99, with_info=False):
         """pts3d [n, 3], pts2d [n, 2] (f32) -> status [n] uint8 (and the info dict)"""

@@ -47,24 +47,15 @@ def bind(lib):
     return lib.bind(TBATCH_SIGNATURES)
 
 
-class TrackerBatch:
+class TrackerBatch(A.Owned):
+    _ptr, _destroy = "_b", "lvi_tbatch_destroy"
+
     def __init__(self, lib, slots, params=None, device=0, **overrides):
         self.lib = bind(lib)
         self.slots = int(slots)
         self.params = params if params is not None else default_tracker_params(lib, **overrides)
         self._b = C.c_void_p()
         lib.check(lib.dll.lvi_tbatch_create(C.byref(self.params), self.slots, int(device), C.byref(self._b)), "lvi_tbatch_create")
-
-    def close(self):
-        if self._b:
-            self.lib.dll.lvi_tbatch_destroy(self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- per-slot tables ----------------------------------------------------
     def _per_slot(self, items):

@@ -23,23 +23,14 @@ def _img(a):
     return a
 
 
-class TrackerHotpath:
+class TrackerHotpath(A.Owned):
+    _ptr, _destroy = "_t", "lvi_tracker_destroy"
+
     def __init__(self, lib, params=None, device=0, **overrides):
         self.lib = lib
         self.params = params if params is not None else default_tracker_params(lib, **overrides)
         self._t = C.c_void_p()
         lib.check(lib.dll.lvi_tracker_create(C.byref(self.params), int(device), C.byref(self._t)), "lvi_tracker_create")
-
-    def close(self):
-        if self._t:
-            self.lib.dll.lvi_tracker_destroy(self._t)
-            self._t = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- one-call seams ---------------------------------------------------
     def lk_track(self, prev, nxt, prev_xy):

@@ -7,6 +7,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _abi as A
 from .marg import PROJECTION_DTYPE, MargProjection  # noqa: F401
 
 _P = C.POINTER
@@ -92,8 +93,9 @@ def _fields(s):
     return {k: (list(getattr(s, k)) if hasattr(getattr(s, k), "__len__") else getattr(s, k)) for k, _ in s._fields_}
 
 
-class WindowSolver:
+class WindowSolver(A.Owned):
     """one sliding window's optimisation problem; the blocks hold the solution after solve()"""
+    _destroy = "lvi_win_destroy"
     record_dtype = PROJECTION_DTYPE
     imu_dtype = IMU_DTYPE
 
@@ -107,17 +109,6 @@ class WindowSolver:
         lib.dll.lvi_win_params_default(C.byref(self.params))
         if params:
             self.set_params(**params)
-
-    def close(self):
-        if self._h:
-            self.lib.dll.lvi_win_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_params(self, **kw):
         """any field of lvi_win_params; G takes three values"""

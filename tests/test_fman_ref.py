@@ -2,6 +2,7 @@
 constructed scenes, csrc/lvi_fman_math.hpp compiled alone (plain and as a stand-alone program under the host sanitizers)
 against mpmath with the bar of the GPU tier, and the invariants of the reference's operations on random sequences."""
 import ctypes
+import importlib
 import os
 import re
 import subprocess
@@ -97,9 +98,12 @@ def test_host_libraries_link_with_and_without_the_feature_manager(pkg, oracle, t
     out = tmp_path / "liblvi_host_oracle.so"
     H.build_host_library(str(out), os.path.dirname(oracle.path), os.path.splitext(os.path.basename(oracle.path))[0][3:])
     assert not H.HostLibrary(str(out)).has_fman
-    assert H.FMAN_SOURCES == ("lvi_fman_capi.cpp",) and pkg.load_host().has_fman
-    b = open(os.path.join(pkg.PKG_DIR, "build.py")).read()
-    assert '"lvi_fman.hip"' in b and '"lvi_fman.h"' in b and "FMAN_SOURCES" in b
+    assert H.COMPONENTS["fman"].sources == ("lvi_fman_capi.cpp",) and pkg.load_host().has_fman
+    b = importlib.import_module(pkg.__name__ + ".build")
+    assert "lvi_fman.hip" in b.SOURCES and os.path.join(ROOT, "include", "lvi_fman.h") in b.hip_dependencies()
+    closure = H.component_sources(["fman"])
+    assert set(H.COMPONENTS["marg"].sources + H.COMPONENTS["win"].sources + H.COMPONENTS["fman"].sources) <= set(closure)
+    assert set(closure) <= set(H.component_sources())              # which is what build.build_host links
 
 
 # ---- the reference on constructed scenes -------------------------------------------------------------

@@ -44,7 +44,7 @@ def test_host_library_links_loop(pkg):
                  "lvh_loop_closed", "lvh_loop_cloud"):
         assert name in syms, name
     assert "lvh_loop_create" not in _exports(pkg.HIP_LIB_PATH)
-    assert "lvi_loop_capi.cpp" in pkg.host_api.LOOP_SOURCES
+    assert "lvi_loop_capi.cpp" in pkg.host_api.COMPONENTS["loop"].sources and "lvi_loop_capi.cpp" in pkg.host_api.component_sources()
 
 
 def test_oracle_does_not_export_loop(pkg, oracle):

@@ -98,7 +98,8 @@ def test_host_libraries_link_with_and_without_the_marginalizer(pkg, oracle, tmp_
     for name in ("lvh_marg_create", "lvh_marg_destroy", "lvh_marg_handle", "lvh_marg_set_window", "lvh_marg_set_features", "lvh_marg_set_imu", "lvh_marg_run",
                  "lvh_marg_last_error"):
         assert re.search(r"\b%s\b" % name, syms), name
-    assert H.HostLibrary(H.HOST_HIP_LIB).has_marg and H.MARG_SOURCES == ("lvi_marg_capi.cpp",)
+    assert H.HostLibrary(H.HOST_HIP_LIB).has_marg and H.COMPONENTS["marg"].sources == ("lvi_marg_capi.cpp",)
+    assert "lvi_marg_capi.cpp" in H.component_sources()
 
 
 def test_load_estimator_yaml(pkg, tmp_path):

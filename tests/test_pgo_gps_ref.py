@@ -4,6 +4,7 @@ and binding checks, the float64 reference tests/pgo_gps_ref.py against central d
 into stand-alone programs, plain and under the host sanitizers: the GPS error of csrc/lvi_pgo_math.hpp and the decision of
 host/lvi_gps_gate.hpp."""
 import ctypes
+import importlib
 import os
 import re
 import subprocess
@@ -42,8 +43,9 @@ def test_header_and_gps_binding_agree(pkg):
         body = open(os.path.join(ROOT, rel)).read()
         assert "not restated" not in body and "GPS factors are out of scope" not in body, rel
         assert "lvi_pgo_gps.h" in body or "lvi_gps_gate.hpp" in body, rel
-    build = open(os.path.join(ROOT, "lidar-visual-inertial-slam_amd", "build.py")).read()
-    assert "lvi_pgo_gps.h" in build
+    # both libraries are rebuilt when the header changes
+    build = importlib.import_module(pkg.__name__ + ".build")
+    assert HEADER in build.hip_dependencies() and HEADER in pkg.host_api.host_dependencies(pkg.host_api.component_sources(["pgo"]))
 
 
 def test_hip_library_exports_the_gps_abi_and_the_oracle_does_not(pkg, oracle):

@@ -380,4 +380,5 @@ def test_host_libraries_link_with_and_without_the_window_solve(pkg, oracle, tmp_
     for name in ("lvh_win_create", "lvh_win_destroy", "lvh_win_handle", "lvh_win_set_imu", "lvh_win_set_lidar_flags", "lvh_win_optimize", "lvh_win_get_window",
                  "lvh_win_last_error"):
         assert re.search(r"\b%s\b" % name, syms), name
-    assert H.HostLibrary(H.HOST_HIP_LIB).has_win and H.WIN_SOURCES == ("lvi_win_capi.cpp",) and H.MARG_SOURCES == ("lvi_marg_capi.cpp",)
+    assert H.HostLibrary(H.HOST_HIP_LIB).has_win and H.COMPONENTS["win"].sources == ("lvi_win_capi.cpp",)
+    assert H.COMPONENTS["marg"].sources == ("lvi_marg_capi.cpp",) and H.component_sources(["win"]) == ("lvi_marg_capi.cpp", "lvi_win_capi.cpp")
