@@ -8,7 +8,7 @@ import it through ``__graft_entry__.import_package()`` (module name
 """
 import os
 
-from . import _abi, bow, config, depth, fman, fmat, fmatb, gmap, host_api, kf, loop, marg, pgo, pnp, preint, relpose, replay, synth, tbatch, win  # noqa: F401
+from . import _abi, align, bow, config, depth, fman, fmat, fmatb, gmap, host_api, kf, loop, marg, pgo, pnp, preint, relpose, replay, synth, tbatch, win  # noqa: F401
 from ._abi import Library, LviError, PT_DTYPE, LIVOX_DTYPE  # noqa: F401
 from .lidar import LidarHotpath, default_params  # noqa: F401
 from .tracker import TrackerHotpath, default_tracker_params  # noqa: F401
@@ -27,6 +27,7 @@ from .win import WindowSolver  # noqa: F401
 from .fman import FeatureTable  # noqa: F401
 from .preint import ImuWindow  # noqa: F401
 from .relpose import RelativePose  # noqa: F401
+from .align import ImuAligner  # noqa: F401
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(PKG_DIR)

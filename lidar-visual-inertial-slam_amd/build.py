@@ -6,7 +6,7 @@ from shutil import which
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 OUT = os.path.join(CSRC, "liblvi_hip.so")
-SOURCES = ["lvi_sort.hip", "lvi_voxel.hip", "lvi_scan.hip", "lvi_icp.hip", "lvi_capi.hip", "lvi_tracker.hip", "lvi_depth.hip", "lvi_fmat.hip", "lvi_gmap.hip", "lvi_loop.hip", "lvi_kf.hip", "lvi_bow.hip", "lvi_pnp.hip", "lvi_pgo.hip", "lvi_winsys.hip", "lvi_marg.hip", "lvi_win.hip", "lvi_fman.hip", "lvi_preint.hip", "lvi_relpose.hip"]
+SOURCES = ["lvi_sort.hip", "lvi_voxel.hip", "lvi_scan.hip", "lvi_icp.hip", "lvi_capi.hip", "lvi_tracker.hip", "lvi_depth.hip", "lvi_fmat.hip", "lvi_gmap.hip", "lvi_loop.hip", "lvi_kf.hip", "lvi_bow.hip", "lvi_pnp.hip", "lvi_pgo.hip", "lvi_winsys.hip", "lvi_marg.hip", "lvi_win.hip", "lvi_fman.hip", "lvi_preint.hip", "lvi_relpose.hip", "lvi_align.hip"]
 # -ffp-contract=off: voxel keys, KNN distances and the other bit-exact paths must never be fused into FMA
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
