@@ -101,7 +101,7 @@ struct LidarDev {
     int *sector_idx = nullptr, *sector_cnt = nullptr;      // [N_SCAN*6*40], [N_SCAN*6]
     lvi_pt* corner = nullptr; int* corner_idx = nullptr; int* d_ncorner = nullptr;
     lvi_pt* surf = nullptr;                                // concatenated per-ring DS output
-    int* d_fresh = nullptr;                                // 1 until the first extract of this handle
+    int* d_fresh = nullptr;                                // 1 until a scan marks picked[0] (the reference never clears it)
     int* d_status = nullptr;
     long long* d_feat_cycles = nullptr;                    // [8] phase cycle counters of ring 0 (diagnostics)
     long long* d_icp_cycles = nullptr;                     // [16] phase cycle counters: [0..7] residual workgroup 0, [8..15] solve kernel

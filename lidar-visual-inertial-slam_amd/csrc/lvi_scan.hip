@@ -464,9 +464,10 @@ __global__ __launch_bounds__(FEAT_THREADS) void feat_sector_kernel(Batch<FeatArg
         }
         __syncthreads();
         LVI_STAMP(0);
-        // slot 4 of the whole cloud is the never-rewritten cloudSmoothness entry {0, ind 0}: it is not a
-        // candidate in either walk; k = 4 can only be sp of ring 0, sector 0.
-        const int jlo = (sp == 4 && ring == 0 && sec == 0) ? 6 : 5;      // first candidate local index
+        // slot 4 of the whole cloud is the never-rewritten cloudSmoothness entry {0, ind 0}: point 4 is not a
+        // candidate in either walk; k = 4 can only be sp of sector 0 of the first populated ring
+        // (an empty ring 0 hands its start index 4 on to the next one).
+        const int jlo = (sp == 4 && sec == 0) ? 6 : 5;                   // first candidate local index
         const int jhi = 5 + (ep - sp);                                    // local index of ep
         // ---- static part of the surf walk (needs curvature and reach only, so it runs before the hand-over wait):
         // thread t owns the 16 CONTIGUOUS points [16t, 16t+16); for each of them the set of reachable neighbours that
@@ -631,13 +632,17 @@ __global__ __launch_bounds__(FEAT_THREADS) void feat_sector_kernel(Batch<FeatArg
         }
         __syncthreads();
         LVI_STAMP(3);
-        // ---- first scan of a fresh node: the stale entry {0, ind 0} is the first element of the ascending
-        // walk of ring 0 / sector 0; it labels ind 0 and marks picked[1..5] (only 5 is a candidate).
-        if (jlo == 6 && fresh && tid == 0) {
-            bool ok = true;
-            for (int k = 1; k <= 5; k++) ok = ok && (abs(a.col[k] - a.col[k - 1]) <= 10);
-            if (ok && a.surfThreshold > 0.f) s_pick[6] = 1;             // local index of k = 5
-            if (a.surfThreshold > 0.f && n > 0) { a.label[0] = -1; a.picked[0] = 1; }      // ind 0 itself (outside every sector: no effect on the outputs)
+        // ---- a node whose picked[0] is still 0 ("fresh"): the stale entry {0, ind 0} is the first element of the ascending
+        // walk of the sector that starts at slot 4; it labels ind 0 and marks picked[0..5] up to a column jump (only 5 is a
+        // candidate).  Not if the corner walk has just marked picked[0] (point 5 taken, five free steps backwards).
+        // Local index of k is k + 1 here (k0 = -1).
+        if (jlo == 6 && fresh && tid == 0 && a.surfThreshold > 0.f && s_pick[1] == 0) {
+            a.label[0] = -1;                                            // ind 0 itself lies outside every sector's label write-back
+            s_pick[1] = 1;
+            for (int k = 1; k <= 5 && k < n; k++) {
+                if (abs(a.col[k] - a.col[k - 1]) > 10) break;
+                s_pick[k + 1] = 1;
+            }
         }
         __syncthreads();
         // ---- surf walk as a fixed point (ascending curvature, position ep last; a point is labelled iff no
@@ -781,7 +786,7 @@ __global__ __launch_bounds__(FEAT_THREADS) void feat_sector_big_kernel(Batch<Fea
         int* out_idx = a.sector_idx + (ring * 6 + sec) * CORNERS_PER_SECTOR;
         if (sp >= ep) { if (tid == 0) a.sector_cnt[ring * 6 + sec] = 0; continue; }
         // slot 4 of the whole cloud: the never-rewritten cloudSmoothness entry, not a candidate
-        const int klo = (sp == 4 && ring == 0 && sec == 0) ? 5 : sp;
+        const int klo = (sp == 4 && sec == 0) ? 5 : sp;
         // ---- corners
         int taken = 0;
         for (int round = 0; round < CORNERS_PER_SECTOR + 1; round++) {
@@ -816,12 +821,10 @@ __global__ __launch_bounds__(FEAT_THREADS) void feat_sector_big_kernel(Batch<Fea
             if (taken >= CORNERS_PER_SECTOR) break;
         }
         if (tid == 0) a.sector_cnt[ring * 6 + sec] = taken;
-        // ---- first scan of a fresh node (see the LDS kernel)
-        if (klo == 5 && fresh && tid == 0) {
-            bool ok = true;
-            for (int k = 1; k <= 5; k++) ok = ok && (abs(a.col[k] - a.col[k - 1]) <= 10);
-            if (ok && a.surfThreshold > 0.f) picked[5] = 1;
-            if (a.surfThreshold > 0.f && n > 0) { label[0] = -1; picked[0] = 1; }
+        // ---- a node whose picked[0] is still 0: the stale entry (see the LDS kernel)
+        if (klo == 5 && fresh && tid == 0 && a.surfThreshold > 0.f && picked[0] == 0) {
+            label[0] = -1; picked[0] = 1;
+            for (int k = 1; k <= 5 && !brk(k); k++) picked[k] = 1;
         }
         __threadfence_block();
         __syncthreads();
@@ -891,7 +894,6 @@ __global__ void feat_finalize_kernel(Batch<FeatArgs> B_)
         off[ns] = o;
         *a.d_ncorner = o;
         for (int r = 0; r < a.N_SCAN; r++) { a.ringDyn[r].in_off = a.ringBase[r]; a.ringDyn[r].n = a.ringBase[r + 1] - a.ringBase[r]; }
-        if (*a.d_n > 16) *a.d_fresh = 0;              // the "fresh node" case ends with the first real scan
     }
     __syncthreads();
     // pipelined sector kernel: marks a sector made on the last five points of its predecessor
@@ -905,6 +907,11 @@ __global__ void feat_finalize_kernel(Batch<FeatArgs> B_)
         const int k = sp - 5 + i;
         if (k >= 0 && k < *a.d_n) a.picked[k] = 1;
     }
+    __syncthreads();
+    // The reference never rewrites picked[0]; it is set by the stale entry's own visit or by the backward marks of point 5, and
+    // from then on the stale entry is skipped.  picked[0] here is rewritten per scan, so the node's state lives in d_fresh: the
+    // "fresh node" case ends with the first scan that marks picked[0], not with the first scan of any size.
+    if (threadIdx.x == 0 && *a.d_n > 0 && a.picked[0]) *a.d_fresh = 0;
     for (int t = threadIdx.x; t < ns * CORNERS_PER_SECTOR; t += blockDim.x) {
         const int s = t / CORNERS_PER_SECTOR, q = t % CORNERS_PER_SECTOR;
         if (q < scnt[s]) {
