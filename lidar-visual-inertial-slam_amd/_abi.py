@@ -256,5 +256,16 @@ def pts_xyzi(a):
     return np.ascontiguousarray(a).view(np.float32).reshape(-1, 4)
 
 
+def _d(a):
+    return a.ctypes.data_as(_P(_f64))
+
+
+def _arr(a, shape):
+    a = np.ascontiguousarray(a, np.float64)
+    if a.shape != shape:
+        raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
+    return a
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
+from ._abi import _arr, _d
 
 _P = C.POINTER
 _vp, _i32, _f64 = C.c_void_p, C.c_int32, C.c_double
@@ -62,17 +63,6 @@ ALIGN_SIGNATURES = {
 def bind(lib):
     """set the alignment signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
     return lib.bind(ALIGN_SIGNATURES)
-
-
-def _d(a):
-    return a.ctypes.data_as(_P(_f64))
-
-
-def _arr(a, shape):
-    a = np.ascontiguousarray(a, np.float64)
-    if a.shape != shape:
-        raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
-    return a
 
 
 class ImuAligner(A.Owned):

@@ -2,11 +2,10 @@
 // DESIGN §31).
 //
 // Four kernels, plain HIP C++ with vector stores only.
-//   align_repropagate  one workgroup of 256 threads per job, the shape of preint_run without the covariance: thread
-//                      r * 15 + c owns element (r, c) of the jacobian, lanes 225..233 build F of the next step, lane 255 runs
-//                      the vector chain a chunk of LVI_PREINT_CHUNK samples ahead.  A push and a fresh pending
-//                      preintegration are one job that travels as the kernel argument; the repropagation of a solve is one
-//                      job per frame, read from the solve's upload, with the bias the gyro kernel left on the device.
+//   align_repropagate  the integration body of lvi_preint_dev.hpp, which describes it, in its form without the covariance,
+//                      one workgroup of 256 threads per job.  A push and a fresh pending preintegration are one job that
+//                      travels as the kernel argument; the repropagation of a solve is one job per frame, read from the
+//                      solve's upload, with the bias the gyro kernel left on the device.
 //   align_gyro         one lane per pair computes the pair's nine plus three products, twelve lanes sum them in pair order,
 //                      one lane solves the 3 x 3 system and advances Bgs.
 //   align_system       one lane per pair builds r_A and r_b; after a barrier one thread per entry of the compact system
@@ -26,11 +25,10 @@
 
 #include "../../include/lvi_align.h"
 #include "lvi_align_math.hpp"
-#include "lvi_dev.hpp"
+#include "lvi_preint_dev.hpp"
 
-using namespace lvi;
+using namespace lvi_preint_dev;
 namespace am = lvi_align_math;
-namespace pm = lvi_preint_math;
 
 static_assert(LVI_ALIGN_OK == am::OK && LVI_ALIGN_GRAVITY_NORM == am::GRAVITY_NORM && LVI_ALIGN_NEGATIVE_SCALE == am::NEGATIVE_SCALE &&
               LVI_ALIGN_NEGATIVE_SCALE_REFINED == am::NEGATIVE_SCALE_REFINED && LVI_ALIGN_SINGULAR == am::SINGULAR && LVI_ALIGN_TOO_FEW == am::TOO_FEW &&
@@ -40,19 +38,10 @@ static_assert(sizeof(lvi_align_frame) == 8 * 13 + 16 + 8 * (1 + 3 + 4 + 3 + 3 + 
 
 namespace {
 
-constexpr int TB = 256, CHUNK = LVI_PREINT_CHUNK, SD = 7, NN = pm::N * pm::N;
 constexpr int MAXF = LVI_ALIGN_MAX_FRAMES, MAXND = 3 * MAXF, MAXN = MAXND + am::NB_LINEAR;
 constexpr int PAIR_DOUBLES = 110;                             // r_A (at most 10 x 10) and r_b
 constexpr int SYS_STRIDE = am::BW * MAXND + (am::NB_LINEAR + 2) * MAXN;
 
-enum { J_CREATE = 1, J_REPROP = 2, J_INTEGRATE = 4, J_LIST = 8 };
-
-// a frame's IntegrationBase without its buffers and without its covariance
-struct FrameState {
-    pm::State s;
-    double linearized_acc[3], linearized_gyr[3];
-    double jacobian[NN];
-};
 // one frame of the list as a solve uploads it
 struct FrameIn {
     double R[9], T[3];
@@ -67,64 +56,14 @@ struct Work {
     int32_t reason, n_state, built, reserved;
     double delta_bg[3], s, g_linear[3], g[3], min_pivot[6], Bgs[33], g0[3];
 };
-struct Job {
-    int32_t phys, first, count, flags;
-    double ba[3], bg[3], acc_0[3], gyr_0[3];                  // J_CREATE
-};
 
 __global__ __launch_bounds__(TB) void align_repropagate(Job jb, const FrameIn* __restrict__ fin, const Work* __restrict__ wk, FrameState* __restrict__ states,
                                                         double* __restrict__ smp, int max_samples)
 {
-    __shared__ double sJ[NN], sF[2][NN], sV[2][pm::N * pm::NV];
-    __shared__ double sS[CHUNK * SD];
+    __shared__ double sJ[NN], sF[2][NN], sS[CHUNK * SD];
     __shared__ pm::StepGeom sG[CHUNK];
-    if (jb.flags & J_LIST) {                                  // :31-35: frame blockIdx.x + 1 of the list with Ba = 0 and the new Bgs[0]
-        const FrameIn& f = fin[blockIdx.x + 1];
-        jb.phys = f.phys; jb.first = 0; jb.count = f.count;
-        jb.flags = J_REPROP | (f.count > 0 ? J_INTEGRATE : 0);
-        for (int k = 0; k < 3; k++) { jb.ba[k] = 0.; jb.bg[k] = wk->Bgs[k]; }
-    }
-    const int tid = threadIdx.x, flags = jb.flags;
-    const bool mat = tid < NN, builder = tid >= NN && tid < NN + 9, chain = tid == TB - 1;
-    const int r = tid / pm::N, c = tid % pm::N, bi = (tid - NN) / 3, bj = (tid - NN) % 3;
-    FrameState* st = states + jb.phys;
-    if (mat) sJ[tid] = (flags & (J_CREATE | J_REPROP)) ? (r == c ? 1. : 0.) : st->jacobian[tid];
-    pm::State s;
-    if (chain) {
-        if (flags & J_CREATE) pm::state_reset(s, jb.acc_0, jb.gyr_0, jb.ba, jb.bg);
-        else if (flags & J_REPROP) pm::state_reset(s, st->linearized_acc, st->linearized_gyr, jb.ba, jb.bg);
-        else s = st->s;
-    }
-    __syncthreads();
-    if (flags & J_INTEGRATE) {
-        const double* src = smp + ((size_t)jb.phys * max_samples + jb.first) * SD;
-        int par = 0;
-        for (int base = 0; base < jb.count; base += CHUNK) {
-            const int m = min(CHUNK, jb.count - base);
-            for (int t = tid; t < m * SD; t += TB) sS[t] = src[(size_t)base * SD + t];
-            __syncthreads();
-            if (chain)
-                for (int k = 0; k < m; k++) pm::step_state(s, sS[SD * k], sS + SD * k + 1, sS + SD * k + 4, sG[k]);
-            __syncthreads();
-            if (builder) pm::build_entry(sG[0], bi, bj, sF[par], sV[par]);
-            __syncthreads();
-            for (int k = 0; k < m; k++) {
-                double jn = 0.;
-                if (mat) jn = pm::f_dot(sF[par], r, sJ, c);
-                if (builder && k + 1 < m) pm::build_entry(sG[k + 1], bi, bj, sF[par ^ 1], sV[par ^ 1]);
-                __syncthreads();                               // every product has read the jacobian
-                if (mat) sJ[tid] = jn;
-                __syncthreads();                               // the step's jacobian is whole; F of this parity is free
-                par ^= 1;
-            }
-        }
-    }
-    if (mat) st->jacobian[tid] = sJ[tid];
-    if (chain) {
-        st->s = s;
-        if (flags & J_CREATE)
-            for (int k = 0; k < 3; k++) { st->linearized_acc[k] = jb.acc_0[k]; st->linearized_gyr[k] = jb.gyr_0[k]; }
-    }
+    if (jb.flags & J_LIST) list_job(jb, fin[blockIdx.x + 1], wk->Bgs);   // :31-35: frame blockIdx.x + 1 of the list with Ba = 0 and the new Bgs[0]
+    integrate_job<false>({sJ, sF, sS, sG}, jb, states, smp, max_samples, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(TB) void align_gyro(const SolveHead* __restrict__ head, const FrameIn* __restrict__ fin, const FrameState* __restrict__ states,
@@ -168,9 +107,7 @@ __global__ __launch_bounds__(TB) void align_system(int which, const SolveHead* _
     if (tid < F - 1) {
         const pm::State& sj = states[fin[tid + 1].phys].s;
         am::Pre pre;
-        pre.sum_dt = sj.sum_dt;
-        for (int k = 0; k < 3; k++) { pre.delta_p[k] = sj.delta_p[k]; pre.delta_v[k] = sj.delta_v[k]; }
-        for (int k = 0; k < 4; k++) pre.delta_q[k] = sj.delta_q[k];
+        copy_pre(sj, pre);
         double rA[100], rb[10];
         am::pair_system(fin[tid].R, fin[tid].T, fin[tid + 1].R, fin[tid + 1].T, pre, head->TIC, which >= 1 ? lxly : nullptr, g0, rA, rb);
         double* o = pairs + (size_t)PAIR_DOUBLES * tid;
@@ -276,13 +213,6 @@ __global__ __launch_bounds__(LVI_WAVE) void align_factor_solve(int which, const 
         for (int e = tid; e < MAXN; e += LVI_WAVE) x_out[e] = e < n ? sX[e] : 0.;
 }
 
-bool finite_n(const double* v, size_t n)
-{
-    for (size_t k = 0; k < n; k++)
-        if (!std::isfinite(v[k])) return false;
-    return true;
-}
-
 struct HostFrame {
     double stamp, R[9], T[3];
     int phys, count;
@@ -292,14 +222,13 @@ struct HostFrame {
 }  // namespace
 
 struct lvi_align : Handle {
-    int max_frames = 0, max_samples = 0;
+    int max_frames = 0;
     lvi_align_params P{};
-    FrameState* d_states = nullptr; double* d_smp = nullptr;     // max_frames + 1 slots
+    SampleStore smp;                                             // max_frames + 1 slots, as d_states
+    FrameState* d_states = nullptr;
     char* d_in = nullptr; char* d_work = nullptr;                // SolveHead | FrameIn [max_frames];  Work | x [MAXN]
     double *d_pairs = nullptr, *d_sys = nullptr;
-    double* h_up = nullptr; char* h_in = nullptr; char* h_down = nullptr;      // pinned
-    size_t down_bytes = 0;
-    hipEvent_t up_done = nullptr; bool up_pending = false;       // the upload that last read h_up
+    char* h_in = nullptr; char* h_down = nullptr;                // pinned
     // the host's mirror
     std::vector<HostFrame> list;
     std::vector<int> free_slots;
@@ -313,18 +242,17 @@ namespace {
 
 template <class A, class B> void carve(A& a, B& pin, lvi_align* h)
 {
-    const size_t ms = (size_t)h->max_samples, slots = (size_t)h->max_frames + 1;
+    const size_t slots = (size_t)h->max_frames + 1;
     const size_t in_bytes = sizeof(SolveHead) + sizeof(FrameIn) * (size_t)h->max_frames;
-    h->down_bytes = std::max({sizeof(FrameState) * slots, sizeof(double) * SD * ms, sizeof(double) * (size_t)SYS_STRIDE, sizeof(Work) + sizeof(double) * MAXN});
+    h->smp.carve(a, pin, slots);
     h->d_states = a.template alloc<FrameState>(slots);
-    h->d_smp = a.template alloc<double>(slots * ms * SD);
     h->d_in = a.template alloc<char>(in_bytes);
     h->d_work = a.template alloc<char>(sizeof(Work) + sizeof(double) * MAXN);
     h->d_pairs = a.template alloc<double>((size_t)PAIR_DOUBLES * (MAXF - 1));
     h->d_sys = a.template alloc<double>((size_t)SYS_STRIDE * am::SYSTEMS);
-    h->h_up = pin.template alloc<double>(ms * SD);
     h->h_in = pin.template alloc<char>(in_bytes);
-    h->h_down = pin.template alloc<char>(h->down_bytes);
+    h->h_down = pin.template alloc<char>(std::max({sizeof(FrameState) * slots, h->smp.bytes(h->smp.max_samples), sizeof(double) * (size_t)SYS_STRIDE,
+                                                   sizeof(Work) + sizeof(double) * MAXN}));
 }
 
 void forget(lvi_align* h)
@@ -338,14 +266,8 @@ void forget(lvi_align* h)
 
 void launch_job(lvi_align* h, const Job& j)
 {
-    hipLaunchKernelGGL(align_repropagate, dim3(1), dim3(TB), 0, h->stream, j, (const FrameIn*)nullptr, (const Work*)nullptr, h->d_states, h->d_smp, h->max_samples);
+    hipLaunchKernelGGL(align_repropagate, dim3(1), dim3(TB), 0, h->stream, j, (const FrameIn*)nullptr, (const Work*)nullptr, h->d_states, h->smp.d_smp, h->smp.max_samples);
     LVI_HIP(hipGetLastError());
-}
-
-void download(lvi_align* h, const void* d, size_t bytes)
-{
-    LVI_HIP(hipMemcpyAsync(h->h_down, d, bytes, hipMemcpyDeviceToHost, h->stream));
-    LVI_HIP(hipStreamSynchronize(h->stream));
 }
 
 int find_stamp(const lvi_align* h, double stamp)
@@ -364,8 +286,7 @@ int32_t lvi_align_abi_version(void) { return LVI_ALIGN_ABI_VERSION; }
 void lvi_align_params_default(lvi_align_params* p)
 {
     if (!p) return;
-    p->acc_n = 0.08; p->gyr_n = 0.004; p->acc_w = 0.00004; p->gyr_w = 2.0e-6;
-    p->G[0] = 0.; p->G[1] = 0.; p->G[2] = 9.8;
+    noise_defaults(p);
     p->TIC[0] = p->TIC[1] = p->TIC[2] = 0.;
 }
 
@@ -377,32 +298,22 @@ int32_t lvi_align_create(int32_t device, const lvi_align_caps* caps, lvi_align**
     if (caps->max_frames < 2 || caps->max_frames > LVI_ALIGN_MAX_FRAMES) return fail(LVI_ERR_INVALID_ARG, "max_frames is outside 2..LVI_ALIGN_MAX_FRAMES");
     if (caps->max_samples < 1 || caps->max_samples > LVI_PREINT_MAX_SAMPLES) return fail(LVI_ERR_INVALID_ARG, "max_samples is outside 1..LVI_PREINT_MAX_SAMPLES");
     return create_handle(device, out, lvi_align_destroy,
-        [&](lvi_align* h) { h->max_frames = caps->max_frames; h->max_samples = caps->max_samples; lvi_align_params_default(&h->P); forget(h); },
+        [&](lvi_align* h) { h->max_frames = caps->max_frames; h->smp.max_samples = caps->max_samples; lvi_align_params_default(&h->P); forget(h); },
         [&](lvi_align* h) -> int32_t {
             h->open(device, [&](auto& dev, auto& pin) { carve(dev, pin, h); });
-            LVI_HIP(hipEventCreateWithFlags(&h->up_done, hipEventDisableTiming));
+            h->smp.open();
             LVI_HIP(hipMemsetAsync(h->d_states, 0, sizeof(FrameState) * ((size_t)h->max_frames + 1), h->stream));
             LVI_HIP(hipStreamSynchronize(h->stream));
             return LVI_OK;
         });
 }
 
-void lvi_align_destroy(lvi_align* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->up_done) (void)hipEventDestroy(h->up_done);
-    h->close();
-    delete h;
-}
+void lvi_align_destroy(lvi_align* h) { destroy_with_store(h); }
 
 int32_t lvi_align_set_params(lvi_align* h, const lvi_align_params* p)
 {
     if (!h || !p) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    const double v[10] = {p->acc_n, p->gyr_n, p->acc_w, p->gyr_w, p->G[0], p->G[1], p->G[2], p->TIC[0], p->TIC[1], p->TIC[2]};
-    if (!finite_n(v, 10) || p->acc_n < 0 || p->gyr_n < 0 || p->acc_w < 0 || p->gyr_w < 0)
-        return fail(LVI_ERR_INVALID_ARG, "the parameters must be finite and the noise values >= 0");
+    if (!noise_valid(p) || !finite_n(p->TIC, 3)) return fail(LVI_ERR_INVALID_ARG, "the parameters must be finite and the noise values >= 0");
     h->P = *p;
     return LVI_OK;
 }
@@ -422,21 +333,12 @@ int32_t lvi_align_push_imu(lvi_align* h, int32_t n, const double* dt, const doub
     if (n > 0 && (!finite_n(dt, (size_t)n) || !finite_n(acc, 3 * (size_t)n) || !finite_n(gyr, 3 * (size_t)n)))
         return fail(LVI_ERR_INVALID_ARG, "a sample is not finite");
     if (n == 0) return LVI_OK;
-    if (h->pending >= 0 && h->pending_count + (int64_t)n > h->max_samples) return fail(LVI_ERR_CAPACITY, "the pending preintegration would exceed max_samples");
+    if (h->pending >= 0 && h->pending_count + (int64_t)n > h->smp.max_samples) return fail(LVI_ERR_CAPACITY, "the pending preintegration would exceed max_samples");
     const int32_t st = h->pending < 0 ? LVI_OK : guarded(h->device, [&]() -> int32_t {
         const int at = h->pending_count;
-        if (h->up_pending) LVI_HIP(hipEventSynchronize(h->up_done));           // the staging buffer is free again
-        for (int k = 0; k < n; k++) {
-            double* o = h->h_up + (size_t)SD * k;
-            o[0] = dt[k];
-            for (int a = 0; a < 3; a++) { o[1 + a] = acc[3 * (size_t)k + a]; o[4 + a] = gyr[3 * (size_t)k + a]; }
-        }
-        LVI_HIP(hipMemcpyAsync(h->d_smp + ((size_t)h->pending * h->max_samples + at) * SD, h->h_up, sizeof(double) * SD * (size_t)n, hipMemcpyHostToDevice,
-                               h->stream));
-        LVI_HIP(hipEventRecord(h->up_done, h->stream));
-        h->up_pending = true;
+        h->smp.stage(h->stream, h->pending, at, n, dt, acc, gyr);
         Job j{};
-        j.phys = h->pending; j.first = at; j.count = n; j.flags = J_INTEGRATE;
+        j.phys = j.src = h->pending; j.src_first = j.dst_first = at; j.count = n; j.flags = J_INTEGRATE;
         launch_job(h, j);
         h->pending_count = at + n;
         return LVI_OK;
@@ -457,7 +359,7 @@ int32_t lvi_align_add_frame(lvi_align* h, double stamp, const double* Ba, const 
     return guarded(h->device, [&]() -> int32_t {
         const int fresh = h->free_slots.back();                // max_frames + 1 slots for max_frames frames and the pending one
         Job j{};
-        j.phys = fresh; j.flags = J_CREATE;
+        j.phys = j.src = fresh; j.flags = J_CREATE;
         for (int k = 0; k < 3; k++) { j.ba[k] = Ba[k]; j.bg[k] = Bg[k]; j.acc_0[k] = h->acc_0[k]; j.gyr_0[k] = h->gyr_0[k]; }
         launch_job(h, j);
         h->free_slots.pop_back();
@@ -509,13 +411,7 @@ int32_t lvi_align_excitation(lvi_align* h, double* var)
         download(h, h->d_states, sizeof(FrameState) * ((size_t)h->max_frames + 1));
         const FrameState* st = reinterpret_cast<const FrameState*>(h->h_down);
         std::vector<am::Pre> pre((size_t)F - 1);
-        for (int i = 1; i < F; i++) {
-            const pm::State& s = st[h->list[i].phys].s;
-            am::Pre& p = pre[(size_t)i - 1];
-            p.sum_dt = s.sum_dt;
-            for (int k = 0; k < 3; k++) { p.delta_p[k] = s.delta_p[k]; p.delta_v[k] = s.delta_v[k]; }
-            for (int k = 0; k < 4; k++) p.delta_q[k] = s.delta_q[k];
-        }
+        for (int i = 1; i < F; i++) copy_pre(st[h->list[i].phys].s, pre[(size_t)i - 1]);
         *var = am::excitation(pre.data(), F - 1);
         return LVI_OK;
     });
@@ -557,7 +453,7 @@ int32_t lvi_align_solve(lvi_align* h, double* Bgs_inout, double* g_out, double* 
         LVI_HIP(hipGetLastError());
         Job j{};
         j.flags = J_LIST;
-        hipLaunchKernelGGL(align_repropagate, dim3(F - 1), dim3(TB), 0, h->stream, j, d_fi, (const Work*)d_wk, h->d_states, h->d_smp, h->max_samples);
+        hipLaunchKernelGGL(align_repropagate, dim3(F - 1), dim3(TB), 0, h->stream, j, d_fi, (const Work*)d_wk, h->d_states, h->smp.d_smp, h->smp.max_samples);
         LVI_HIP(hipGetLastError());
         for (int w = 0; w < am::SYSTEMS; w++) {
             hipLaunchKernelGGL(align_system, dim3(1), dim3(TB), 0, h->stream, w, d_hd, d_fi, h->d_states, (const Work*)d_wk, h->d_pairs, h->d_sys);
@@ -596,24 +492,10 @@ int32_t lvi_align_get_frame(lvi_align* h, int32_t index, lvi_align_frame* out, i
     const int32_t st = !f.has_pre ? LVI_OK : guarded(h->device, [&]() -> int32_t {
         download(h, h->d_states + f.phys, sizeof(FrameState));
         const FrameState& s = *reinterpret_cast<const FrameState*>(h->h_down);
-        o.sum_dt = s.s.sum_dt;
-        for (int k = 0; k < 3; k++) {
-            o.delta_p[k] = s.s.delta_p[k]; o.delta_v[k] = s.s.delta_v[k]; o.linearized_ba[k] = s.s.linearized_ba[k]; o.linearized_bg[k] = s.s.linearized_bg[k];
-            o.linearized_acc[k] = s.linearized_acc[k]; o.linearized_gyr[k] = s.linearized_gyr[k];
-        }
-        for (int k = 0; k < 4; k++) o.delta_q[k] = s.s.delta_q[k];
+        copy_pre(s.s, o);
+        for (int k = 0; k < 3; k++) { o.linearized_acc[k] = s.linearized_acc[k]; o.linearized_gyr[k] = s.linearized_gyr[k]; }
         std::memcpy(o.jacobian, s.jacobian, sizeof(o.jacobian));
-        if ((dt || acc || gyr) && n > 0) {
-            download(h, h->d_smp + (size_t)f.phys * h->max_samples * SD, sizeof(double) * SD * (size_t)n);
-            const double* v = reinterpret_cast<const double*>(h->h_down);
-            for (int k = 0; k < n; k++) {
-                if (dt) dt[k] = v[SD * k];
-                for (int a = 0; a < 3; a++) {
-                    if (acc) acc[3 * k + a] = v[SD * k + 1 + a];
-                    if (gyr) gyr[3 * k + a] = v[SD * k + 4 + a];
-                }
-            }
-        }
+        if ((dt || acc || gyr) && n > 0) h->smp.fetch(h, f.phys, n, dt, acc, gyr);
         return LVI_OK;
     });
     if (st == LVI_OK) *out = o;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -133,6 +134,13 @@ struct ArenaSizer {
 
 // a device array and its pinned mirror, carved together: the size is written once
 template <class T, class A, class B> void alloc_pair(A& dev, B& pin, T*& d, T*& h, size_t n) { d = dev.template alloc<T>(n); h = pin.template alloc<T>(n); }
+
+inline bool finite_n(const double* v, size_t n)
+{
+    for (size_t k = 0; k < n; k++)
+        if (!std::isfinite(v[k])) return false;
+    return true;
+}
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }   // byte offsets of the parts of one buffer

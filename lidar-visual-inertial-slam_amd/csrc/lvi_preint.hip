@@ -1,15 +1,9 @@
 // lvi_preint.hip — the IMU preintegration of vins_estimator's sliding window on the device (include/lvi_preint.h).
 //
-// One kernel.  A launch runs a list of at most LVI_PREINT_SLOTS jobs, one workgroup of 256 threads per job; a job names a
-// slot, a run of samples, and whether the slot is created, repropagated with new biases or continued.  Threads 0..224 own
-// one element of jacobian and covariance each (thread r * 15 + c owns (r, c)); lanes 225..233 of the last wave build the
-// 3 x 3 blocks of F and V of the NEXT step while the matrix threads multiply with the present one, and lane 255 runs the
-// vector chain (delta_p / delta_q / delta_v and the navigation state) a chunk of samples ahead.  F and V are double
-// buffered, so a step costs two barriers; a chunk of LVI_PREINT_CHUNK samples costs three more.
-//
-// LDS per workgroup: jacobian, covariance and T (3 x 1800 B), two F (2 x 1800 B), two V (2 x 2160 B), LVI_PREINT_CHUNK
-// samples (896 B) and their step geometry (3584 B): 17.4 KB.  The V noise V' term is summed from V by the thread that owns
-// the element and is never stored.
+// One kernel, preint_run: the full form of the integration body of lvi_preint_dev.hpp, which describes it.  A launch runs a
+// list of at most LVI_PREINT_SLOTS jobs, one workgroup of 256 threads per job.  LDS per workgroup: jacobian, covariance and
+// T (3 x 1800 B), two F (2 x 1800 B), two V (2 x 2160 B), LVI_PREINT_CHUNK samples (896 B) and their step geometry
+// (3584 B): 17.4 KB.
 //
 // What follows from the caller's own arguments lives on the host: which slots exist, how many samples each holds, the biases
 // of the navigation state, and the estimator's acc_0 / gyr_0 / first_imu (the last sample pushed), which a launch receives as
@@ -17,12 +11,9 @@
 #include <cmath>
 #include <cstring>
 
-#include "../../include/lvi_preint.h"
-#include "lvi_dev.hpp"
-#include "lvi_preint_math.hpp"
+#include "lvi_preint_dev.hpp"
 
-using namespace lvi;
-namespace pm = lvi_preint_math;
+using namespace lvi_preint_dev;
 
 static_assert(sizeof(lvi_win_imu) == 16 + 8 * (1 + 3 + 4 + 3 + 3 + 3 + 225 + 225), "lvi_win_imu layout");
 static_assert(sizeof(lvi_preint_nav) == sizeof(pm::Nav) && sizeof(lvi_preint_nav) == 8 * 21, "lvi_preint_nav layout");
@@ -30,123 +21,29 @@ static_assert(sizeof(pm::StepGeom) == 8 * 28 && sizeof(pm::State) == 8 * 23, "lv
 
 namespace {
 
-constexpr int TB = 256, SLOTS = LVI_PREINT_SLOTS, CHUNK = LVI_PREINT_CHUNK, SD = 7;   // SD: doubles per sample: dt, acc, gyr
-constexpr int NN = pm::N * pm::N;
+constexpr int SLOTS = LVI_PREINT_SLOTS;
 
-enum { J_CREATE = 1, J_REPROP = 2, J_INTEGRATE = 4, J_NAV = 8 };
-
-// an IntegrationBase without its buffers
-struct SlotState {
-    pm::State s;
-    double linearized_acc[3], linearized_gyr[3];
-    double jacobian[NN], covariance[NN];
-};
-
-struct Job {
-    int32_t phys;                // the slot's state and the buffer the samples end in
-    int32_t src, src_first;      // the buffer and the sample the run starts at
-    int32_t dst_first;           // where the run lies in the slot's own buffer; a run read elsewhere is copied there
-    int32_t count, flags;
-    double ba[3], bg[3];         // J_CREATE, J_REPROP: linearized_ba / bg
-    double acc_0[3], gyr_0[3];   // J_CREATE: acc_0, gyr_0
-};
 struct Launch {
     Job job[SLOTS];
-    double q[pm::NV];            // the diagonal of noise
-    double G[3];
-    double nav_acc[3], nav_gyr[3];   // J_NAV: the estimator's acc_0, gyr_0 before the call (the host holds them)
+    FullArgs x;
     int32_t max_samples, reserved;
 };
 static_assert(sizeof(Launch) < 4096, "the launch description travels as a kernel argument");
 
 __global__ __launch_bounds__(TB) void preint_run(Launch L, SlotState* slots, double* smp, pm::Nav* nav)
 {
-    __shared__ double sJ[NN], sC[NN], sT[NN], sF[2][NN], sV[2][pm::N * pm::NV];
-    __shared__ double sS[CHUNK * SD];
+    __shared__ double sJ[NN], sF[2][NN], sS[CHUNK * SD], sC[NN], sT[NN], sV[2][pm::N * pm::NV];
     __shared__ pm::StepGeom sG[CHUNK];
-    const Job& jb = L.job[blockIdx.x];
-    const int tid = threadIdx.x, flags = jb.flags;
-    const bool mat = tid < NN, builder = tid >= NN && tid < NN + 9, chain = tid == TB - 1;
-    const int r = tid / pm::N, c = tid % pm::N, bi = (tid - NN) / 3, bj = (tid - NN) % 3;
-    SlotState* st = slots + jb.phys;
-    if (mat) {
-        if (flags & (J_CREATE | J_REPROP)) { sJ[tid] = r == c ? 1. : 0.; sC[tid] = 0.; }
-        else { sJ[tid] = st->jacobian[tid]; sC[tid] = st->covariance[tid]; }
-    }
-    pm::State s;
-    pm::Nav nv;
-    double e_acc[3], e_gyr[3];
-    if (chain) {
-        if (flags & J_CREATE) pm::state_reset(s, jb.acc_0, jb.gyr_0, jb.ba, jb.bg);
-        else if (flags & J_REPROP) pm::state_reset(s, st->linearized_acc, st->linearized_gyr, jb.ba, jb.bg);   // :40-49
-        else s = st->s;
-        if (flags & J_NAV) {
-            nv = *nav;
-            for (int k = 0; k < 3; k++) { e_acc[k] = L.nav_acc[k]; e_gyr[k] = L.nav_gyr[k]; }
-        }
-    }
-    __syncthreads();
-    if (flags & J_INTEGRATE) {
-        const double* src = smp + ((size_t)jb.src * L.max_samples + jb.src_first) * SD;
-        double* dst = smp + ((size_t)jb.phys * L.max_samples + jb.dst_first) * SD;
-        const bool copy = src != dst;
-        int par = 0;
-        for (int base = 0; base < jb.count; base += CHUNK) {
-            const int m = min(CHUNK, jb.count - base);
-            for (int t = tid; t < m * SD; t += TB) {
-                const double v = src[(size_t)base * SD + t];
-                sS[t] = v;
-                if (copy) dst[(size_t)base * SD + t] = v;
-            }
-            __syncthreads();
-            if (chain)
-                for (int k = 0; k < m; k++) {
-                    const double* x = sS + SD * k;
-                    pm::step_state(s, x[0], x + 1, x + 4, sG[k]);
-                    if (flags & J_NAV) {
-                        pm::nav_step(nv, e_acc, e_gyr, x[0], x + 1, x + 4, L.G);
-                        for (int a = 0; a < 3; a++) { e_acc[a] = x[1 + a]; e_gyr[a] = x[4 + a]; }
-                    }
-                }
-            __syncthreads();
-            if (builder) pm::build_entry(sG[0], bi, bj, sF[par], sV[par]);
-            __syncthreads();
-            for (int k = 0; k < m; k++) {
-                double jn = 0.;
-                if (mat) { jn = pm::f_dot(sF[par], r, sJ, c); sT[tid] = pm::f_dot(sF[par], r, sC, c); }
-                if (builder && k + 1 < m) pm::build_entry(sG[k + 1], bi, bj, sF[par ^ 1], sV[par ^ 1]);
-                __syncthreads();                                   // T is whole; nobody reads jacobian or covariance any more
-                if (mat) { sC[tid] = pm::tf_dot(sT, r, sF[par], c) + pm::vqv_dot(sV[par], L.q, r, c); sJ[tid] = jn; }
-                __syncthreads();                                   // the step's matrices are whole; F and V of this parity are free
-                par ^= 1;
-            }
-        }
-    }
-    if (mat) { st->jacobian[tid] = sJ[tid]; st->covariance[tid] = sC[tid]; }
-    if (chain) {
-        st->s = s;
-        if (flags & J_CREATE)
-            for (int k = 0; k < 3; k++) { st->linearized_acc[k] = jb.acc_0[k]; st->linearized_gyr[k] = jb.gyr_0[k]; }
-        if (flags & J_NAV) *nav = nv;
-    }
-}
-
-bool finite_n(const double* v, size_t n)
-{
-    for (size_t k = 0; k < n; k++)
-        if (!std::isfinite(v[k])) return false;
-    return true;
+    integrate_job<true>({{sJ, sF, sS, sG}, sC, sT, sV}, L.job[blockIdx.x], slots, smp, L.max_samples, &L.x, nav);
 }
 
 }  // namespace
 
 struct lvi_preint : Handle {
-    int max_samples = 0;
     lvi_preint_params P{};
-    SlotState* d_slots = nullptr; double* d_smp = nullptr; pm::Nav* d_nav = nullptr;
-    double* h_up = nullptr; char* h_down = nullptr; pm::Nav* h_nav = nullptr;      // pinned
-    size_t down_bytes = 0;
-    hipEvent_t up_done = nullptr; bool up_pending = false;      // the upload that last read h_up
+    SampleStore smp;                                            // SLOTS slots
+    SlotState* d_slots = nullptr; pm::Nav* d_nav = nullptr;
+    char* h_down = nullptr; pm::Nav* h_nav = nullptr;           // pinned
     // the host's mirror: what a call is checked against
     int map[SLOTS] = {};                                        // window slot -> the physical slot that holds it
     int count[SLOTS] = {}; bool created[SLOTS] = {};            // by physical slot
@@ -158,27 +55,24 @@ namespace {
 
 template <class A, class B> void carve(A& a, B& pin, lvi_preint* h)
 {
-    const size_t ms = (size_t)h->max_samples;
-    h->down_bytes = std::max(sizeof(SlotState), sizeof(double) * SD * ms);
+    h->smp.carve(a, pin, SLOTS);
     h->d_slots = a.template alloc<SlotState>(SLOTS);
-    h->d_smp = a.template alloc<double>(SLOTS * ms * SD);
     h->d_nav = a.template alloc<pm::Nav>(1);
-    h->h_up = pin.template alloc<double>(ms * SD);
-    h->h_down = pin.template alloc<char>(h->down_bytes);
+    h->h_down = pin.template alloc<char>(std::max(sizeof(SlotState), h->smp.bytes(h->smp.max_samples)));
     h->h_nav = pin.template alloc<pm::Nav>(1);
 }
 
 void fill_launch(const lvi_preint* h, Launch& L)
 {
     std::memset(&L, 0, sizeof(L));
-    pm::noise_diag(h->P.acc_n, h->P.gyr_n, h->P.acc_w, h->P.gyr_w, L.q);
-    for (int k = 0; k < 3; k++) L.G[k] = h->P.G[k];
-    L.max_samples = h->max_samples;
+    pm::noise_diag(h->P.acc_n, h->P.gyr_n, h->P.acc_w, h->P.gyr_w, L.x.q);
+    for (int k = 0; k < 3; k++) L.x.G[k] = h->P.G[k];
+    L.max_samples = h->smp.max_samples;
 }
 
 void launch(lvi_preint* h, const Launch& L, int jobs)
 {
-    hipLaunchKernelGGL(preint_run, dim3(jobs), dim3(TB), 0, h->stream, L, h->d_slots, h->d_smp, h->d_nav);
+    hipLaunchKernelGGL(preint_run, dim3(jobs), dim3(TB), 0, h->stream, L, h->d_slots, h->smp.d_smp, h->d_nav);
     LVI_HIP(hipGetLastError());
 }
 
@@ -217,13 +111,6 @@ pm::Nav nav_identity()
     return n;
 }
 
-// one download into the pinned buffer and the call's wait
-void download(lvi_preint* h, const void* d, size_t bytes)
-{
-    LVI_HIP(hipMemcpyAsync(h->h_down, d, bytes, hipMemcpyDeviceToHost, h->stream));
-    LVI_HIP(hipStreamSynchronize(h->stream));
-}
-
 int32_t slot_of(lvi_preint* h, int32_t slot, int* phys)
 {
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null argument");
@@ -236,12 +123,7 @@ int32_t slot_of(lvi_preint* h, int32_t slot, int* phys)
 void to_record(const SlotState& st, lvi_win_imu* o)
 {
     o->pose_i = o->speed_bias_i = o->pose_j = o->speed_bias_j = 0;
-    o->sum_dt = st.s.sum_dt;
-    for (int k = 0; k < 3; k++) {
-        o->delta_p[k] = st.s.delta_p[k]; o->delta_v[k] = st.s.delta_v[k];
-        o->linearized_ba[k] = st.s.linearized_ba[k]; o->linearized_bg[k] = st.s.linearized_bg[k];
-    }
-    for (int k = 0; k < 4; k++) o->delta_q[k] = st.s.delta_q[k];
+    copy_pre(st.s, *o);
     std::memcpy(o->jacobian, st.jacobian, sizeof(o->jacobian));
     std::memcpy(o->covariance, st.covariance, sizeof(o->covariance));
 }
@@ -254,9 +136,7 @@ int32_t lvi_preint_abi_version(void) { return LVI_PREINT_ABI_VERSION; }
 
 void lvi_preint_params_default(lvi_preint_params* p)
 {
-    if (!p) return;
-    p->acc_n = 0.08; p->gyr_n = 0.004; p->acc_w = 0.00004; p->gyr_w = 2.0e-6;
-    p->G[0] = 0.; p->G[1] = 0.; p->G[2] = 9.8;
+    if (p) noise_defaults(p);
 }
 
 int32_t lvi_preint_create(int32_t device, const lvi_preint_caps* caps, lvi_preint** out)
@@ -266,31 +146,21 @@ int32_t lvi_preint_create(int32_t device, const lvi_preint_caps* caps, lvi_prein
     if (!caps) return fail(LVI_ERR_INVALID_ARG, "null argument");
     if (caps->max_samples < 1 || caps->max_samples > LVI_PREINT_MAX_SAMPLES) return fail(LVI_ERR_INVALID_ARG, "max_samples is outside 1..LVI_PREINT_MAX_SAMPLES");
     return create_handle(device, out, lvi_preint_destroy,
-        [&](lvi_preint* h) { h->max_samples = caps->max_samples; lvi_preint_params_default(&h->P); forget(h); },
+        [&](lvi_preint* h) { h->smp.max_samples = caps->max_samples; lvi_preint_params_default(&h->P); forget(h); },
         [&](lvi_preint* h) -> int32_t {
             h->open(device, [&](auto& dev, auto& pin) { carve(dev, pin, h); });
-            LVI_HIP(hipEventCreateWithFlags(&h->up_done, hipEventDisableTiming));
+            h->smp.open();
             LVI_HIP(hipMemsetAsync(h->d_slots, 0, sizeof(SlotState) * SLOTS, h->stream));
             return upload_nav(h, nav_identity());
         });
 }
 
-void lvi_preint_destroy(lvi_preint* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->up_done) (void)hipEventDestroy(h->up_done);
-    h->close();
-    delete h;
-}
+void lvi_preint_destroy(lvi_preint* h) { destroy_with_store(h); }
 
 int32_t lvi_preint_set_params(lvi_preint* h, const lvi_preint_params* p)
 {
     if (!h || !p) return fail(LVI_ERR_INVALID_ARG, "null argument");
-    const double v[7] = {p->acc_n, p->gyr_n, p->acc_w, p->gyr_w, p->G[0], p->G[1], p->G[2]};
-    if (!finite_n(v, 7) || p->acc_n < 0 || p->gyr_n < 0 || p->acc_w < 0 || p->gyr_w < 0)
-        return fail(LVI_ERR_INVALID_ARG, "the parameters must be finite and the noise values >= 0");
+    if (!noise_valid(p)) return fail(LVI_ERR_INVALID_ARG, "the parameters must be finite and the noise values >= 0");
     h->P = *p;
     return LVI_OK;
 }
@@ -334,7 +204,7 @@ int32_t lvi_preint_push(lvi_preint* h, int32_t frame_count, int32_t n, const dou
     if (n == 0) return LVI_OK;
     const int phys = h->map[frame_count];
     const bool integrate = frame_count != 0;
-    if (integrate && (h->created[phys] ? h->count[phys] : 0) + (int64_t)n > h->max_samples)
+    if (integrate && (h->created[phys] ? h->count[phys] : 0) + (int64_t)n > h->smp.max_samples)
         return fail(LVI_ERR_CAPACITY, "the slot would exceed max_samples");
     return guarded(h->device, [&]() -> int32_t {
         Launch L;
@@ -348,20 +218,11 @@ int32_t lvi_preint_push(lvi_preint* h, int32_t frame_count, int32_t n, const dou
             j.flags |= J_CREATE;
             for (int k = 0; k < 3; k++) { j.ba[k] = h->nav_Ba[k]; j.bg[k] = h->nav_Bg[k]; j.acc_0[k] = a0[k]; j.gyr_0[k] = g0[k]; }
         }
-        for (int k = 0; k < 3; k++) { L.nav_acc[k] = a0[k]; L.nav_gyr[k] = g0[k]; }
+        for (int k = 0; k < 3; k++) { L.x.nav_acc[k] = a0[k]; L.x.nav_gyr[k] = g0[k]; }
         if (integrate) {
             j.flags |= J_INTEGRATE | J_NAV;
             j.src_first = j.dst_first = at; j.count = n;
-            if (h->up_pending) LVI_HIP(hipEventSynchronize(h->up_done));       // the staging buffer is free again
-            for (int k = 0; k < n; k++) {
-                double* o = h->h_up + (size_t)SD * k;
-                o[0] = dt[k];
-                for (int a = 0; a < 3; a++) { o[1 + a] = acc[3 * (size_t)k + a]; o[4 + a] = gyr[3 * (size_t)k + a]; }
-            }
-            LVI_HIP(hipMemcpyAsync(h->d_smp + ((size_t)phys * h->max_samples + at) * SD, h->h_up, sizeof(double) * SD * (size_t)n, hipMemcpyHostToDevice,
-                                   h->stream));
-            LVI_HIP(hipEventRecord(h->up_done, h->stream));
-            h->up_pending = true;
+            h->smp.stage(h->stream, phys, at, n, dt, acc, gyr);
         }
         if (j.flags) launch(h, L, 1);                              // frame_count == 0 on a slot that exists: only acc_0 and gyr_0 move
         h->created[phys] = true;
@@ -418,7 +279,7 @@ int32_t lvi_preint_slide_new(lvi_preint* h)
     if (!h) return fail(LVI_ERR_INVALID_ARG, "null argument");
     const int p9 = h->map[SLOTS - 2], p10 = h->map[SLOTS - 1];
     if (!h->created[p9] || !h->created[p10]) return fail(LVI_ERR_STATE, "slots 9 and 10 must exist");
-    if (h->count[p9] + h->count[p10] > h->max_samples) return fail(LVI_ERR_CAPACITY, "slot 9 has too little room for slot 10's samples");
+    if (h->count[p9] + h->count[p10] > h->smp.max_samples) return fail(LVI_ERR_CAPACITY, "slot 9 has too little room for slot 10's samples");
     return guarded(h->device, [&]() -> int32_t {
         Launch L;
         fill_launch(h, L);
@@ -458,15 +319,7 @@ int32_t lvi_preint_get_samples(lvi_preint* h, int32_t slot, int32_t cap, int32_t
     if (count) *count = n;
     if ((!dt && !acc && !gyr) || n == 0) return LVI_OK;
     return guarded(h->device, [&]() -> int32_t {
-        download(h, h->d_smp + (size_t)phys * h->max_samples * SD, sizeof(double) * SD * (size_t)n);
-        const double* v = reinterpret_cast<const double*>(h->h_down);
-        for (int k = 0; k < n; k++) {
-            if (dt) dt[k] = v[SD * k];
-            for (int a = 0; a < 3; a++) {
-                if (acc) acc[3 * k + a] = v[SD * k + 1 + a];
-                if (gyr) gyr[3 * k + a] = v[SD * k + 4 + a];
-            }
-        }
+        h->smp.fetch(h, phys, n, dt, acc, gyr);
         return LVI_OK;
     });
 }
@@ -486,12 +339,7 @@ int32_t lvi_preint_evaluate(lvi_preint* h, int32_t slot, const double* pose_i, c
         double *S = buf.data(), *work = S + 225, *r = work + 675, *J = r + 15;
         if (!im::imu_sqrt_info(st.covariance, S, work)) return fail(LVI_ERR_STATE, "the slot's covariance is not positive definite");
         im::ImuPre p;
-        p.sum_dt = st.s.sum_dt;
-        for (int k = 0; k < 3; k++) {
-            p.delta_p[k] = st.s.delta_p[k]; p.delta_v[k] = st.s.delta_v[k];
-            p.linearized_ba[k] = st.s.linearized_ba[k]; p.linearized_bg[k] = st.s.linearized_bg[k];
-        }
-        for (int k = 0; k < 4; k++) p.delta_q[k] = st.s.delta_q[k];
+        copy_pre(st.s, p);
         std::memcpy(p.jacobian, st.jacobian, sizeof(p.jacobian));
         im::imu_eval_raw(pose_i, sb_i, pose_j, sb_j, p, h->P.G, r, jacobians ? J : nullptr);
         for (int i = 0; i < 15; i++) residual[i] = im::imu_info_dot(S, i, r, 1, 0);

@@ -110,13 +110,6 @@ template <class A, class B> void carve(A& a, B& pin, lvi_relpose* h)
     h->h_down = pin.template alloc<char>(out_bytes((int)mp));
 }
 
-bool finite_n(const double* v, size_t n)
-{
-    for (size_t k = 0; k < n; k++)
-        if (!std::isfinite(v[k])) return false;
-    return true;
-}
-
 void identity_result(lvi_relpose_result* r)
 {
     std::memset(r, 0, sizeof(*r));

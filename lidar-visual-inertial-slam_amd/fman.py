@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
+from ._abi import _arr, _d
 from .marg import PROJECTION_DTYPE
 
 _P = C.POINTER
@@ -71,23 +72,12 @@ def bind(lib):
     return lib.bind(FMAN_SIGNATURES)
 
 
-def _d(a):
-    return a.ctypes.data_as(_P(_f64))
-
-
 def _i(a):
     return a.ctypes.data_as(_P(_i32))
 
 
 def _fields(s):
     return {k: getattr(s, k) for k, _ in s._fields_}
-
-
-def _arr(a, shape):
-    a = np.ascontiguousarray(a, np.float64)
-    if a.shape != shape:
-        raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
-    return a
 
 
 class FeatureTable(A.Owned):

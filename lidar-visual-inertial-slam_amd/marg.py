@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
+from ._abi import _d
 
 _P = C.POINTER
 _vp, _i32, _f64 = C.c_void_p, C.c_int32, C.c_double
@@ -67,10 +68,6 @@ MARG_SIGNATURES = {
 def bind(lib):
     """set the marg signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
     return lib.bind(MARG_SIGNATURES)
-
-
-def _d(a):
-    return a.ctypes.data_as(_P(_f64))
 
 
 def _i(a):

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
+from ._abi import _arr, _d
 from .win import IMU_DTYPE
 
 _P = C.POINTER
@@ -53,17 +54,6 @@ PREINT_SIGNATURES = {
 def bind(lib):
     """set the preintegration signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
     return lib.bind(PREINT_SIGNATURES)
-
-
-def _d(a):
-    return a.ctypes.data_as(_P(_f64))
-
-
-def _arr(a, shape):
-    a = np.ascontiguousarray(a, np.float64)
-    if a.shape != shape:
-        raise ValueError(f"expected an array of shape {shape}, got {a.shape}")
-    return a
 
 
 class ImuWindow(A.Owned):

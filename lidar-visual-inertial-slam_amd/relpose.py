@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
+from ._abi import _d
 from . import fmat as _fmat
 from .fmat import FmatInfo
 
@@ -55,10 +56,6 @@ def bind(lib):
     """set the two-view signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
     _fmat.bind(lib)
     return lib.bind(RELPOSE_SIGNATURES)
-
-
-def _d(a):
-    return a.ctypes.data_as(_P(_f64))
 
 
 def _pose_dict(p):

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi as A
+from ._abi import _d
 from .marg import PROJECTION_DTYPE, MargProjection  # noqa: F401
 
 _P = C.POINTER
@@ -79,10 +80,6 @@ WIN_SIGNATURES = {
 def bind(lib):
     """set the window-solve signatures on a loaded product Library (idempotent); raises AttributeError on a missing export"""
     return lib.bind(WIN_SIGNATURES)
-
-
-def _d(a):
-    return a.ctypes.data_as(_P(_f64))
 
 
 def _i(a):

@@ -15,6 +15,7 @@ import align_ref as R
 pytestmark = pytest.mark.gpu
 
 MAXF, MAXS = 66, 48
+PRE_FIELDS = ("sum_dt", "delta_p", "delta_q", "delta_v", "linearized_ba", "linearized_bg", "linearized_acc", "linearized_gyr", "jacobian")
 
 
 @pytest.fixture(scope="module")
@@ -169,6 +170,40 @@ def test_frame_records_equal_an_imu_window_slot(pkg, hip, al):
         same("repropagate")
     finally:
         win.close()
+
+
+def test_the_split_into_pushes_does_not_matter(pkg, hip):
+    """one frame's 35 samples one at a time, as 1 + 16 + 18 and at once: the same bytes, and the reference's record"""
+    dt, acc, gyr = R.PR.samples(79, 36, vary=True, zero_dt_at=9)       # the first sample only sets acc_0 / gyr_0
+    ba, bg = np.array([0.01, -0.02, 0.005]), np.array([1e-3, 2e-3, -1e-3])
+
+    def run(dev, cuts):
+        dev.push_imu(dt[:1], acc[:1], gyr[:1])
+        dev.add_frame(1.0, ba, bg)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            dev.push_imu(dt[a:b], acc[a:b], gyr[a:b])
+        dev.add_frame(2.0, ba, bg)
+
+    results = {}
+    for name, cuts in (("one at a time", list(range(1, 37))), ("1, 16, 18", [1, 2, 18, 36]), ("at once", [1, 36])):
+        dev = pkg.ImuAligner(hip, max_frames=4, max_samples=64)
+        try:
+            run(dev, cuts)
+            f = dev.frame(1)
+        finally:
+            dev.close()
+        assert f["samples"] == 35 and sorted(f["pre"]) == sorted(PRE_FIELDS)
+        results[name] = f
+    ref = R.Aligner(max_frames=4, max_samples=64)
+    run(ref, [1, 36])
+    want = ref.record(1)
+    once = results["at once"]
+    for name, f in results.items():
+        for k in PRE_FIELDS:
+            assert np.asarray(f["pre"][k], np.float64).tobytes() == np.asarray(once["pre"][k], np.float64).tobytes(), (name, k)
+            assert np.array_equal(np.ravel(f["pre"][k]), np.ravel(want["pre"][k])), (name, k)
+        for k, v in (("dt", dt), ("acc", acc), ("gyr", gyr)):
+            assert f[k].tobytes() == once[k].tobytes() and f[k].tobytes() == np.ascontiguousarray(v[1:]).tobytes(), (name, k)
 
 
 # ---- errors leave the state as it was -----------------------------------------------------------------------------------

@@ -13,6 +13,8 @@ JSON line.  The time of each launch comes from a kernel trace of a run of this t
     timeout -k 10 300 python tools/diag/align_time.py
     timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d D -- python tools/diag/align_time.py --frames 30 --rounds 30 --no-host
     python tools/diag/align_time.py --trace D        # median microseconds per launch of every align_* kernel, by grid size
+
+--lib PATH times another build of liblvi_hip.so (the parent commit's, say) in place of the tree's.
 """
 import argparse
 import csv
@@ -142,13 +144,14 @@ def main():
     ap.add_argument("--frames", default="11,30,100")
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--trace", default=None)
+    ap.add_argument("--lib", default=None, help="another build of liblvi_hip.so to time instead of the tree's")
     a = ap.parse_args()
     if a.trace:
         print(json.dumps(_trace(a.trace)))
         return
     pkg = graft.import_package()
     import align_ref as R
-    hip = pkg.load_hip()
+    hip = pkg._abi.Library(a.lib) if a.lib else pkg.load_hip()
     out = dict(rounds=a.rounds, samples=a.samples)
     with tempfile.TemporaryDirectory() as tmp:
         for F in (int(t) for t in a.frames.split(",")):

@@ -11,6 +11,8 @@ is rebuilt outside the timed window.  The host column is the median of the same 
 -ffp-contract=off), the eleven chains one after the other.  No threshold is set on any of the numbers.  Prints one JSON line.
 
     timeout -k 10 300 python tools/diag/preint_time.py
+
+--lib PATH times another build of liblvi_hip.so (the parent commit's, say) in place of the tree's.
 """
 import argparse
 import json
@@ -83,6 +85,7 @@ def _host(pkg, tmp, dt, acc, gyr, chains, rounds):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=200)
+    ap.add_argument("--lib", default=None, help="another build of liblvi_hip.so to time instead of the tree's")
     a = ap.parse_args()
     try:
         import torch
@@ -92,7 +95,7 @@ def main():
         pass
     pkg = graft.import_package()
     import preint_ref as R
-    hip = pkg.load_hip()
+    hip = pkg._abi.Library(a.lib) if a.lib else pkg.load_hip()
     w = pkg.ImuWindow(hip, max_samples=512)
     nav = dict(P=np.zeros(3), R=np.eye(3), V=np.array([1.0, 0.0, 0.0]), Ba=np.array([0.01, -0.02, 0.015]), Bg=np.array([0.001, 0.002, -0.0015]))
     s20, s200 = R.samples(1, 20), R.samples(2, 200)
